@@ -9,11 +9,15 @@ Inputs are resident in HBM when the timed region starts.
 
     python bench.py --gpus N --steps K --warmup W                 # config M, weak scaling: 4096 problems per GPU
     python bench.py --config D|E --gpus N                         # BASELINE configs[3] / [4]: 4096 / 8192 problems sharded over N GPUs
+    python bench.py ... --full                                    # plus every figure listed below roofline
+    python bench.py ... --dump-outputs DIR                        # plus DIR/<name>.npy: the last timed step's results
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line.  Besides the contract keys it carries
   roofline      dominant kernel of the timed launch against the HBM roof, algorithmic bytes =
                 SURVEY §8d per-evaluation bytes x evaluations actually performed in the launch
+A plain run stops there: set-up, warm-up, the timed steps, the outputs and the line.  With --full the line also carries
+(each from runs of its own after the timed steps; --no-cpu / --no-extras leave out the first / the others)
   cpu_baseline  the CPU oracle (oracle/, kind "port") solving a bounded sample of the same
                 workload on the host cores of this box (rank 0, N=1 only), one pinned thread per physical core
   to_convergence  the metric's own mode ("SQP-to-convergence"): NPSOL-equivalent cold start run to NPSOL's tolerances, and the
@@ -32,6 +36,24 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BYTES = 64 * 10 ** 6  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one float64 .npy per result array (one row per problem; the integer counters are exact in float64).  Beyond
+    DUMP_BYTES the same fixed, seeded sample of rows is written from every array, and its row indices as sampled_rows.npy."""
+    import numpy as np
+    arrs = {k: v.detach().cpu().numpy().astype(np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrs.values())))
+    row_bytes = sum(a[0].nbytes for a in arrs.values())
+    os.makedirs(path, exist_ok=True)
+    head = 1024 * (len(arrs) + 1)   # room for the .npy headers
+    if n * row_bytes > DUMP_BYTES - head:
+        rows = np.sort(np.random.default_rng(0).choice(n, (DUMP_BYTES - head) // (row_bytes + 8), replace=False))
+        arrs = {k: a[rows] for k, a in arrs.items()}
+        arrs["sampled_rows"] = rows.astype(np.float64)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def orc_off(spec):
@@ -125,11 +147,18 @@ def main():
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"],
                     help="weak: --batch problems per GPU (default for M / B); strong: --batch problems in all, split over the GPUs (default for D / E)")
     ap.add_argument("--hessian", type=int, default=-1, help="configs D / E: 2 structured Newton mode, 3 QP-based SQP step (default: 2 for D, 3 for E)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: leave out the figures other than the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the CPU baseline, the other modes, sizes and configurations and the standalone kernels")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step as DIR/<name>.npy (float64; a fixed row sample beyond %d MB)" % (DUMP_BYTES // 10 ** 6))
     args = ap.parse_args()
-    # the CPU baseline pins one thread per physical core: the OpenMP runtime reads these when it starts
-    os.environ.setdefault("OMP_PROC_BIND", "spread"); os.environ.setdefault("OMP_PLACES", "cores")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.full:
+        # the CPU baseline pins one thread per physical core: the OpenMP runtime reads these when it starts
+        os.environ.setdefault("OMP_PROC_BIND", "spread"); os.environ.setdefault("OMP_PLACES", "cores")
 
     import numpy as np
     import torch
@@ -191,14 +220,15 @@ def main():
         if i is not None:
             ev[i][1].record()
         if world > 1:  # the only collective: final gather of the results (RCCL over xGMI)
-            shard.gather_results(x, out["objective"], total, world, inform=out["inform"], iters=out["iters"])
+            return shard.gather_results(x, out["objective"], total, world, inform=out["inform"], iters=out["iters"])
+        return x, out["objective"], out["inform"], out["iters"]
 
     for _ in range(args.warmup):
         step()
     sync_all()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(i)
+        last = step(i)
     sync_all()
     dt = shard.max_over_ranks(time.perf_counter() - t0, world, dev)
 
@@ -276,7 +306,15 @@ def main():
     if traffic:
         res["roofline"]["traffic_over_alg"] = traffic / alg_bytes
 
-    if rank == 0 and world == 1 and not args.no_extras and not large:
+    # what a caller of the timed path receives from its last step (all problems: gathered over the ranks when there are several),
+    # written before any --full measurement reuses x
+    if rank == 0 and args.dump_outputs:
+        names = dict(zip(("x", "objective", "inform", "iters"), last))
+        if world == 1:
+            names["nfev"] = out["nfev"]
+        dump_outputs(args.dump_outputs, names)
+
+    if args.full and rank == 0 and world == 1 and not args.no_extras and not large:
         # ---- the metric's own mode, SQP to convergence, two ways ----
         def to_conv(opt, nrep=5):
             wc = torch.empty(plan.workspace_bytes(B, opt), dtype=torch.uint8, device=dev)
@@ -669,7 +707,7 @@ def main():
                                                             "set_grids_with_preconditioner_s": setup2_s}
         del og, xg, pg, xs_g
 
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         # ---- CPU baseline: the oracle on a bounded sample of the same workload, on the host cores of this box.  Two flavours
         #      (SURVEY 8d): "ref" = the reference's loops and dense temporaries (cost.c:117-134), "opt" = banded, allocation-free
         #      evaluation.  One pinned thread per PHYSICAL core (OMP_PLACES=cores, OMP_PROC_BIND=spread), >= 32 problems per thread;

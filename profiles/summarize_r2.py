@@ -21,7 +21,7 @@ for r in tr:
     dur[short(r["Kernel_Name"])].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6)
 bench = json.loads(open(os.path.join(SRC, "bench.json")).read().strip().splitlines()[-1])
 json.dump(bench, open(os.path.join(DST, "r02_bench.json"), "w"), indent=1)
-summ = {"how": "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 1 --no-cpu (tools/prof_r2.sh); durations in ms"}
+summ = {"how": "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 1 --full --no-cpu (tools/prof_r2.sh); durations in ms"}
 label = {"sqp_kernel<0, 6, 6, 128, 4, false, false, 4, false>": "headline sqp_kernel: 4096 x config M, 50 fixed majors (identity cold start)",
          "sqp_kernel<0, 6, 6, 128, 4, false, true, 4, false>": "sqp_kernel config M to convergence (4096 and 65536 problems mixed)",
          "sqp_kernel<4, 4, 8, 256, 4, false, true, 0, true>": "sqp_kernel config D, 512 problems, structured Newton mode",

@@ -26,7 +26,7 @@ for r in tr:
     dur[short(r["Kernel_Name"])].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6)
 bench = json.loads(open(os.path.join(SRC, "bench.json")).read().strip().splitlines()[-1])
 json.dump(bench, open(os.path.join(DST, "r03_bench.json"), "w"), indent=1)
-summ = {"how": "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 1 --no-cpu (tools/prof_r3.sh); durations in ms; device sources " + SHA}
+summ = {"how": "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 1 --full --no-cpu (tools/prof_r3.sh); durations in ms; device sources " + SHA}
 for k, d in sorted(dur.items()):
     if any(s in k for s in ("sqp_", "eval_", "grid_")):
         d = sorted(d)

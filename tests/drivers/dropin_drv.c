@@ -10,7 +10,9 @@
  * "sequence": vanderpol, kincar, vanderpol again in ONE process (ntg() keeps file-scope state like the reference,
  * ntg.c:17-41: repeated calls with different shapes must not leak into each other); options persist across the calls
  * as NPSOL's do.  "kincarR": kincar, then the returned factor R (row-major, n x n).
- * Usage: dropin_drv vanderpol|kincar|obstacle|ineq|sequence|kincarR   -> prints "RESULT inform objective c0 c1 ..."
+ * A second argument "files" also writes the solution with PrintVector ("coef1") and the initial-constraint matrix with PrintMatrix
+ * ("lic"), and frees the DoubleMatrix storage, as the examples do: the remaining helpers of include/ntg.h are called here too.
+ * Usage: dropin_drv vanderpol|kincar|obstacle|ineq|sequence|kincarR [files]   -> prints "RESULT inform objective c0 c1 ..."
  */
 #include <math.h>
 #include "ntg.h"
@@ -35,7 +37,7 @@ static void obs_con(int *mode, int *nstate, int *i, double *c, double **dc, doub
 	if (*mode == 0 || *mode == 2) c[0] = dx * dx + dy * dy;
 	if (*mode == 1 || *mode == 2) { for (v = 0; v < 6; v++) dc[0][v] = 0; dc[0][0] = 2 * dx; dc[0][3] = 2 * dy; }
 }
-static int g_obstacle = 0, g_printR = 0;
+static int g_obstacle = 0, g_printR = 0, g_files = 0;
 
 static int run(int nout, int order_, int mult_, int ninterv_, int nbps, int nlic, double **lic, int nlfc, double **lfc,
                double *lowerb, double *upperb, void (*ucf)(int *, int *, int *, double *, double *, double **),
@@ -59,6 +61,7 @@ static int run(int nout, int order_, int mult_, int ninterv_, int nbps, int nlic
 	    0, NULL, g_obstacle ? 2 : 0, g_obstacle ? ctav : NULL, 0, NULL,
 	    lowerb, upperb, 0, NULL, 1, ucf, 0, NULL, 0, NULL, ntav, tav, 0, NULL,
 	    istate, clambda, R, &inform, &objective);
+	if (g_files) PrintVector("coef1", coef, ncoef);
 	printf("RESULT %d %.17g", inform, objective);
 	for (i = 0; i < ncoef; i++) printf(" %.17g", coef[i]);
 	printf("\n");
@@ -83,6 +86,7 @@ static int run(int nout, int order_, int mult_, int ninterv_, int nbps, int nlic
 static int one(int argc, char **argv);
 int main(int argc, char **argv)
 {
+	if (argc > 2 && !strcmp(argv[2], "files")) g_files = 1;
 	if (argc > 1 && !strcmp(argv[1], "sequence")) {
 		char *a1[2] = {argv[0], "vanderpol"}, *a2[2] = {argv[0], "kincar"};
 		int rc = one(2, a1);
@@ -98,10 +102,13 @@ static int one(int argc, char **argv)
 	if (argc > 1 && !strcmp(argv[1], "vanderpol")) {
 		static AV tav[3] = {{0, 0}, {0, 1}, {0, 2}};
 		double **lic = DoubleMatrix(2, 3), **lfc = DoubleMatrix(1, 3), lo[3], up[3];
+		int i;
 		lic[0][0] = 1.0; lo[0] = up[0] = 1.0;
 		lic[1][1] = 1.0; lo[1] = up[1] = 0.0;
 		lfc[0][0] = -1.0; lfc[0][1] = 1.0; lo[2] = up[2] = 1.0;
-		return run(1, 5, 3, 2, 20, 2, lic, 1, lfc, lo, up, vdp_cost, 3, tav);
+		i = run(1, 5, 3, 2, 20, 2, lic, 1, lfc, lo, up, vdp_cost, 3, tav);
+		if (g_files) { FreeDoubleMatrix(lic); FreeDoubleMatrix(lfc); }
+		return i;
 	} else {
 		static AV tav[2] = {{0, 2}, {1, 2}};
 		Matrix *lic = MakeMatrix(6, 6), *lfc = MakeMatrix(6, 6);
@@ -116,6 +123,7 @@ static int one(int argc, char **argv)
 			g_obstacle = 1; lo[12] = 9.0; up[12] = 1e20;
 			return run(2, 6, 3, 10, 51, 6, lic->elements, 6, lfc->elements, lo, up, car_cost, 2, tav);
 		}
+		if (g_files) PrintMatrix("lic", lic);
 		return run(2, 5, 3, 2, 20, 6, lic->elements, 6, lfc->elements, lo, up, car_cost, 2, tav);
 	}
 }
