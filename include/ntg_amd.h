@@ -50,6 +50,7 @@ extern "C" {
 #define NTG_FAM_QUADROTOR 4  /* 4 outputs x,y,z,yaw, maxderiv 5: snap^2 + yaw''^2; rows: thrust^2 = x''^2+y''^2+(z''+g)^2, speed^2 */
 #define NTG_FAM_MANIP 5      /* 3 joints per planar arm, maxderiv 3: sum q''^2; one tip-height row sin(qa)+sin(qa+qb)+sin(qa+qb+qc) per arm */
 #define NTG_FAM_HOST (-1)    /* host function pointers (ntg() drop-in path only) */
+#define NTG_FAM_MODULE_BASE 64  /* ids of families loaded from modules (ntg_family_load) start here */
 
 typedef struct { int output; int deriv; } ntg_av; /* == AV of av.h:22-26 */
 
@@ -107,6 +108,16 @@ typedef struct ntg_plan ntg_plan;
 int ntg_device_count(void);
 const char *ntg_last_error(void);
 void ntg_default_opts(ntg_solve_opts *o);
+
+/* User problem families (include/ntg_amd_family.hpp, INTEGRATION.md "Your own problem family"): load a module built from that
+ * header and get its family id (>= NTG_FAM_MODULE_BASE) for ntg_spec.family.  No HIP call: works without a device.  The same
+ * file loaded again returns the same id; modules stay loaded for the life of the process.  NTG_E_BADARG (with the reason in
+ * ntg_last_error) for a missing file, a shared object without the module entry point, or a module built against other
+ * headers than this library (ABI stamp or structure sizes differ). */
+int ntg_family_load(const char *path, int *family);
+/* what a loaded module declares: name (NUL-terminated, truncated to name_len), maxderiv of every output, the most nonlinear
+ * rows of each kind a plan may use, the outputs a plan must have (0 = any).  Any output pointer may be NULL. */
+int ntg_family_info(int family, char *name, int name_len, int *maxderiv, int *nnlic, int *nnltc, int *nnlfc, int *nout);
 
 /* Build the device-resident, batch-shared part of a problem: basis blocks and offsets (HIP
  * basis kernel), banded linear-constraint rows A, (A A')^-1, optional preconditioner. */

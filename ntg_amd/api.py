@@ -79,6 +79,8 @@ def lib():
         L.ntg_plan_clear_grids.restype = None
         L.ntg_batch_kincar_reverse.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
         L.ntg_batch_mpc_shift.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ntg_family_load.argtypes = [C.c_char_p, ip]
+        L.ntg_family_info.argtypes = [C.c_int, C.c_char_p, C.c_int] + [ip] * 5
         _lib = L
     return _lib
 
@@ -324,6 +326,22 @@ class Plan:
                                      _ptr(out["objective"]), _ptr(out["inform"]), _ptr(out["iters"]), _ptr(out["nfev"]),
                                      _ptr(out.get("clambda")), _ptr(work), work.numel() * work.element_size(), self._stream()))
         return out
+
+
+def load_family(path: str) -> int:
+    """Load a family module (ntg_amd.family.build_module) and return its id for Spec.family.  The same file loaded again returns
+    the same id.  Needs no GPU."""
+    fam = C.c_int()
+    _check(lib().ntg_family_load(os.fsencode(path), C.byref(fam)))
+    return fam.value
+
+
+def family_info(family: int) -> dict:
+    """What a loaded module declares: name, maxderiv, the most nonlinear rows of each kind, the outputs a plan must have (0: any)."""
+    name = C.create_string_buffer(256)
+    v = [C.c_int() for _ in range(5)]
+    _check(lib().ntg_family_info(family, name, len(name), *[C.byref(x) for x in v]))
+    return dict(name=name.value.decode(), maxderiv=v[0].value, nnlic=v[1].value, nnltc=v[2].value, nnlfc=v[3].value, nout=v[4].value)
 
 
 def basis_batch(knots, bps, order: int, mult: int, maxderiv: int):

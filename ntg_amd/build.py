@@ -1,5 +1,7 @@
 """Build libntg_amd.so in-tree with hipcc for gfx950 (no JIT cache: the .so travels with the repo)."""
 from __future__ import annotations
+import glob
+import hashlib
 import os
 import subprocess
 import sys
@@ -8,8 +10,21 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libntg_amd.so")
 SOURCES = ["kernels.hip", "grids.hip", "fam_kincar.hip", "fam_kincar_chm.hip", "fam_kincar_wave.hip", "fam_vanderpol.hip", "fam_testfam.hip", "fam_obstacle.hip", "fam_quadrotor.hip",
-           "fam_manip.hip", "plan.cpp", "ntg_host.cpp"]
-HEADERS = ["ntg_dev.hpp", "solve_impl.hpp", "newton.hpp", "qpdual.hpp", "eval_fast.hpp", "solve_wave.hpp", "families.hpp", "linesearch.hpp", "plan.hpp", "../../include/ntg_amd.h", "../../include/ntg.h"]
+           "fam_manip.hip", "plan.cpp", "ntg_host.cpp", "family_registry.cpp"]
+HEADERS = ["ntg_dev.hpp", "solve_impl.hpp", "newton.hpp", "qpdual.hpp", "eval_fast.hpp", "solve_wave.hpp", "families.hpp", "linesearch.hpp", "plan.hpp", "../../include/ntg_amd.h", "../../include/ntg.h",
+           "family_module.hpp", "../../include/ntg_amd_family.hpp"]
+MODULES = os.path.join(HERE, "modules")   # in-tree family modules (ntg_amd/modules/*.hip), built next to their sources
+
+
+def abi_stamp() -> str:
+    """Stamp of the headers a family module is compiled against: 64 bits of the SHA-256 of the HEADERS files' contents.  The library
+    and every module get it as -DNTG_AMD_ABI; ntg_family_load refuses a module whose stamp differs from the library's."""
+    h = hashlib.sha256()
+    for f in HEADERS:
+        h.update(f.encode() + b"\0")
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(fh.read())
+    return "0x" + h.hexdigest()[:16] + "ull"
 
 
 BASES = os.path.join(CSRC, "fam_kincar_wave.abase")   # accumulator bases (main, alt) the wave-kernel object on disk was compiled with
@@ -33,7 +48,7 @@ def _read_bases():
 def _compile_wave(hipcc, src, obj, base, extra):
     cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-c", src, "-o", obj, "-I", os.path.join(HERE, "..", "include"),
            "-Wno-unused-result", "-Wno-unused-value", "-Wno-pass-failed", "-save-temps=obj", "-Wno-unused-command-line-argument",
-           "-DNTGW_ABASE=%d" % base["main"], "-DNTGW_ABASE_ALT=%d" % base["alt"]] + [f for f in extra if not f.startswith("-DNTGW_ABASE")]
+           "-DNTGW_ABASE=%d" % base["main"], "-DNTGW_ABASE_ALT=%d" % base["alt"], "-DNTG_AMD_ABI=" + abi_stamp()] + [f for f in extra if not f.startswith("-DNTGW_ABASE")]
     with open(obj + ".log", "w") as log:
         if subprocess.call(cmd, stdout=log, stderr=subprocess.STDOUT) != 0:
             sys.stderr.write(open(obj + ".log").read())
@@ -45,10 +60,16 @@ def _compile_wave(hipcc, src, obj, base, extra):
 
 
 def _stale() -> bool:
+    from . import family
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + HEADERS if os.path.exists(os.path.join(CSRC, f)))
+    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + HEADERS if os.path.exists(os.path.join(CSRC, f))) or \
+        any(family.stale(m) for m in in_tree_modules())
+
+
+def in_tree_modules():
+    return sorted(glob.glob(os.path.join(MODULES, "*.hip")))
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -61,6 +82,15 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if os.environ.get("NTG_AMD_WAVE_ABASE"):      # e.g. NTG_AMD_WAVE_ABASE=256: build the fallback on purpose; =16: try the full register tier again
         wave_base = {"main": int(os.environ["NTG_AMD_WAVE_ABASE"]), "alt": int(os.environ["NTG_AMD_WAVE_ABASE"])}
     hdr_t = max(os.path.getmtime(os.path.join(CSRC, f)) for f in HEADERS if os.path.exists(os.path.join(CSRC, f)))
+    abi = abi_stamp()
+    # the in-tree family modules compile alongside the library's units (they only need the headers)
+    from . import family
+    mod_procs = []
+    for m in in_tree_modules():
+        if force or family.stale(m):
+            out = family.module_path(m)
+            log = open(out + ".log", "w")
+            mod_procs.append((m, out, subprocess.Popen(family.module_command(m, out), stdout=log, stderr=subprocess.STDOUT), log))
     for src in SOURCES:   # one hipcc per translation unit, all at once (the family units are independent)
         path = os.path.join(CSRC, src)
         obj = os.path.join(CSRC, os.path.splitext(src)[0] + ".o")
@@ -68,7 +98,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(path), hdr_t):
             continue
         cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-c", path, "-o", obj,
-               "-I", os.path.join(HERE, "..", "include"), "-Wno-unused-result", "-Wno-unused-value", "-Wno-pass-failed"]
+               "-I", os.path.join(HERE, "..", "include"), "-Wno-unused-result", "-Wno-unused-value", "-Wno-pass-failed", "-DNTG_AMD_ABI=" + abi]
         if src.endswith(".hip"):
             cmd += ["-save-temps=obj", "-Wno-unused-command-line-argument"]   # keeps the device assembly next to the object: audited below
         if verbose:
@@ -85,8 +115,17 @@ def build(force: bool = False, verbose: bool = False) -> str:
         if rc != 0:
             failed.append(src)
             sys.stderr.write(open(obj + ".log").read())
+    for m, out, pr, log in mod_procs:
+        rc = pr.wait()
+        log.close()
+        if rc != 0:
+            failed.append(os.path.basename(m))
+            sys.stderr.write(open(out + ".log").read())
     if failed:
         raise RuntimeError("hipcc failed for " + ", ".join(failed))
+    for m, out, _, _ in mod_procs:
+        os.remove(out + ".log")
+        family.finish_module(m, out)   # call-boundary audit of the module's device code (removes the .so on a violation)
     # call boundaries of the device code (no generic pointers into the private segment, no FLAT in out-of-line functions, no dynamic
     # stack: ntg_amd/call_audit.py says why); the other intermediate files of -save-temps are removed
     from . import call_audit

@@ -212,3 +212,39 @@ def manipulator_bounds(batch: int, narms: int = 4, ceiling: float = 2.5, seed: i
         up[p, :6 * nout] = lo[p, :6 * nout]
         lo[p, 6 * nout:] = -INF_BOUND; up[p, 6 * nout:] = ceiling
     return lo, up
+
+
+def config_U(family: int, ninterv: int = 8, order: int = 6, mult: int = 3, T: float = 4.0) -> Spec:
+    """Unicycle (the in-tree family module ntg_amd/modules/unicycle.hip, loaded as `family`): flat outputs x, y; acceleration
+    effort as running cost plus acceleration penalties at both ends; positions pinned at both ends and the initial heading along
+    +x (y'(0) = 0) by linear rows; initial speed^2 (one row), speed^2 and the lateral-acceleration proxy x'y'' - y'x'' at every
+    breakpoint (two rows), final speed^2 (one row) through the bounds of unicycle_bounds."""
+    nz = 6
+    lic = np.zeros((3, nz)); lic[0, 0] = 1.0; lic[1, 3] = 1.0; lic[2, 4] = 1.0   # x(0), y(0), y'(0)
+    lfc = np.zeros((2, nz)); lfc[0, 0] = 1.0; lfc[1, 3] = 1.0                    # x(T), y(T)
+    acc = [(0, 2), (1, 2)]
+    return Spec(
+        nout=2, bps=linspace_c(0.0, T, 5 * ninterv + 1), kninterv=[ninterv] * 2,
+        knots=[linspace_c(0.0, T, ninterv + 1) for _ in range(2)], order=[order] * 2, mult=[mult] * 2, maxderiv=[3] * 2,
+        family=family, lic=lic, ltc=np.zeros((0, nz)), lfc=lfc, nnlic=1, nnltc=2, nnlfc=1,
+        icav=[(0, 1), (1, 1)], tcav=[(0, 1), (0, 2), (1, 1), (1, 2)], fcav=[(0, 1), (1, 1)],
+        nicf=1, nucf=1, nfcf=1, icostav=acc, tcostav=acc, fcostav=acc, name=f"U:unicycle-k{order}-l{ninterv}")
+
+
+def unicycle_bounds(batch: int, seed: int = SEED):
+    """Per-problem bounds of config_U: start (x0, y0) heading along +x at speed v0, end (x0 + U(3, 5), y0 + U(-2.5, 2.5)); speed^2 at
+    most vmax^2 and |x'y'' - y'x''| at most a at every breakpoint, final speed in [vf - 0.2, vf + 0.2].  vmax and a are drawn
+    so that a visible share of the batch ends with one of the trajectory rows active.
+    Rows: [x(0), y(0), y'(0); x(T), y(T); v0^2; speed^2; cross; final speed^2]."""
+    rng = np.random.default_rng(seed)
+    lo = np.zeros((batch, 9)); up = np.zeros((batch, 9))
+    for p in range(batch):
+        x0 = rng.uniform(-1, 1); y0 = rng.uniform(-1, 1); v0 = rng.uniform(0.8, 1.2)
+        xf = x0 + rng.uniform(3, 5); yf = y0 + rng.uniform(-2.5, 2.5); vf = rng.uniform(0.8, 1.2)
+        vmax = rng.uniform(2.5, 3.0); a = rng.uniform(0.35, 1.0)
+        lo[p, :5] = up[p, :5] = (x0, y0, 0.0, xf, yf)
+        lo[p, 5] = up[p, 5] = v0 * v0
+        lo[p, 6], up[p, 6] = -INF_BOUND, vmax * vmax
+        lo[p, 7], up[p, 7] = -a, a
+        lo[p, 8], up[p, 8] = (vf - 0.2) ** 2, (vf + 0.2) ** 2
+    return lo, up

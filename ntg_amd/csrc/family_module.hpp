@@ -1,0 +1,34 @@
+// family_module.hpp -- the descriptor a loadable family module exports (include/ntg_amd_family.hpp fills it in, family_registry.cpp
+// checks it and kernels.hip dispatches through it).  Kept out of include/ntg_amd.h: that header declares plain C functions only.
+#pragma once
+#include "ntg_dev.hpp"
+
+// stamp of the library's headers (ntg_amd/build.py hashes its HEADERS list and passes -DNTG_AMD_ABI=... to the library and to every
+// module): a module compiled against other headers than the library it is loaded into is refused
+#ifndef NTG_AMD_ABI
+#define NTG_AMD_ABI 0ull
+#endif
+
+// the Family<> slot a module's kernels are instantiated for.  Every module uses the same slot, so two modules hold kernels with the
+// same mangled names: the module's hidden visibility and dlopen(RTLD_LOCAL) keep each launch inside its own shared object.  At run
+// time a module family has the id ntg_family_load() returned (>= NTG_FAM_MODULE_BASE), the kernels never read it.
+#define NTG_FAM_MODULE_SLOT 1000
+#define NTG_FAMILY_MODULE_ENTRY "ntg_family_module_v1"
+
+typedef hipError_t (*ntg_module_eval_fn)(const NtgDims &, const NtgTables &, const SmemLayout &, const EvalArgs &);
+typedef hipError_t (*ntg_module_sqp_fn)(const NtgDims &, const NtgTables &, const SmemLayout &, const SolveParams &, const SqpArgs &);
+
+struct ntg_family_module_desc {
+	unsigned long long abi;   // NTG_AMD_ABI the module was compiled with (first member in every version of the descriptor)
+	int sizeof_dims, sizeof_tables, sizeof_layout, sizeof_params, sizeof_eval_args, sizeof_sqp_args;
+	const char *name;
+	int dm;                   // maxderiv of every output
+	int nnlic, nnltc, nnlfc;  // the most nonlinear rows of each kind a plan may use
+	int nout;                 // outputs a plan must have (0: any)
+	ntg_module_eval_fn launch_eval;
+	ntg_module_sqp_fn launch_sqp;
+};
+typedef const ntg_family_module_desc *(*ntg_family_module_entry_fn)(void);
+
+// the registry (family_registry.cpp): the descriptor of a loaded module family, nullptr for any other id
+const ntg_family_module_desc *ntg_family_module(int family);

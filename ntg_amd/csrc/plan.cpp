@@ -18,10 +18,12 @@
 #include "ntg_dev.hpp"
 #include "plan.hpp"
 #include "qpdual.hpp"
+#include "family_module.hpp"
 
 static int build_newton_tables(ntg_plan *p);
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
+int ntg_fail(int code, const std::string &msg) { return fail(code, msg); }
 #define HIPCHK(x)                                                                                 \
 	do {                                                                                          \
 		hipError_t e_ = (x);                                                                      \
@@ -123,11 +125,20 @@ extern "C" int ntg_plan_create(const ntg_spec *s, int device, ntg_plan **out)
 	D.nclin = s->nlic + s->nltc * s->nbps + s->nlfc;           // ntg.c:156
 	D.ncnln = s->nnlic + s->nnltc * s->nbps + s->nnlfc;        // ntg.c:157
 	D.nbounds = s->nlic + s->nltc + s->nlfc + s->nnlic + s->nnltc + s->nnlfc;
+	const ntg_family_module_desc *mod = ntg_family_module(s->family);   // a family loaded by ntg_family_load (nullptr: built in, or unknown)
 	if (s->family != NTG_FAM_KINCAR && s->family != NTG_FAM_VANDERPOL && s->family != NTG_FAM_TESTFAM && s->family != NTG_FAM_OBSTACLE &&
-	    s->family != NTG_FAM_QUADROTOR && s->family != NTG_FAM_MANIP && s->family != NTG_FAM_HOST) {
+	    s->family != NTG_FAM_QUADROTOR && s->family != NTG_FAM_MANIP && s->family != NTG_FAM_HOST && !mod) {
 		delete p; return fail(NTG_E_BADARG, "unknown problem family");
 	}
-	if (s->family != NTG_FAM_HOST) {
+	if (mod) {
+		for (int o = 0; o < s->nout; o++)
+			if (D.d[o] != mod->dm) { delete p; return fail(NTG_E_UNSUPPORTED, std::string("family module ") + mod->name + ": wrong maxderiv (the family has " + std::to_string(mod->dm) + ")"); }
+		if (s->nnlic > mod->nnlic || s->nnltc > mod->nnltc || s->nnlfc > mod->nnlfc) {
+			delete p; return fail(NTG_E_BADARG, std::string("family module ") + mod->name + " has " + std::to_string(mod->nnlic) + "/" + std::to_string(mod->nnltc) + "/" +
+			                                        std::to_string(mod->nnlfc) + " nonlinear constraints (initial/trajectory/final)");
+		}
+		if (mod->nout > 0 && s->nout != mod->nout) { delete p; return fail(NTG_E_BADARG, std::string("family module ") + mod->name + " has " + std::to_string(mod->nout) + " outputs"); }
+	} else if (s->family != NTG_FAM_HOST) {
 		const int dm = s->family == NTG_FAM_QUADROTOR ? 5 : 3;   // Family<>::DM of families.hpp
 		for (int o = 0; o < s->nout; o++)
 			if (D.d[o] != dm) { delete p; return fail(NTG_E_UNSUPPORTED, "device family: wrong maxderiv (5 for the quadrotor family, 3 otherwise)"); }

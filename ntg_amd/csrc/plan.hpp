@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <vector>
 #include <mutex>
+#include <string>
 #include "ntg_dev.hpp"
 
 struct ntg_plan {
@@ -38,6 +39,8 @@ struct ntg_plan {
 };
 
 void ntg_plan_dense_A(const ntg_plan *p, double *A);
+// sets the message ntg_last_error() returns (this thread), returns code
+int ntg_fail(int code, const std::string &msg);
 
 // LDS carve-up: tables + (with_x) the coefficient vector + nvec further vectors of nC doubles.
 //   eval_kernel   nvec 0 (the gradient is assembled into the x buffer once x is no longer needed)
