@@ -98,7 +98,11 @@ __device__ __forceinline__ void wave_sums(double (&v)[KV], int lane)
 		double w[16];
 #pragma unroll
 		for (int k = 0; k < 16; k++) w[k] = k < KV ? v[k] : 0.0;
-		const double t = wave_sum_many<KV>(w, lane);   // lane L: total of value L & 15
+		// (the lane index through an opaque copy: the butterfly's lane masks are then formed here, not kept for the whole kernel in scalar
+		// register pairs that spill)
+		int ln = lane;
+		asm volatile("" : "+v"(ln));
+		const double t = wave_sum_many<KV>(w, ln);   // lane L: total of value L & 15
 #pragma unroll
 		for (int k = 0; k < KV; k++) v[k] = bcast(t, k);
 	}
@@ -113,6 +117,23 @@ struct WaveArgs {
 	unsigned int *counter;    // problem queue (zeroed before the launch)
 	int hbm_slots;            // slots per wave in hist
 };
+
+// The kernel's arguments as they sit in the kernarg segment (same layout: each argument at its own alignment).  Fields needed inside the
+// evaluation loop are read there at their point of use, through an opaque copy of the segment pointer (uniform loads): passed by value and
+// read once, they were scalar registers live across the whole problem loop -- spilled into VGPR lanes and reloaded on every trip.
+struct WaveKernArgs {
+	NtgDims D;
+	NtgTables T;
+	SolveParams sp;
+	WaveArgs A;
+};
+typedef const __attribute__((address_space(4))) WaveKernArgs *WaveKernArgsPtr;
+__device__ __forceinline__ WaveKernArgsPtr kernargs()
+{
+	WaveKernArgsPtr p = (WaveKernArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+	asm volatile("" : "+s"(p));
+	return p;
+}
 
 // LDS (doubles) of one workgroup: tables, then per wave [stage | tmp | delta | kappa | links | line search | chain tier]
 template <int NCH, int K, int NINT>
@@ -272,13 +293,17 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 			return fval;
 		};
 		double Fp = 0.0;
+		// (the lane's slot count and interval through opaque copies: the per-slot lane masks are then formed here, one compare each, instead of
+		// being kept for the whole kernel in scalar register pairs -- which spilled, two lane reads and a wait per use)
+		int cn = cnt, tl = t;
+		asm volatile("" : "+v"(cn), "+v"(tl));
 		{
 			double bbA[NCH][K], bbB[NCH][K], wA, wB, dtA, dtB;
 			slot_load(0, bbA, wA, dtA);
 			slot_load(1, bbB, wB, dtB);
 			double fprev = slot_compute(0, bbA, wA), dtprev = dtA;
 			double fnext = from_next(fprev);
-			if (t >= NINT - 1) fnext = 0.0;
+			if (tl >= NINT - 1) fnext = 0.0;
 			static_for<1, SMAX>([&](auto Sc) __attribute__((always_inline)) {
 				constexpr int s2 = decltype(Sc)::value;
 				double fval;
@@ -289,7 +314,7 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 					if constexpr (s2 + 1 < SMAX) slot_load(s2 + 1, bbB, wB, dtB);
 					fval = slot_compute(s2, bbA, wA);
 				}
-				Fp += dtprev * ((s2 < cnt ? fval : fnext) + fprev) / 2;
+				Fp += dtprev * ((s2 < cn ? fval : fnext) + fprev) / 2;
 				fprev = fval; dtprev = (s2 & 1) ? dtB : dtA;
 			});
 			Fp += dtprev * (fnext + fprev) / 2;
@@ -477,7 +502,9 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 #pragma unroll
 		for (int k = 0; k < 16; k++) acc[k] = 0.0;
 		auto flush = [&](int base) __attribute__((always_inline)) {   // slots base .. base+15 -> delta
-			const double tot = wave_sum_many<16>(acc, lane);
+			int ln = lane;
+			asm volatile("" : "+v"(ln));   // (see wave_sums)
+			const double tot = wave_sum_many<16>(acc, ln);
 			if (lane < 16 && base + lane < nso) s_dl[base + lane] = tot;
 #pragma unroll
 			for (int k = 0; k < 16; k++) acc[k] = 0.0;
@@ -519,13 +546,24 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 		auto kappa_of = [&](int j) -> double {   // uniform j < 64
 			return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(kap0), j), __builtin_amdgcn_readlane(__double2loint(kap0), j));
 		};
-		// pass 2: tv += kappa_j d_j
+		// pass 2: tv += kappa_j d_j.  (The slot count through an opaque copy: each slot's test is then one scalar compare here, instead of
+		// the twenty tests of pass 1 kept as lane masks across the passes -- they spilled, two lane reads and a wait per slot.  The kappas of
+		// a round of four slots are read from their lanes together: the reads fill each other's wait states before the first FMA uses one.)
+		int nso2 = nso;
+		asm volatile("" : "+s"(nso2));
 		if constexpr (NREG > 0) {
-			static_for<0, NREG>([&](auto Jc) __attribute__((always_inline)) {
-				constexpr int J = decltype(Jc)::value;
-				if (J < nso) {
-					const double kj = bcast(kap0, J);
-					static_for<0, EPL>([&](auto Ec) __attribute__((always_inline)) { constexpr int E = decltype(Ec)::value; tv[E] += kj * areg_read<ABASE, J * EPL + E>(); });
+			static_for<0, (NREG + 3) / 4>([&](auto Gc) __attribute__((always_inline)) {
+				constexpr int J0 = 4 * decltype(Gc)::value;
+				if (J0 < nso2) {
+					double kq[4];
+#pragma unroll
+					for (int u = 0; u < 4; u++) kq[u] = bcast(kap0, J0 + u);
+					static_for<0, 4>([&](auto Uc) __attribute__((always_inline)) {
+						constexpr int U = decltype(Uc)::value, J = J0 + U;
+						if constexpr (J < NREG) {
+							if (J < nso2) static_for<0, EPL>([&](auto Ec) __attribute__((always_inline)) { constexpr int E = decltype(Ec)::value; tv[E] += kq[U] * areg_read<ABASE, J * EPL + E>(); });
+						}
+					});
 				}
 			});
 		}
@@ -748,6 +786,10 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 						  int rq_ = __builtin_amdgcn_readfirstlane(l2_.step(fq_, sq_)); l2_.make_uniform(); asm volatile("" ::"s"(rq_), "s"(l2_.a), "s"(l2_.a_lo), "s"(l2_.a_hi), "s"(l2_.phi_lo), "s"(l2_.phi_hi), "s"(l2_.a_prev)); }
 #endif
 						if constexpr (LSREG) {
+							{   // the line search's constants from the argument segment (LineSearch::init stored the same values)
+								const WaveKernArgsPtr ka = kernargs();
+								ls.mu = ka->sp.ls_mu; ls.eta = ka->sp.ls_eta; ls.maxfev = ka->sp.ls_maxfev;
+							}
 							rc = __builtin_amdgcn_readfirstlane(ls.step(Fn, part[2]));
 							ls.make_uniform();
 							ls_a = ls.a;
@@ -768,7 +810,7 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 						continue;
 					}
 					if (rc != 1) {
-						const double tolg = sp.sr * (1.0 + fmax(1.0 + fabs(F), sqrt(gn2)));
+						const double tolg = kernargs()->sp.sr * (1.0 + fmax(1.0 + fabs(F), sqrt(gn2)));
 						if (nupd > 0 && sqrt(r4[3]) > tolg) {
 							// line search failed with a non-trivial W: drop the updates and retry from the same point with W0
 							nupd = 0; ns = 0; headpair = false;
@@ -797,7 +839,7 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 						// before the update count does and this kernel restarts a few majors EARLIER than the oracle and sqp_kernel -- a different (still
 						// valid) quasi-Newton operator from there on.  On the strictly convex problems of this kernel's class s'y > 0 at every accepted
 						// step (no update is ever skipped: the fixed-iteration parity tests compare evaluation counts), so the two conditions coincide.
-						if (nupd == sp.memcap || ns + 3 > cap) {
+						if (nupd == kernargs()->sp.memcap || ns + 3 > cap) {
 							nupd = 0; ns = 0; headpair = true;
 							apply_w0(gp, d);
 						}
@@ -827,24 +869,24 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 						wave_sums<8, MINW == 1>(r6, lane);
 						const bool upd = r6[0] > 1e-12 * sqrt(r6[4]) * sqrt(r6[5]);
 						const double rho = upd ? 1.0 / r6[0] : 0.0, c2 = upd ? rho * (1.0 + rho * r6[1]) : 0.0;
-						double dn[EPL];
+						// the new direction d+ is formed in place of d (the loop-carried direction keeps one set of registers instead of being rebuilt
+						// from a temporary on this path only); the pair term's u = t - d of the old d is kept for it
+						double uv[EPL];
 #pragma unroll
 						for (int e = 0; e < EPL; e++) {
 							const double s = sv[e], u = tv[e] - d[e];
-							dn[e] = upd ? tv[e] - rho * (s * r6[3] + u * r6[2]) + c2 * s * r6[2] : tv[e];
+							uv[e] = u;
+							d[e] = upd ? tv[e] - rho * (s * r6[3] + u * r6[2]) + c2 * s * r6[2] : tv[e];
 						}
 						if (headpair && upd) {
 							// first update after a restart at an accepted step: s is the step actually taken (along the OLD direction), not
 							// -alpha W0 gp: the pair (s, u) is stored as two slots joined by the link (-rho, c2) -- exactly the pair term
 							// -rho (s u' + u s') + c2 s s' -- followed by a null link to the chain that starts with d+
-							double uv[EPL];
-#pragma unroll
-							for (int e = 0; e < EPL; e++) uv[e] = tv[e] - d[e];
-							slot_store(0, sv); slot_store(1, uv); slot_store(2, dn);
+							slot_store(0, sv); slot_store(1, uv); slot_store(2, d);
 							if (lane == 0) { s_lk[0] = -rho; s_lk[1] = c2; s_lk[2] = 0.0; s_lk[3] = 0.0; }
 							ns = 3; nupd = 1;
 						} else if (headpair) {
-							slot_store(0, dn); ns = 1;   // no update: W stays W0, a clean chain starts at d+
+							slot_store(0, d); ns = 1;   // no update: W stays W0, a clean chain starts at d+
 						} else {
 							// link of this major: s = -alpha d_k, u = beta d_{k+1} + gamma d_k (omega = -(s.g)/(s.y) > 0 whenever the update is taken)
 							double le = 0.0, lf = 0.0;
@@ -854,7 +896,7 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 								le = rho * alpha * beta; lf = 2.0 * rho * alpha * gamma + c2 * alpha * alpha;
 								nupd++;
 							}
-							slot_store(ns, dn);
+							slot_store(ns, d);
 							if (lane == 0) { s_lk[2 * (ns - 1)] = le; s_lk[2 * (ns - 1) + 1] = lf; }
 							ns++;
 						}
@@ -863,26 +905,26 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 						double r2[2] = {0.0, 0.0};
 #pragma unroll
 						for (int e = 0; e < EPL; e++) {
-							gp[e] = gpt[e]; d[e] = dn[e];
+							gp[e] = gpt[e];
 							r2[0] += gp[e] * d[e]; r2[1] += d[e] * d[e];
 						}
 						wave_sums<2, MINW == 1>(r2, lane);
 						r4[0] = r2[0]; r4[1] = r2[1]; r4[2] = r6[6]; r4[3] = r6[7];
 						F = Fn; gn2 = gn2n;
 						iter++;
-						if (!sp.fixed_iters && alpha * pnorm <= sp.sr * (1.0 + sqrt(r4[2])) &&
-						    sqrt(r4[3]) <= sp.sr * (1.0 + fmax(1.0 + fabs(F), sqrt(gn2)))) { inner_inform = 0; finished = true; }
+						if (!kernargs()->sp.fixed_iters && alpha * pnorm <= kernargs()->sp.sr * (1.0 + sqrt(r4[2])) &&
+						    sqrt(r4[3]) <= kernargs()->sp.sr * (1.0 + fmax(1.0 + fabs(F), sqrt(gn2)))) { inner_inform = 0; finished = true; }
 						else new_major = true;
 					}
 				}
 				if (new_major) {
 					// ---- start of a major iteration at (x, gp, d) ----
-					if (iter >= sp.itlim) { inner_inform = 4; finished = true; }
+					if (iter >= kernargs()->sp.itlim) { inner_inform = 4; finished = true; }
 					else {
 						double dphi0 = -r4[0];
 						pnorm = sqrt(r4[1]);
 						const double xnorm = sqrt(r4[2]), gpnorm = sqrt(r4[3]);
-						const double tolg = sp.sr * (1.0 + fmax(1.0 + fabs(F), sqrt(gn2)));
+						const double tolg = kernargs()->sp.sr * (1.0 + fmax(1.0 + fabs(F), sqrt(gn2)));
 						if (pnorm == 0.0 || !(dphi0 < 0.0)) {
 							if (pnorm != 0.0) {   // W lost definiteness numerically: restart from W0 once
 								nupd = 0; ns = 0; headpair = false;
@@ -896,13 +938,13 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 							}
 							if (pnorm == 0.0 || !(dphi0 < 0.0)) { inner_inform = (gpnorm <= tolg) ? 0 : 6; finished = true; }
 						}
-						if (!finished && !sp.fixed_iters && gpnorm <= 1e-3 * tolg) { inner_inform = 0; finished = true; }
+						if (!finished && !kernargs()->sp.fixed_iters && gpnorm <= 1e-3 * tolg) { inner_inform = 0; finished = true; }
 						if (!finished) {
-							const double amax = sp.steplimit * (1.0 + xnorm) / pnorm;
+							const double amax = kernargs()->sp.steplimit * (1.0 + xnorm) / pnorm;
 							const double a = amax < 1.0 ? amax : 1.0;
-							if constexpr (LSREG) ls.init(F, dphi0, a, amax, sp.ls_mu, sp.ls_eta, sp.ls_maxfev);
+							if constexpr (LSREG) ls.init(F, dphi0, a, amax, kernargs()->sp.ls_mu, kernargs()->sp.ls_eta, kernargs()->sp.ls_maxfev);
 							else {
-								if (lane == 0) lsm->init(F, dphi0, a, amax, sp.ls_mu, sp.ls_eta, sp.ls_maxfev);
+								if (lane == 0) lsm->init(F, dphi0, a, amax, kernargs()->sp.ls_mu, kernargs()->sp.ls_eta, kernargs()->sp.ls_maxfev);
 								nwt_wave_sync();
 							}
 							ls_a = a; tstep = a;
