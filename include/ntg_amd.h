@@ -14,6 +14,7 @@
  *   ntg_plan_tables      colloc.h:42-71  read-back of Block.matrix / Block.offset / A
  *   ntg_basis_batch      colloc.c:92-111 the same basis evaluation for many grids at once
  *   ntg_plan_set_grids   ntg.c:114-229 per problem: own knots and breakpoints for every problem of a batch
+ *   ntg_plan_set_params  the file-scope parameter globals of the examples (kincar.c:43 default_params), one row per problem
  *   ntg_batch_eval       ntg.c:274-371   NPfunobj + NPfuncon (cost.c, constraints.c, integrator.c)
  *   ntg_batch_bounds     constraints.c:5-33 bounds()
  *   ntg_batch_solve      ntg.c:237-253   the npsol_() call, for `batch` problems at once
@@ -49,6 +50,8 @@ extern "C" {
 #define NTG_FAM_OBSTACLE 3   /* kincar cost + circular-obstacle trajectory constraint (x-20)^2+(y-0.5)^2 >= r^2 */
 #define NTG_FAM_QUADROTOR 4  /* 4 outputs x,y,z,yaw, maxderiv 5: snap^2 + yaw''^2; rows: thrust^2 = x''^2+y''^2+(z''+g)^2, speed^2 */
 #define NTG_FAM_MANIP 5      /* 3 joints per planar arm, maxderiv 3: sum q''^2; one tip-height row sin(qa)+sin(qa+qb)+sin(qa+qb+qc) per arm */
+#define NTG_FAM_OBSTACLE_FIELD 6  /* kincar cost (2 outputs) + m = nnltc <= 8 rows (x-cx_j)^2+(y-cy_j)^2 >= r_j^2: the centres are per-problem
+                                     parameters [cx_0, cy_0, ..., cx_{m-1}, cy_{m-1}] (ntg_plan_set_params), the radii come through the bounds */
 #define NTG_FAM_HOST (-1)    /* host function pointers (ntg() drop-in path only) */
 #define NTG_FAM_MODULE_BASE 64  /* ids of families loaded from modules (ntg_family_load) start here */
 
@@ -181,6 +184,23 @@ int ntg_basis_batch(int ngrids, int ninterv, int order, int mult, int maxderiv, 
  * re-pin with every problem's own basis blocks) until ntg_plan_clear_grids(). */
 int ntg_plan_set_grids(ntg_plan *p, int batch, const double *d_knots, const double *d_bps, int with_precond, void *stream);
 void ntg_plan_clear_grids(ntg_plan *p);
+
+/* Per-problem family parameters: the data a family's callbacks read besides the flat flag (obstacle centres, a reference to track),
+ * one row of doubles per problem -- what the reference's examples keep in file-scope globals (kincar.c:43) while ntg() solves one
+ * problem at a time.
+ * ntg_plan_param_count: the doubles every problem needs for this plan's family (0 for the families without parameters; 2 nnltc for
+ * NTG_FAM_OBSTACLE_FIELD; NPARAM + NPARAM_BP * nbps for a family module, include/ntg_amd_family.hpp).
+ * ntg_plan_set_params: d_params [batch][nparam] (device) is copied, ordered on `stream`, into a buffer the plan owns (the caller's
+ * pointer is not kept; setting them again with the same batch * nparam reuses the buffer at the same address).  NTG_E_BADARG if nparam
+ * is not ntg_plan_param_count or the family takes none; NTG_E_UNSUPPORTED for host-callback plans.
+ * Afterwards ntg_batch_eval / ntg_batch_solve / ntg_batch_mpc_run of exactly `batch` problems read problem b's row (NTG_E_BADARG for
+ * any other batch); ntg_batch_mpc_run reads the buffer at every step, so new parameters set between two runs take effect.
+ * ntg_batch_mpc_shift / ntg_batch_bounds / ntg_batch_interp call no family callback and ignore them.  A family that needs parameters
+ * refuses eval / solve / mpc_run (NTG_E_BADARG) while none are set.  Independent of per-problem grids: both can be in force.
+ * ntg_plan_clear_params drops them. */
+int ntg_plan_param_count(const ntg_plan *p, int *nparam);
+int ntg_plan_set_params(ntg_plan *p, int batch, int nparam, const double *d_params, void *stream);
+void ntg_plan_clear_params(ntg_plan *p);
 
 /* SplineInterp (colloc.c:449-484) for a whole batch: the flat flag of every problem at ntimes points in time shared by
  * the batch (d_times [ntimes], inside the knot range of every output) -> d_z [batch][ntimes][nz], entry iz[o]+r =

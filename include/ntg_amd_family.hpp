@@ -19,6 +19,14 @@
 //     callback reads: the kernels only materialise the entries some list names.
 //   - callbacks are device code: no allocation, no host calls, no recursion; keep them __forceinline__ (NTG_AMD_HD below does).
 //
+// Per-problem parameters (ntg_plan_set_params): a family that reads data besides the flat flag -- obstacle positions, a
+// reference to track -- declares NPARAM (doubles per problem) and / or NPARAM_BP (doubles per breakpoint); a plan of the family then needs
+// NPARAM + NPARAM_BP * nbps doubles per problem, laid out [NPARAM fixed | NPARAM_BP for breakpoint 0 | ... ].  Such a family writes EVERY
+// callback with one more trailing argument, const double *prm, the problem's row (the same for all breakpoints; ucf / nltcf get the
+// breakpoint index i, so breakpoint data is prm[NPARAM + NPARAM_BP * i + k]):
+//   ucf(nout, i, z, f, df, prm)   icf(nout, z, f, df, prm)   nltcf(nout, i, z, c, dc, prm)   ... (the defaults come in both forms)
+// The row is read only; it is the same for every lane that works on the problem.
+//
 // Derive from ntg_amd::FamilyDefaults<YourFamily> and write only the callbacks your problem has.  The defaults are: no nonlinear
 // rows of any kind (NNLIC = NNLTC = NNLFC = 0), zero initial and final cost, DM = 3, the trajectory rows' two-step form
 // (nltc_val / nltc_vjp) through the dense nltcf, and no second-order blocks.  Then, in one .hip file:
@@ -60,6 +68,7 @@ struct FamilyDefaults {
 	static constexpr unsigned long long TCON_VARS = ~0ull;   // flag entries a trajectory row can depend on (all: not declared)
 	static constexpr bool PER_OUTPUT_COST = false;      // only the tuned built-in instances use this
 	static constexpr int COUPLE = 0, CG = 1;            // no second-order blocks (modules do not offer them)
+	static constexpr int NPARAM = 0, NPARAM_BP = 0;     // per-problem parameters: doubles per problem, doubles per breakpoint
 	static NTG_AMD_HD int row_group(int) { return 0; }
 	static NTG_AMD_HD void icf(int nout, const double *, double &f, double *df)
 	{
@@ -74,11 +83,23 @@ struct FamilyDefaults {
 	static NTG_AMD_HD void nlicf(int, const double *, double *, double *) {}
 	static NTG_AMD_HD void nltcf(int, int, const double *, double *, double *) {}
 	static NTG_AMD_HD void nlfcf(int, const double *, double *, double *) {}
+	// ... and the same defaults in the form a family with parameters is called in (trailing prm)
+	static NTG_AMD_HD void icf(int nout, const double *z, double &f, double *df, const double *) { icf(nout, z, f, df); }
+	static NTG_AMD_HD void fcf(int nout, const double *z, double &f, double *df, const double *) { fcf(nout, z, f, df); }
+	static NTG_AMD_HD void nlicf(int, const double *, double *, double *, const double *) {}
+	static NTG_AMD_HD void nltcf(int, int, const double *, double *, double *, const double *) {}
+	static NTG_AMD_HD void nlfcf(int, const double *, double *, double *, const double *) {}
 #if NTG_AMD_FAMILY_DEVICE
 	// the trajectory rows in the augmented-Lagrangian evaluation's two-step form: values, then df += J' t, both through nltcf
 	template <int NZMAX> static __device__ __forceinline__ void nltc_val(int nout, int i, const double *z, double *c, double *) { DenseTraj<F, NZMAX>::val(nout, i, z, c); }
 	template <int NZMAX> static __device__ __forceinline__ void nltc_vjp(int nout, int nz, int i, const double *z, const double *t, double *df, const double *) { DenseTraj<F, NZMAX>::vjp(nout, nz, i, z, t, df); }
 	template <int NZMAX> static __device__ __forceinline__ void nltc_block(int, int, const double *, const double *, double, bool, double *) {}
+	template <int NZMAX> static __device__ __forceinline__ void nltc_val(int nout, int i, const double *z, double *c, double *, const double *prm) { DenseTraj<F, NZMAX>::val(nout, i, z, c, prm); }
+	template <int NZMAX> static __device__ __forceinline__ void nltc_vjp(int nout, int nz, int i, const double *z, const double *t, double *df, const double *, const double *prm)
+	{
+		DenseTraj<F, NZMAX>::vjp(nout, nz, i, z, t, df, prm);
+	}
+	template <int NZMAX> static __device__ __forceinline__ void nltc_block(int, int, const double *, const double *, double, bool, double *, const double *) {}
 #endif
 };
 
@@ -92,6 +113,7 @@ struct FamilyDefaults {
 #define NTG_AMD_FAMILY_MODULE(FAMILY, NAME, NOUT_REQUIRED)                                                                                  \
 	static_assert(FAMILY::COUPLE == 0, "module families have no second-order (Newton / QP) blocks");                                       \
 	static_assert(FAMILY::DM >= 1 && FAMILY::NNLIC >= 0 && FAMILY::NNLTC >= 0 && FAMILY::NNLFC >= 0, "bad family constants");           \
+	static_assert(FamPrmCounts<FAMILY>::n >= 0 && FamPrmCounts<FAMILY>::bp >= 0 && FamPrmRow<FAMILY>::value == 0, "bad parameter counts");  \
 	template <> struct Family<NTG_FAM_MODULE_SLOT> : FAMILY {};                                                                            \
 	namespace {                                                                                                                            \
 	hipError_t ntg_module_launch_eval(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)                      \
@@ -105,7 +127,7 @@ struct FamilyDefaults {
 	const ntg_family_module_desc ntg_module_desc = {                                                                                       \
 		NTG_AMD_ABI, (int)sizeof(NtgDims), (int)sizeof(NtgTables), (int)sizeof(SmemLayout), (int)sizeof(SolveParams),                     \
 		(int)sizeof(EvalArgs), (int)sizeof(SqpArgs), NAME, FAMILY::DM, FAMILY::NNLIC, FAMILY::NNLTC, FAMILY::NNLFC, (NOUT_REQUIRED),        \
-		&ntg_module_launch_eval, &ntg_module_launch_sqp};                                                                                  \
+		&ntg_module_launch_eval, &ntg_module_launch_sqp, FamPrmCounts<FAMILY>::n, FamPrmCounts<FAMILY>::bp};                             \
 	}                                                                                                                                      \
 	extern "C" __attribute__((visibility("default"))) const ntg_family_module_desc *ntg_family_module_v1(void) { return &ntg_module_desc; }
 #endif

@@ -76,6 +76,9 @@ def lib():
         L.ntg_batch_interp_strided.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
         L.ntg_plan_set_grids.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ntg_plan_clear_grids.argtypes = [C.c_void_p]
+        L.ntg_plan_param_count.argtypes = [C.c_void_p, ip]
+        L.ntg_plan_set_params.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.ntg_plan_clear_params.argtypes = [C.c_void_p]
         L.ntg_plan_clear_grids.restype = None
         L.ntg_batch_kincar_reverse.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
         L.ntg_batch_mpc_shift.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -119,6 +122,7 @@ class Plan:
         self.spec = spec
         self.device = device
         self.grid_batch = 0   # batch of the per-problem grids in force (set_grids / clear_grids)
+        self.param_batch = 0  # batch of the per-problem parameters in force (set_params / clear_params)
         k = self._keep = {}
         k["bps"] = np.ascontiguousarray(spec.bps, dtype=np.float64)
         for nm in ("kninterv", "order", "mult", "maxderiv"):
@@ -254,6 +258,27 @@ class Plan:
     def clear_grids(self):
         lib().ntg_plan_clear_grids(self.h)
         self.grid_batch = 0
+
+    @property
+    def param_count(self) -> int:
+        """doubles of per-problem parameters the plan's family reads (0: it takes none).  See ntg_plan_param_count."""
+        n = C.c_int()
+        _check(lib().ntg_plan_param_count(self.h, C.byref(n)))
+        return n.value
+
+    def set_params(self, params):
+        """Per-problem family parameters: params [batch, param_count] (device, float64), copied into the plan.  Eval, solve and mpc_run
+        then take exactly `batch` problems.  See ntg_plan_set_params."""
+        import torch
+        _check_tensor(params, torch.device("cuda", self.device))
+        if params.dim() != 2 or params.shape[1] != self.param_count:
+            raise NtgError(f"params must be [batch, {self.param_count}]")
+        _check(lib().ntg_plan_set_params(self.h, params.shape[0], params.shape[1], _ptr(params), self._stream()))
+        self.param_batch = int(params.shape[0])
+
+    def clear_params(self):
+        lib().ntg_plan_clear_params(self.h)
+        self.param_batch = 0
 
     def kincar_reverse(self, z, wheelbase: float = 3.0, reverse_gear: bool = False):
         """Flat flag -> (x, y, theta, v, delta) per car: z [batch, ntimes, nz] (from interp) -> [batch, ntimes, ncars, 5]."""

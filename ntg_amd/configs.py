@@ -6,12 +6,14 @@
   M   headline: 6 flat outputs (three cars stacked), same splines
   T   testfam: every callback slot populated (exercises cost.c / constraints.c row orders)
   O   kincar + circular obstacle (one nonlinear trajectory inequality)
+  OF  kincar + a per-problem field of circular obstacles (family 6: centres are per-problem parameters)
+  TR  reference tracking (the in-tree family module ntg_amd/modules/tracking.hip: the path is per-problem parameters)
   D   quadrotor: 4 outputs, order 8, mult 4, 40 intervals, maxderiv 5, P = 201, 2 nonlinear trajectory rows
   E   manipulator: 12 outputs, order 6, mult 3, 60 intervals, P = 301, 4 nonlinear trajectory inequalities
 """
 from __future__ import annotations
 import numpy as np
-from .spec import Spec, linspace_c, FAM_KINCAR, FAM_VANDERPOL, FAM_TESTFAM, FAM_OBSTACLE, FAM_QUADROTOR, FAM_MANIP
+from .spec import Spec, linspace_c, FAM_KINCAR, FAM_VANDERPOL, FAM_TESTFAM, FAM_OBSTACLE, FAM_QUADROTOR, FAM_MANIP, FAM_OBSTACLE_FIELD
 
 SEED = 20261003
 WHEELBASE = 3.0  # kincar.c:43
@@ -137,6 +139,65 @@ def obstacle_bounds(batch: int, radius: float = 3.0, seed: int = SEED):
     lo = np.concatenate([lo, np.full((batch, 1), radius * radius)], axis=1)
     up = np.concatenate([up, np.full((batch, 1), INF_BOUND)], axis=1)
     return lo, up
+
+
+def config_OF(nobs: int, ninterv: int = 20, order: int = 6) -> Spec:
+    """config_O's kincar with a per-problem obstacle field (family 6): nobs rows (x-cx_j)^2 + (y-cy_j)^2 >= r_j^2 at every breakpoint,
+    the centres (cx_j, cy_j) per problem through Plan.set_params, r_j^2 through the bounds (obstacle_field_problems)."""
+    s = _kincar_spec(1, order, 3, ninterv, 5 * ninterv + 1, 5.0, f"OF:kincar-field{nobs}-k{order}-l{ninterv}")
+    s.family = FAM_OBSTACLE_FIELD
+    s.nnltc = nobs
+    s.tcav = [(0, 0), (1, 0)]
+    return s
+
+
+def obstacle_field_problems(batch: int, nobs: int, seed: int = SEED, rmin: float = 1.0, rmax: float = 2.5):
+    """Per-problem obstacle fields for config_OF(nobs): returns (params [batch, 2 nobs], lower, upper).  The kincar bounds are those of
+    kincar_random_bounds(1, batch, seed); obstacle j sits on the problem's straight route from its start to its end position, at
+    fraction (j + 1) / (nobs + 1) of the way, moved off the route by up to half its radius, radius in [rmin, rmax) (draws of a second
+    PCG64 stream, seed + 1): every obstacle blocks the straight route, and the solution must pass it on one side."""
+    lo, up = kincar_random_bounds(1, batch, seed)
+    rng = np.random.default_rng(seed + 1)
+    prm = np.empty((batch, 2 * nobs)); r2 = np.empty((batch, nobs))
+    for p in range(batch):
+        x0, y0, xf, yf = lo[p, 0], lo[p, 3], lo[p, 6], lo[p, 9]
+        for j in range(nobs):
+            f = (j + 1) / (nobs + 1)
+            r = rng.uniform(rmin, rmax)
+            prm[p, 2 * j] = x0 + f * (xf - x0)
+            prm[p, 2 * j + 1] = y0 + f * (yf - y0) + rng.uniform(-0.5, 0.5) * r
+            r2[p, j] = r * r
+    lo = np.concatenate([lo, r2], axis=1)
+    up = np.concatenate([up, np.full((batch, nobs), INF_BOUND)], axis=1)
+    return prm, lo, up
+
+
+def config_TR(family: int, ninterv: int = 8, order: int = 6, mult: int = 3, T: float = 4.0) -> Spec:
+    """Reference tracking (the in-tree family module ntg_amd/modules/tracking.hip, loaded as `family`): flat outputs x, y; running
+    cost W ((x - xr_i)^2 + (y - yr_i)^2) + x''^2 + y''^2 with the reference (xr_i, yr_i) per problem and breakpoint (tracking_problems);
+    positions pinned at both ends by linear rows."""
+    nz = 6
+    lic = np.zeros((2, nz)); lic[0, 0] = 1.0; lic[1, 3] = 1.0   # x(0), y(0)
+    lfc = np.zeros((2, nz)); lfc[0, 0] = 1.0; lfc[1, 3] = 1.0   # x(T), y(T)
+    return Spec(
+        nout=2, bps=linspace_c(0.0, T, 5 * ninterv + 1), kninterv=[ninterv] * 2,
+        knots=[linspace_c(0.0, T, ninterv + 1) for _ in range(2)], order=[order] * 2, mult=[mult] * 2, maxderiv=[3] * 2,
+        family=family, lic=lic, ltc=np.zeros((0, nz)), lfc=lfc, nucf=1, tcostav=[(0, 0), (0, 2), (1, 0), (1, 2)],
+        name=f"TR:tracking-k{order}-l{ninterv}")
+
+
+def tracking_problems(spec: Spec, batch: int, seed: int = SEED):
+    """Per-problem references for config_TR: returns (params [batch, 2 nbps], lower, upper).  Problem p follows its own curve
+    (a_p t, b_p sin(w_p t + ph_p)) sampled at the breakpoints; the ends are pinned on the curve."""
+    rng = np.random.default_rng(seed)
+    t = np.asarray(spec.bps)
+    prm = np.empty((batch, 2 * t.size)); lo = np.empty((batch, 4))
+    for p in range(batch):
+        a = rng.uniform(0.5, 1.5); b = rng.uniform(0.5, 2.0); w = rng.uniform(0.5, 2.0); ph = rng.uniform(0, 2 * np.pi)
+        xr, yr = a * t, b * np.sin(w * t + ph)
+        prm[p, 0::2] = xr; prm[p, 1::2] = yr
+        lo[p] = (xr[0], yr[0], xr[-1], yr[-1])
+    return prm, lo, lo.copy()
 
 
 QUAD_G = 9.81

@@ -21,6 +21,7 @@ eval_fast_kernel(FastEvalDims D, NtgTables T, int batch, int mode, const double 
                  double *__restrict__ g)
 {
 	using Fam = Family<FAM>;
+	static_assert(FamCall<Fam>::KIND == 0, "the lean evaluation kernels serve families without per-problem parameters");
 	constexpr int DM = Fam::DM, NCH = chm_count(CHM), NZ = NOUT * DM, NW = NT / 64, XE = 4, WP = W + 2;
 	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
 	const int P = D.P, nC = D.nC, nco = D.nco, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -102,7 +103,7 @@ eval_fast_kernel(FastEvalDims D, NtgTables T, int batch, int mode, const double 
 					z[DM * o + r] = acc;
 				}
 			}
-			Fam::ucf(NOUT, i, z, fv, df);
+			FamCall<Fam>{nullptr, 0}.ucf(NOUT, i, z, fv, df);
 			s_f[i] = fv;
 			const double w = s_wts[i];
 #pragma unroll
@@ -242,6 +243,7 @@ eval_interval_kernel(IntervalEvalDims D, NtgTables T, int batch, int mode, const
                      double *__restrict__ g)
 {
 	using Fam = Family<FAM>;
+	static_assert(FamCall<Fam>::KIND == 0, "the lean evaluation kernels serve families without per-problem parameters");
 	constexpr int DM = Fam::DM, NCH = chm_count(CHM), NZL = OPL * DM, NW = NT / 64, SMAX = 6, S = K / 2, NG = NOUT / OPL, XE = 6;   // XE: the host checked PW nC <= 64 XE
 	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
 	const int P = D.P, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -339,7 +341,7 @@ eval_interval_kernel(IntervalEvalDims D, NtgTables T, int batch, int mode, const
 					}
 					z[DM * o + r] = acc;
 				}
-			Fam::ucf(OPL, i0 + s2, z, fval, df);   // OPL < NOUT: the cost is a sum over the outputs (PER_OUTPUT_COST), this is the lane's share
+			FamCall<Fam>{nullptr, 0}.ucf(OPL, i0 + s2, z, fval, df);   // OPL < NOUT: the cost is a sum over the outputs (PER_OUTPUT_COST), this is the lane's share
 			const double w = s_wt[s2 * nint + t];
 #pragma unroll
 			for (int o = 0; o < OPL; o++)

@@ -16,24 +16,114 @@
 //   NTG_FAM_OBSTACLE   kincar cost (2 outputs) + trajectory constraint c = (x-20)^2 + (y-0.5)^2 (>= r^2 via bounds)
 //   NTG_FAM_QUADROTOR  4 outputs (x, y, z, yaw), maxderiv 5: snap^2 + yaw''^2; c0 = x''^2+y''^2+(z''+g)^2, c1 = |v|^2
 //   NTG_FAM_MANIP      3 joints per planar arm, maxderiv 3: sum q''^2; per arm c = sin(qa)+sin(qa+qb)+sin(qa+qb+qc)
+//   NTG_FAM_OBSTACLE_FIELD  kincar cost (2 outputs) + m <= 8 rows c_j = (x-cx_j)^2 + (y-cy_j)^2, the centres per problem (parameters)
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "../../include/ntg_amd.h"
+#include "ntg_dev.hpp"
+#include "obstacle_field.hpp"
 
 template <int FAM> struct Family;
 
-// nltc_val / nltc_vjp through the dense callback (families with a handful of constraints)
+// Per-problem parameters (ntg_plan_set_params, NtgTables::prm).  A family that takes them receives the problem's parameter row as one
+// more trailing argument of every callback; the others keep the signatures above.  Which form a family has:
+//   0  none                                       the built-in families below, modules with NPARAM = NPARAM_BP = 0
+//   1  (..., const double *prm)                   family modules that declare NPARAM or NPARAM_BP (include/ntg_amd_family.hpp)
+//   2  (..., const double *prm, int nnltc)        built-in families whose parameters come per trajectory row function (NPARAM_ROW
+//                                                 doubles each): they also get the plan's number of trajectory rows
+template <class F, class = void> struct FamPrmCounts { static constexpr int n = 0, bp = 0; };   // NPARAM, NPARAM_BP (0 where not declared)
+template <class F> struct FamPrmCounts<F, std::void_t<decltype(F::NPARAM + F::NPARAM_BP)>> { static constexpr int n = F::NPARAM, bp = F::NPARAM_BP; };
+template <class F, class = void> struct FamPrmRow { static constexpr int value = 0; };
+template <class F> struct FamPrmRow<F, std::void_t<decltype(F::NPARAM_ROW)>> { static constexpr int value = F::NPARAM_ROW; };
+template <class F> constexpr int fam_prm_kind() { return FamPrmRow<F>::value > 0 ? 2 : (FamPrmCounts<F>::n + FamPrmCounts<F>::bp > 0 ? 1 : 0); }
+
+// The one way the kernels call a family: FamCall<Fam>{problem's parameter row, D.nnltc}.fn(...) -- for a family without parameters exactly
+// Fam::fn(...), so that its code does not change; for the others the row is appended.  The row is the same for every lane of a problem
+// (uniform loads at the point of use); nothing on the device writes it.
+template <class F>
+struct FamCall {
+	static constexpr int KIND = fam_prm_kind<F>();
+	const double *prm; int nrow;
+	__device__ __forceinline__ void ucf(int nout, int i, const double *z, double &f, double *df) const
+	{
+		if constexpr (KIND == 0) F::ucf(nout, i, z, f, df); else if constexpr (KIND == 1) F::ucf(nout, i, z, f, df, prm); else F::ucf(nout, i, z, f, df, prm, nrow);
+	}
+	__device__ __forceinline__ void icf(int nout, const double *z, double &f, double *df) const
+	{
+		if constexpr (KIND == 0) F::icf(nout, z, f, df); else if constexpr (KIND == 1) F::icf(nout, z, f, df, prm); else F::icf(nout, z, f, df, prm, nrow);
+	}
+	__device__ __forceinline__ void fcf(int nout, const double *z, double &f, double *df) const
+	{
+		if constexpr (KIND == 0) F::fcf(nout, z, f, df); else if constexpr (KIND == 1) F::fcf(nout, z, f, df, prm); else F::fcf(nout, z, f, df, prm, nrow);
+	}
+	__device__ __forceinline__ void nlicf(int nout, const double *z, double *c, double *dc) const
+	{
+		if constexpr (KIND == 0) F::nlicf(nout, z, c, dc); else if constexpr (KIND == 1) F::nlicf(nout, z, c, dc, prm); else F::nlicf(nout, z, c, dc, prm, nrow);
+	}
+	__device__ __forceinline__ void nltcf(int nout, int i, const double *z, double *c, double *dc) const
+	{
+		if constexpr (KIND == 0) F::nltcf(nout, i, z, c, dc); else if constexpr (KIND == 1) F::nltcf(nout, i, z, c, dc, prm); else F::nltcf(nout, i, z, c, dc, prm, nrow);
+	}
+	__device__ __forceinline__ void nlfcf(int nout, const double *z, double *c, double *dc) const
+	{
+		if constexpr (KIND == 0) F::nlfcf(nout, z, c, dc); else if constexpr (KIND == 1) F::nlfcf(nout, z, c, dc, prm); else F::nlfcf(nout, z, c, dc, prm, nrow);
+	}
+	template <int NZMAX> __device__ __forceinline__ void nltc_val(int nout, int i, const double *z, double *c, double *tape) const
+	{
+		if constexpr (KIND == 0) F::template nltc_val<NZMAX>(nout, i, z, c, tape);
+		else if constexpr (KIND == 1) F::template nltc_val<NZMAX>(nout, i, z, c, tape, prm);
+		else F::template nltc_val<NZMAX>(nout, i, z, c, tape, prm, nrow);
+	}
+	template <int NZMAX> __device__ __forceinline__ void nltc_vjp(int nout, int nz, int i, const double *z, const double *t, double *df, const double *tape) const
+	{
+		if constexpr (KIND == 0) F::template nltc_vjp<NZMAX>(nout, nz, i, z, t, df, tape);
+		else if constexpr (KIND == 1) F::template nltc_vjp<NZMAX>(nout, nz, i, z, t, df, tape, prm);
+		else F::template nltc_vjp<NZMAX>(nout, nz, i, z, t, df, tape, prm, nrow);
+	}
+	template <int NZMAX> __device__ __forceinline__ void nltc_block(int nout, int g, const double *z, const double *t, double mu, bool curv, double *B) const
+	{
+		if constexpr (KIND == 0) F::template nltc_block<NZMAX>(nout, g, z, t, mu, curv, B);
+		else if constexpr (KIND == 1) F::template nltc_block<NZMAX>(nout, g, z, t, mu, curv, B, prm);
+		else F::template nltc_block<NZMAX>(nout, g, z, t, mu, curv, B, prm, nrow);
+	}
+};
+
+// The problem's parameter row inside a kernel, for families that take parameters: published in LDS once per problem by lane 0
+// (ntg_prm_publish, followed by a barrier) and read back wave-uniform where a callback is called (ntg_prm_row).  A family without
+// parameters never instantiates the slot: its kernels have no extra LDS, no extra code, and ntg_prm_row is nullptr.
+template <int FAM> __device__ __forceinline__ const double *&ntg_prm_slot()
+{
+	__shared__ const double *row;
+	return row;
+}
+template <int FAM> __device__ __forceinline__ void ntg_prm_publish(const NtgTables &T, int b)
+{
+	if constexpr (fam_prm_kind<Family<FAM>>() != 0) { if (threadIdx.x == 0) ntg_prm_slot<FAM>() = T.prm + (size_t)b * T.pp_prm; }
+}
+template <int FAM> __device__ __forceinline__ const double *ntg_prm_row()
+{
+	if constexpr (fam_prm_kind<Family<FAM>>() == 0) return nullptr;
+	else {
+		const u64 v = (u64)ntg_prm_slot<FAM>();
+		const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+		return (const double *)(((u64)hi << 32) | lo);
+	}
+}
+
+// nltc_val / nltc_vjp through the dense callback (families with a handful of constraints); prm: the parameter row of a family that
+// takes one (FamCall)
 template <class Fam, int NZMAX>
 struct DenseTraj {
-	static __device__ __forceinline__ void val(int nout, int i, const double *z, double *c)
+	static __device__ __forceinline__ void val(int nout, int i, const double *z, double *c, const double *prm = nullptr)
 	{
 		double dc[(Fam::NNLTC > 0 ? Fam::NNLTC : 1) * NZMAX];
-		Fam::nltcf(nout, i, z, c, dc);
+		FamCall<Fam>{prm, 0}.nltcf(nout, i, z, c, dc);
 	}
-	static __device__ __forceinline__ void vjp(int nout, int nz, int i, const double *z, const double *t, double *df)
+	static __device__ __forceinline__ void vjp(int nout, int nz, int i, const double *z, const double *t, double *df, const double *prm = nullptr)
 	{
 		double c[Fam::NNLTC > 0 ? Fam::NNLTC : 1], dc[(Fam::NNLTC > 0 ? Fam::NNLTC : 1) * NZMAX];
-		Fam::nltcf(nout, i, z, c, dc);
+		FamCall<Fam>{prm, 0}.nltcf(nout, i, z, c, dc);
 		for (int j = 0; j < Fam::NNLTC; j++)
 #pragma unroll
 			for (int v = 0; v < NZMAX; v++) { if (v < nz) df[v] += t[j] * dc[j * nz + v]; }
@@ -310,5 +400,33 @@ template <> struct Family<NTG_FAM_MANIP> {
 				df[9 * j + 6] += t[j] * c3;
 			}
 		}
+	}
+};
+
+// The obstacle family with a per-problem field of m = nnltc <= 8 obstacles (obstacle_field.hpp): parameters [cx_0, cy_0, ...], NPARAM_ROW = 2
+// doubles per trajectory row function (FamCall form 2: every callback gets the row and the plan's nnltc)
+template <> struct Family<NTG_FAM_OBSTACLE_FIELD> {
+	using OF = ntg_amd::ObstacleField;
+	static constexpr int NPARAM_ROW = 2;
+	static __device__ __forceinline__ int row_group(int j) { (void)j; return 0; }   // coupling group of trajectory row function j (QP-based SQP step)
+	static constexpr int DM = 3, TAPE = 1;
+	static constexpr u64 TCON_VARS = ~0ull;   // flag entries a trajectory constraint row can depend on (all: not declared)
+	static constexpr bool PER_OUTPUT_COST = false;
+	static constexpr int COUPLE = 2, CG = 2;   // one group (x, y); constraint flag entries x, y
+	template <int NZMAX> static __device__ __forceinline__ void nltc_block(int, int, const double *z, const double *t, double mu, bool curv, double *B, const double *prm, int m)
+	{
+		OF::block(m, z, t, mu, curv, B, prm);
+	}
+	static constexpr int NNLIC = 0, NNLTC = OF::MAXOBS, NNLFC = 0;
+	static __device__ __forceinline__ void ucf(int nout, int, const double *z, double &f, double *df, const double *, int) { OF::ucf(nout, z, f, df); }
+	static __device__ __forceinline__ void icf(int, const double *, double &f, double *, const double *, int) { f = 0.0; }
+	static __device__ __forceinline__ void fcf(int, const double *, double &f, double *, const double *, int) { f = 0.0; }
+	static __device__ __forceinline__ void nlicf(int, const double *, double *, double *, const double *, int) {}
+	static __device__ __forceinline__ void nlfcf(int, const double *, double *, double *, const double *, int) {}
+	static __device__ __forceinline__ void nltcf(int nout, int, const double *z, double *c, double *dc, const double *prm, int m) { OF::dense(nout, m, z, c, dc, prm); }
+	template <int NZMAX> static __device__ __forceinline__ void nltc_val(int, int, const double *z, double *c, double *, const double *prm, int m) { OF::val(m, z, c, prm); }
+	template <int NZMAX> static __device__ __forceinline__ void nltc_vjp(int, int, int, const double *z, const double *t, double *df, const double *, const double *prm, int m)
+	{
+		OF::vjp(m, z, t, df, prm);
 	}
 };

@@ -27,6 +27,7 @@ struct ntg_family_module_desc {
 	int nout;                 // outputs a plan must have (0: any)
 	ntg_module_eval_fn launch_eval;
 	ntg_module_sqp_fn launch_sqp;
+	int nparam, nparam_bp;    // per-problem parameters: doubles per problem, doubles per breakpoint (ntg_plan_param_count)
 };
 typedef const ntg_family_module_desc *(*ntg_family_module_entry_fn)(void);
 

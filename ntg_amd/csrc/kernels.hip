@@ -433,7 +433,7 @@ SmemLayout ntg_make_layout(const NtgDims &D, int nthreads, int nvec, int with_x,
 #define NTG_FAM_DECL(NAME)                                                                                         \
 	hipError_t ntg_launch_eval_##NAME(const NtgDims &, const NtgTables &, const SmemLayout &, const EvalArgs &);   \
 	hipError_t ntg_launch_sqp_##NAME(const NtgDims &, const NtgTables &, const SmemLayout &, const SolveParams &, const SqpArgs &);
-NTG_FAM_DECL(kincar) NTG_FAM_DECL(vanderpol) NTG_FAM_DECL(testfam) NTG_FAM_DECL(obstacle) NTG_FAM_DECL(quadrotor) NTG_FAM_DECL(manip)
+NTG_FAM_DECL(kincar) NTG_FAM_DECL(vanderpol) NTG_FAM_DECL(testfam) NTG_FAM_DECL(obstacle) NTG_FAM_DECL(quadrotor) NTG_FAM_DECL(manip) NTG_FAM_DECL(obstacle_field)
 #undef NTG_FAM_DECL
 // any other id: a family module loaded at run time (family_registry.cpp) launches its own generic instances
 
@@ -446,6 +446,7 @@ hipError_t ntg_launch_eval(const NtgDims &D, const NtgTables &T, const SmemLayou
 	case NTG_FAM_OBSTACLE: return ntg_launch_eval_obstacle(D, T, L, a);
 	case NTG_FAM_QUADROTOR: return ntg_launch_eval_quadrotor(D, T, L, a);
 	case NTG_FAM_MANIP: return ntg_launch_eval_manip(D, T, L, a);
+	case NTG_FAM_OBSTACLE_FIELD: return ntg_launch_eval_obstacle_field(D, T, L, a);
 	default:
 		if (const ntg_family_module_desc *m = ntg_family_module(D.family)) return m->launch_eval(D, T, L, a);
 	}
@@ -461,6 +462,7 @@ hipError_t ntg_launch_sqp(const NtgDims &D, const NtgTables &T, const SmemLayout
 	case NTG_FAM_OBSTACLE: return ntg_launch_sqp_obstacle(D, T, L, sp, a);
 	case NTG_FAM_QUADROTOR: return ntg_launch_sqp_quadrotor(D, T, L, sp, a);
 	case NTG_FAM_MANIP: return ntg_launch_sqp_manip(D, T, L, sp, a);
+	case NTG_FAM_OBSTACLE_FIELD: return ntg_launch_sqp_obstacle_field(D, T, L, sp, a);
 	default:
 		if (const ntg_family_module_desc *m = ntg_family_module(D.family)) return m->launch_sqp(D, T, L, sp, a);
 	}

@@ -113,6 +113,9 @@ struct NtgTables {
 	const unsigned char *q_pinned;   // [nC] 1: coefficient c is pinned by the equality rows (NtgDims::q_pin plans only)
 	const int *q_col;      // [q_nt][q_w]
 	const double *q_val;   // [q_nt][q_w], zero padded
+	// per-problem family parameters (ntg_plan_set_params): problem b reads prm + b pp_prm (nullptr / 0: none set).  Read only on the device,
+	// the same row for every lane of a problem; the family callbacks get it through FamCall (families.hpp)
+	const double *prm; long long pp_prm;
 };
 
 // words per column of the column form (see NtgTables::colp)

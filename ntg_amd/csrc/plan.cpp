@@ -127,7 +127,7 @@ extern "C" int ntg_plan_create(const ntg_spec *s, int device, ntg_plan **out)
 	D.nbounds = s->nlic + s->nltc + s->nlfc + s->nnlic + s->nnltc + s->nnlfc;
 	const ntg_family_module_desc *mod = ntg_family_module(s->family);   // a family loaded by ntg_family_load (nullptr: built in, or unknown)
 	if (s->family != NTG_FAM_KINCAR && s->family != NTG_FAM_VANDERPOL && s->family != NTG_FAM_TESTFAM && s->family != NTG_FAM_OBSTACLE &&
-	    s->family != NTG_FAM_QUADROTOR && s->family != NTG_FAM_MANIP && s->family != NTG_FAM_HOST && !mod) {
+	    s->family != NTG_FAM_QUADROTOR && s->family != NTG_FAM_MANIP && s->family != NTG_FAM_OBSTACLE_FIELD && s->family != NTG_FAM_HOST && !mod) {
 		delete p; return fail(NTG_E_BADARG, "unknown problem family");
 	}
 	if (mod) {
@@ -149,6 +149,9 @@ extern "C" int ntg_plan_create(const ntg_spec *s, int device, ntg_plan **out)
 	if (s->family == NTG_FAM_TESTFAM && (s->nnlic > 1 || s->nnltc > 2 || s->nnlfc > 1)) { delete p; return fail(NTG_E_BADARG, "testfam has 1/2/1 nonlinear constraints"); }
 	if ((s->family == NTG_FAM_KINCAR || s->family == NTG_FAM_VANDERPOL) && D.ncnln > 0) { delete p; return fail(NTG_E_BADARG, "family has no nonlinear constraints"); }
 	if (s->family == NTG_FAM_OBSTACLE && (s->nout != 2 || s->nnlic || s->nnlfc || s->nnltc > 1)) { delete p; return fail(NTG_E_BADARG, "obstacle family: 2 outputs, at most one trajectory constraint"); }
+	if (s->family == NTG_FAM_OBSTACLE_FIELD && (s->nout != 2 || s->nnlic || s->nnlfc || s->nnltc < 1 || s->nnltc > 8)) {
+		delete p; return fail(NTG_E_BADARG, "obstacle-field family: 2 outputs, 1 to 8 trajectory constraints (one per obstacle), no initial or final rows");
+	}
 
 	bool ok = true;
 	D.icost_mask = av_mask(D, s->icostav, s->nicostav, &ok);
@@ -484,7 +487,8 @@ static int build_newton_tables(ntg_plan *p)
 	u64 gmask = 0;   // constraint flag entries of group 0, relative to the group's first flag entry
 	const int dm = D.d[0];
 	switch (D.family) {
-	case NTG_FAM_OBSTACLE: go = 2; cg = 2; gmask = (1ull << 0) | (1ull << 3); break;
+	case NTG_FAM_OBSTACLE:
+	case NTG_FAM_OBSTACLE_FIELD: go = 2; cg = 2; gmask = (1ull << 0) | (1ull << 3); break;
 	// (x, y, z) couple through thrust and speed; the yaw output appears in no row: a FREE output -- its block of the model is the cost
 	// model's, the same for every problem and every refresh, factored once here (nwt_lf) and solved by an otherwise idle wave
 	case NTG_FAM_QUADROTOR: go = 3; cg = 6; gmask = (1ull << 1) | (1ull << 2) | (1ull << 6) | (1ull << 7) | (1ull << 11) | (1ull << 12); break;
@@ -703,6 +707,7 @@ extern "C" void ntg_plan_destroy(ntg_plan *p)
 	hipSetDevice(p->device);
 	for (void *q : p->owned) hipFree(q);
 	for (void *q : p->grid_owned) hipFree(q);
+	if (p->d_prm) hipFree(p->d_prm);
 	delete p;
 }
 
@@ -1002,6 +1007,62 @@ extern "C" long long ntg_batch_workspace_bytes(const ntg_plan *p, int batch, con
 	return (long long)(dbl * 8 + 256);
 }
 
+// per-problem family parameters (ntg_plan_set_params): doubles per problem the plan's family needs, 0 for a family without
+static int param_count(const ntg_plan *p)
+{
+	if (p->D.family == NTG_FAM_OBSTACLE_FIELD) return 2 * p->D.nnltc;   // (cx_j, cy_j) per trajectory row function
+	if (const ntg_family_module_desc *m = ntg_family_module(p->D.family)) return m->nparam + m->nparam_bp * p->D.P;
+	return 0;
+}
+
+// the callbacks of eval / solve / mpc_run read problem b's parameter row: the family's parameters must be set, for this batch
+static int check_params(const ntg_plan *p, int batch)
+{
+	if (p->prm_batch && batch != p->prm_batch)
+		return fail(NTG_E_BADARG, "the plan carries per-problem parameters for " + std::to_string(p->prm_batch) + " problems, not " + std::to_string(batch));
+	if (!p->prm_batch && param_count(p) > 0)
+		return fail(NTG_E_BADARG, "the plan's family reads " + std::to_string(param_count(p)) + " parameters per problem: set them with ntg_plan_set_params");
+	return 0;
+}
+
+extern "C" int ntg_plan_param_count(const ntg_plan *p, int *nparam)
+{
+	if (!p || !nparam) return fail(NTG_E_BADARG, "null argument");
+	*nparam = param_count(p);
+	return 0;
+}
+
+extern "C" void ntg_plan_clear_params(ntg_plan *p)
+{
+	if (!p || !p->d_prm) return;
+	hipSetDevice(p->device);
+	hipDeviceSynchronize();   // queued kernels may still read the buffer
+	hipFree(p->d_prm);
+	p->d_prm = nullptr; p->prm_cap = 0; p->prm_batch = 0; p->prm_n = 0;
+	p->T.prm = nullptr; p->T.pp_prm = 0;
+}
+
+extern "C" int ntg_plan_set_params(ntg_plan *p, int batch, int nparam, const double *d_params, void *stream)
+{
+	if (!p) return fail(NTG_E_BADARG, "null plan");
+	if (p->D.family == NTG_FAM_HOST) return fail(NTG_E_UNSUPPORTED, "host-callback plans keep their parameters in the callbacks' own data");
+	const int want = param_count(p);
+	if (want == 0) return fail(NTG_E_BADARG, "the plan's family takes no per-problem parameters");
+	if (nparam != want) return fail(NTG_E_BADARG, "the plan's family takes " + std::to_string(want) + " parameters per problem, not " + std::to_string(nparam));
+	if (batch <= 0 || !d_params) return fail(NTG_E_BADARG, "bad argument");
+	HIPCHK(hipSetDevice(p->device));
+	const size_t n = (size_t)batch * nparam;
+	if (n != p->prm_cap) {   // same batch x nparam: the buffer (and so its address, e.g. in a captured graph) stays
+		ntg_plan_clear_params(p);
+		HIPCHK(hipMalloc((void **)&p->d_prm, n * sizeof(double)));
+		p->prm_cap = n;
+	}
+	HIPCHK(hipMemcpyAsync(p->d_prm, d_params, n * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+	p->prm_batch = batch; p->prm_n = nparam;
+	p->T.prm = p->d_prm; p->T.pp_prm = nparam;
+	return 0;
+}
+
 extern "C" int ntg_batch_bounds(const ntg_plan *p, int batch, const double *d_lower, const double *d_upper,
                                 double *d_bl, double *d_bu, void *stream)
 {
@@ -1020,6 +1081,7 @@ extern "C" int ntg_batch_eval(const ntg_plan *p, int batch, const double *d_x, i
 	if (mode < 0 || mode > 2) return fail(NTG_E_BADARG, "mode must be 0, 1 or 2");
 	if (p->D.family == NTG_FAM_HOST) return fail(NTG_E_UNSUPPORTED, "host-callback plans evaluate through npsolCostFunction");
 	if (p->grid_batch && batch != p->grid_batch) return fail(NTG_E_BADARG, "the plan carries per-problem grids for another batch size");
+	if (int rc = check_params(p, batch)) return rc;
 	if (batch <= 0) return 0;
 	HIPCHK(hipSetDevice(p->device));
 	const NtgDims &D = p->D;
@@ -1052,6 +1114,7 @@ extern "C" int ntg_batch_solve(const ntg_plan *pc, int batch, const double *d_lo
 	if (!d_x || !d_lower || !d_upper) return fail(NTG_E_BADARG, "null argument");
 	if (p->D.family == NTG_FAM_HOST) return fail(NTG_E_UNSUPPORTED, "host-callback plans are solved by ntg()");
 	if (p->grid_batch && batch != p->grid_batch) return fail(NTG_E_BADARG, "the plan carries per-problem grids for another batch size");
+	if (int rc = check_params(p, batch)) return rc;
 	if (!p->lin_ok) return fail(NTG_E_BADARG, "linear constraint rows are rank deficient");
 	if (batch <= 0) return 0;
 	HIPCHK(hipSetDevice(p->device));
@@ -1112,6 +1175,7 @@ extern "C" int ntg_batch_mpc_run(const ntg_plan *p, int batch, int nsteps, int s
 	if (!d_x || !d_lower || !d_upper || !d_inform) return fail(NTG_E_BADARG, "null argument");
 	if (shift_bp < 0 || shift_bp >= p->D.P || shift_knots < 0) return fail(NTG_E_BADARG, "shift out of range");
 	if (p->grid_batch && batch != p->grid_batch) return fail(NTG_E_BADARG, "the plan carries per-problem grids for another batch size");
+	if (int rc = check_params(p, batch)) return rc;
 	HIPCHK(hipSetDevice(p->device));
 	hipStream_t st = (hipStream_t)stream, own = nullptr;
 	if (!st) { HIPCHK(hipStreamCreateWithFlags(&own, hipStreamNonBlocking)); st = own; }   // the legacy default stream cannot be captured
@@ -1281,6 +1345,7 @@ extern "C" void ntg_plan_clear_grids(ntg_plan *p)
 	for (void *q : p->grid_owned) hipFree(q);
 	p->grid_owned.clear();
 	p->T = p->T_shared;
+	p->T.prm = p->prm_batch ? p->d_prm : nullptr; p->T.pp_prm = p->prm_batch ? p->prm_n : 0;   // the parameters stay in force
 	p->grid_batch = 0; p->d_grid_knots = nullptr;
 }
 
@@ -1471,7 +1536,7 @@ extern "C" int ntg_batch_kincar_reverse(const ntg_plan *p, int batch, int ntimes
 	if (batch <= 0 || ntimes <= 0) return 0;
 	if (!d_z || !d_state) return fail(NTG_E_BADARG, "null argument");
 	const NtgDims &D = p->D;
-	if ((D.family != NTG_FAM_KINCAR && D.family != NTG_FAM_OBSTACLE) || D.nout % 2 || D.nz != 3 * D.nout)
+	if ((D.family != NTG_FAM_KINCAR && D.family != NTG_FAM_OBSTACLE && D.family != NTG_FAM_OBSTACLE_FIELD) || D.nout % 2 || D.nz != 3 * D.nout)
 		return fail(NTG_E_UNSUPPORTED, "kincar_flat_reverse needs a kincar-family plan (two outputs per car, three flag entries per output)");
 	if (!(wheelbase > 0.0)) return fail(NTG_E_BADARG, "wheelbase must be positive");
 	HIPCHK(hipSetDevice(p->device));

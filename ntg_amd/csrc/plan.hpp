@@ -36,6 +36,9 @@ struct ntg_plan {
 	double *d_linrows = nullptr; int *d_qrow2coef = nullptr, *d_planoff = nullptr, *d_erow = nullptr; unsigned char *d_qpad = nullptr;
 	std::vector<double> h_qval;
 	std::vector<double *> d_knots;              // break sequence of every basis class (ntg_batch_interp)
+	// per-problem family parameters (ntg_plan_set_params): the plan's own buffer [prm_batch][prm_n] (prm_cap doubles allocated), the batch
+	// they were set for (0: none); NtgTables::prm / pp_prm point into it (ntg_plan_clear_grids puts them back after restoring the tables)
+	double *d_prm = nullptr; size_t prm_cap = 0; int prm_batch = 0, prm_n = 0;
 };
 
 void ntg_plan_dense_A(const ntg_plan *p, double *A);

@@ -574,6 +574,7 @@ __device__ __forceinline__ void cost_phase1(const NtgDims &D, const Smem &S, con
 	constexpr int NI = Fam::NNLIC > 0 ? Fam::NNLIC : 1, NTc = Fam::NNLTC > 0 ? Fam::NNLTC : 1, NF = Fam::NNLFC > 0 ? Fam::NNLFC : 1;
 	const bool alon = HASCON && al.mu > 0.0;
 	const int b0 = D.nlic + D.nltc + D.nlfc;   // first nonlinear slot of lowerb/upperb
+	const FamCall<Fam> fc{ntg_prm_row<FAM>(), D.nnltc};
 	psi = 0.0; rv2 = 0.0;
 	// one constraint value -> AL term, violation, multiplier estimate; returns t
 	auto al_term = [&](double cj, int row, int slot) -> double {
@@ -589,7 +590,7 @@ __device__ __forceinline__ void cost_phase1(const NtgDims &D, const Smem &S, con
 		for (int i = tid; i < P; i += NT) {                       // cost.c:103-109
 			double z[NZ], df[NZ], f = 0.0;
 			compute_z<NOUT, K, DM, CHM>(D, S, sx, i, zmask, z, chm_now);
-			if (D.nucf) Fam::ucf(nout, i, z, f, df);
+			if (D.nucf) fc.ucf(nout, i, z, f, df);
 			else {
 #pragma unroll
 				for (int v = 0; v < NZ; v++) df[v] = 0.0;
@@ -601,10 +602,10 @@ __device__ __forceinline__ void cost_phase1(const NtgDims &D, const Smem &S, con
 			if (HASCON && alon && D.nnltc) {                      // constraints.c:148-155 folded into the same pass
 				double c[NTc], t[NTc];
 				double tape[Fam::TAPE];
-				Fam::template nltc_val<NZ>(nout, i, z, c, tape);
+				fc.template nltc_val<NZ>(nout, i, z, c, tape);
 #pragma unroll
 				for (int j = 0; j < NTc; j++) t[j] = j < D.nnltc ? al_term(c[j], D.nnlic + j * P + i, b0 + D.nnlic + j) : 0.0;
-				Fam::template nltc_vjp<NZ>(nout, nz, i, z, t, df, tape);   // df += J' t, constraint-major like the dense loop
+				fc.template nltc_vjp<NZ>(nout, nz, i, z, t, df, tape);   // df += J' t, constraint-major like the dense loop
 			}
 			if (chm_now) {
 				// the weighted-gradient rows are (output, channel of CHM) in flag order: row = o NCH + rank(r)
@@ -622,10 +623,10 @@ __device__ __forceinline__ void cost_phase1(const NtgDims &D, const Smem &S, con
 	if ((D.nicf || (alon && D.nnlic)) && tid == 0) {              // cost.c:4-36, constraints.c:88-117
 		double z[NZ], df[NZ], f = 0.0;
 		compute_z<NOUT, K, DM>(D, S, sx, 0, alon ? (D.icost_mask | D.icon_mask) : D.icost_mask, z);
-		if (D.nicf) Fam::icf(nout, z, f, df); else for (int v = 0; v < nz; v++) df[v] = 0.0;
+		if (D.nicf) fc.icf(nout, z, f, df); else for (int v = 0; v < nz; v++) df[v] = 0.0;
 		if (HASCON && alon && D.nnlic) {
 			double c[NI], dc[NI * NZ];
-			Fam::nlicf(nout, z, c, dc);
+			fc.nlicf(nout, z, c, dc);
 			for (int j = 0; j < D.nnlic; j++) { const double t = al_term(c[j], j, b0 + j); for (int v = 0; v < nz; v++) df[v] += t * dc[j * nz + v]; }
 		}
 		for (int v = 0; v < nz; v++) S.dfi[v] = df[v];
@@ -634,10 +635,10 @@ __device__ __forceinline__ void cost_phase1(const NtgDims &D, const Smem &S, con
 	if ((D.nfcf || (alon && D.nnlfc)) && tid == (NT > 64 ? 64 : 0)) {   // cost.c:141-174, constraints.c:165-195
 		double z[NZ], df[NZ], f = 0.0;
 		compute_z<NOUT, K, DM>(D, S, sx, P - 1, alon ? (D.fcost_mask | D.fcon_mask) : D.fcost_mask, z);
-		if (D.nfcf) Fam::fcf(nout, z, f, df); else for (int v = 0; v < nz; v++) df[v] = 0.0;
+		if (D.nfcf) fc.fcf(nout, z, f, df); else for (int v = 0; v < nz; v++) df[v] = 0.0;
 		if (HASCON && alon && D.nnlfc) {
 			double c[NF], dc[NF * NZ];
-			Fam::nlfcf(nout, z, c, dc);
+			fc.nlfcf(nout, z, c, dc);
 			for (int j = 0; j < D.nnlfc; j++) { const double t = al_term(c[j], D.nnlic + D.nnltc * P + j, b0 + D.nnlic + D.nnltc + j); for (int v = 0; v < nz; v++) df[v] += t * dc[j * nz + v]; }
 		}
 		for (int v = 0; v < nz; v++) S.dff[v] = df[v];
@@ -884,6 +885,7 @@ __device__ __forceinline__ void eval_constraints(const NtgDims &D, const Smem &S
 	constexpr int DM = Fam::DM, NZ = NOUT > 0 ? DM * NOUT : NTG_MAX_NZ;
 	constexpr int NI = Fam::NNLIC > 0 ? Fam::NNLIC : 1, NTc = Fam::NNLTC > 0 ? Fam::NNLTC : 1, NF = Fam::NNLFC > 0 ? Fam::NNLFC : 1;
 	const int P = D.P, nout = NOUT > 0 ? NOUT : D.nout, nz = D.nz, tid = threadIdx.x;
+	const FamCall<Fam> fc{ntg_prm_row<FAM>(), D.nnltc};
 	auto emit_row = [&](int row, int bp, const double *dcrow, double *jb) {
 		for (int o = 0; o < nout; o++) {
 			const int k = D.order[o], cc = D.cls[o], d = D.d[o];
@@ -902,7 +904,7 @@ __device__ __forceinline__ void eval_constraints(const NtgDims &D, const Smem &S
 	if (Fam::NNLIC > 0 && D.nnlic && tid == 0) {
 		double z[NZ], c[NI], dc[NI * NZ];
 		compute_z<NOUT, K, DM>(D, S, sx, 0, D.icon_mask, z);
-		Fam::nlicf(nout, z, c, dc);
+		fc.nlicf(nout, z, c, dc);
 		for (int j = 0; j < D.nnlic; j++) {
 			if (c_out && mode != 1) c_out[j] = c[j];
 			if (mode != 0) emit_row(j, 0, dc + j * nz, jband);
@@ -929,7 +931,7 @@ __device__ __forceinline__ void eval_constraints(const NtgDims &D, const Smem &S
 			for (int i = tid; i < P; i += NT) {
 				if (!keep || j0 == 0) {
 					compute_z<NOUT, K, DM>(D, S, sx, i, D.tcon_mask, z);
-					Fam::template nltc_val<NZ>(nout, i, z, c, tape);
+					fc.template nltc_val<NZ>(nout, i, z, c, tape);
 					EVCLK(6);
 				}
 				for (int j = j0; j < j0 + jn; j++) {
@@ -943,7 +945,7 @@ __device__ __forceinline__ void eval_constraints(const NtgDims &D, const Smem &S
 					for (int jj = 0; jj < NTc; jj++) t[jj] = jj == j ? 1.0 : 0.0;
 #pragma unroll
 					for (int v = 0; v < NZ; v++) dcr[v] = 0.0;
-					Fam::template nltc_vjp<NZ>(nout, nz, i, z, t, dcr, tape);
+					fc.template nltc_vjp<NZ>(nout, nz, i, z, t, dcr, tape);
 					if (cjac || !coalesced) emit_row(row, i, dcr, coalesced ? nullptr : jband);
 					if (coalesced && sparse_vars) {
 						// the family says which flag entries its rows can touch: only those are copied (12 of config E's 36, 6 of D's 20;
@@ -1098,7 +1100,7 @@ __device__ __forceinline__ void eval_constraints(const NtgDims &D, const Smem &S
 	if (Fam::NNLFC > 0 && D.nnlfc && tid == (NT > 64 ? 64 : 0)) {
 		double z[NZ], c[NF], dc[NF * NZ];
 		compute_z<NOUT, K, DM>(D, S, sx, P - 1, D.fcon_mask, z);
-		Fam::nlfcf(nout, z, c, dc);
+		fc.nlfcf(nout, z, c, dc);
 		for (int j = 0; j < D.nnlfc; j++) {
 			const int row = D.nnlic + D.nnltc * P + j;
 			if (c_out && mode != 1) c_out[row] = c[j];
@@ -1146,6 +1148,7 @@ eval_kernel(NtgDims D, NtgTables T, SmemLayout L, int batch, int mode, const dou
 	for (int b = blockIdx.x; b < batch; b += gridDim.x) {
 		lds_sync();
 		if (pp) { stage_tables<NT>(D, T, S, smem_raw, L, b); lds_sync(); }
+		if constexpr (fam_prm_kind<Family<FAM>>() != 0) { ntg_prm_publish<FAM>(T, b); lds_sync(); }
 		if (xreg) {
 #pragma unroll
 			for (int e = 0; e < XE; e++) { const int i = threadIdx.x + e * NT; if (i < D.nC) S.x[i] = xn[e]; }
@@ -1600,6 +1603,7 @@ sqp_kernel(NtgDims D, NtgTables T, SmemLayout L, SolveParams sp, int batch,
 	constexpr bool DF_OK = !NWT && !BIG && EPT <= 4 && Family<FAM>::NNLIC + Family<FAM>::NNLTC + Family<FAM>::NNLFC == 0;
 	const bool dform = DF_OK && NTG_DFORM && D.nI == 0 && D.nC <= 3 * NT && hrc != nullptr && sp.memcap >= sp.itlim && L.hrc_n > sp.memcap;   // pair scalars (rho, c2): LDS for memories that fit, else with the pair in HBM
 	stage_tables<NT>(D, T, S, smem_raw, L, b);
+	ntg_prm_publish<FAM>(T, b);   // (families with parameters; the barrier below orders it before the first evaluation)
 	NtgTables Tw = T;   // the preconditioner blocks of this problem (per-problem grids) or the shared ones (stride 0)
 	if (HESS && T.n0b) Tw.n0b = T.n0b + (size_t)b * T.pp_n0b;
 	if (NWT && T.nwt_k0) { Tw.nwt_k0 = T.nwt_k0 + (size_t)b * T.pp_k0; Tw.nwt_lf = T.nwt_lf + (size_t)b * T.pp_lf; }   // ... and the Newton mode's cost model / free-output factors
@@ -1677,7 +1681,7 @@ sqp_kernel(NtgDims D, NtgTables T, SmemLayout L, SolveParams sp, int batch,
 					for (int j = 0; j < NTc; j++) t[j] = j < D.nnltc ? tsrc[D.nnlic + j * P2 + i] : 0.0;
 					for (int g = 0; g < ngp; g++) {
 						double Bk[NWT_CG2];
-						FamN::template nltc_block<NZ>(NOUT > 0 ? NOUT : D.nout, g, z, t, mu_gn, curv, Bk);
+						FamCall<FamN>{ntg_prm_row<FAM>(), D.nnltc}.template nltc_block<NZ>(NOUT > 0 ? NOUT : D.nout, g, z, t, mu_gn, curv, Bk);
 						bool nzb = false;
 #pragma unroll
 						for (int e = 0; e < NWT_CG2; e++) { nwt_B[((size_t)g * P2 + i) * NWT_CG2 + e] = Bk[e]; nzb = nzb || Bk[e] != 0.0; }
@@ -1885,7 +1889,7 @@ sqp_kernel(NtgDims D, NtgTables T, SmemLayout L, SolveParams sp, int batch,
 			if (what == 0) {
 				double z[NZ], c[NTc], tape[FamN::TAPE];
 				compute_z<NOUT, K, DM>(D, S, sxt, i, D.tcon_mask, z);   // (the trial-point buffer holds x here -- in LDS also for the BIG layouts, whose x lives in HBM)
-				FamN::template nltc_val<NZ>(NOUT > 0 ? NOUT : D.nout, i, z, c, tape);
+				FamCall<FamN>{ntg_prm_row<FAM>(), D.nnltc}.template nltc_val<NZ>(NOUT > 0 ? NOUT : D.nout, i, z, c, tape);
 #pragma unroll
 				for (int j = 0; j < NTc; j++) {
 					if (j >= D.nnltc) continue;
@@ -1894,7 +1898,7 @@ sqp_kernel(NtgDims D, NtgTables T, SmemLayout L, SolveParams sp, int batch,
 					for (int v = 0; v < NZ; v++) df[v] = 0.0;
 #pragma unroll
 					for (int jj = 0; jj < NTc; jj++) t[jj] = jj == j ? 1.0 : 0.0;
-					FamN::template nltc_vjp<NZ>(NOUT > 0 ? NOUT : D.nout, D.nz, i, z, t, df, tape);
+					FamCall<FamN>{ntg_prm_row<FAM>(), D.nnltc}.template nltc_vjp<NZ>(NOUT > 0 ? NOUT : D.nout, D.nz, i, z, t, df, tape);
 					const int g = FamN::row_group(j), row = j * P + i;
 					double jw = 0.0;
 					for (int u = 0; u < FamN::CG; u++) {

@@ -17,6 +17,7 @@ FAM_TESTFAM = 2
 FAM_OBSTACLE = 3
 FAM_QUADROTOR = 4
 FAM_MANIP = 5
+FAM_OBSTACLE_FIELD = 6
 
 
 def linspace_c(d0: float, d1: float, n: int) -> np.ndarray:
