@@ -14,6 +14,7 @@
  *   ntg_plan_tables      colloc.h:42-71  read-back of Block.matrix / Block.offset / A
  *   ntg_basis_batch      colloc.c:92-111 the same basis evaluation for many grids at once
  *   ntg_plan_set_grids   ntg.c:114-229 per problem: own knots and breakpoints for every problem of a batch
+ *   ntg_plan_grid_tables the read-back of ntg_plan_tables for one problem's grid
  *   ntg_plan_set_params  the file-scope parameter globals of the examples (kincar.c:43 default_params), one row per problem
  *   ntg_batch_eval       ntg.c:274-371   NPfunobj + NPfuncon (cost.c, constraints.c, integrator.c)
  *   ntg_batch_bounds     constraints.c:5-33 bounds()
@@ -177,13 +178,21 @@ int ntg_basis_batch(int ngrids, int ninterv, int order, int mult, int maxderiv, 
  * structure must be the plan's: one basis class, and every breakpoint in the same knot interval as in the plan's grid (checked;
  * NTG_E_BADARG otherwise) -- the index tables stay shared, the VALUES (basis blocks, trapezoid weights, linear-constraint rows,
  * (A A')^-1, projector, with_precond != 0: the preconditioner blocks) become per problem.  Nonlinear rows are allowed (free final time
- * with obstacle / thrust / speed rows: their evaluation and the augmented-Lagrangian solve read the same per-problem tables); linear
- * inequality rows are not (NTG_E_UNSUPPORTED).
+ * with obstacle / thrust / speed rows: their evaluation and the augmented-Lagrangian solve read the same per-problem tables), and so are
+ * linear rows declared as inequalities (ntg_spec.lin_ineq: a corridor ceiling, an end-state window; also when every linear row is one):
+ * their values on the plan's sparsity pattern are computed for every grid.  A grid that puts weight (above 1e-10 x the row's largest
+ * entry) where the plan's pattern of a linear row, equality or inequality, has an exact zero is refused with NTG_E_UNSUPPORTED; the
+ * message names the problem and the row.  Plans with inequality rows are solved by the general kernel (sqp_kernel), hessian = 2 / 3
+ * acting as 1, on per-problem grids as on the plan's own.
  * Afterwards ntg_batch_eval / ntg_batch_solve / ntg_batch_interp of exactly `batch` problems use these grids (hessian = 2 / 3 included: the band model's cost part is built per grid;
  * ntg_batch_interp then takes d_times as [batch][ntimes]: every problem at its own times; ntg_batch_mpc_shift and ntg_batch_mpc_run
  * re-pin with every problem's own basis blocks) until ntg_plan_clear_grids(). */
 int ntg_plan_set_grids(ntg_plan *p, int batch, const double *d_knots, const double *d_bps, int with_precond, void *stream);
 void ntg_plan_clear_grids(ntg_plan *p);
+/* ntg_plan_tables for one problem of the per-problem grids in force: blk that problem's basis blocks, off the plan's (the grids share
+ * it), A dense column-major nclin x nC with every linear row, equality and inequality, in the plan's row order -- the values the solver
+ * reads for that problem.  Synchronous.  NTG_E_BADARG without per-problem grids or with problem outside [0, batch). */
+int ntg_plan_grid_tables(const ntg_plan *p, int problem, double *blk, int *off, double *A);
 
 /* Per-problem family parameters: the data a family's callbacks read besides the flat flag (obstacle centres, a reference to track),
  * one row of doubles per problem -- what the reference's examples keep in file-scope globals (kincar.c:43) while ntg() solves one

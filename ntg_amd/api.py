@@ -64,6 +64,7 @@ def lib():
         L.ntg_plan_destroy.argtypes = [C.c_void_p]
         L.ntg_plan_dims.argtypes = [C.c_void_p] + [ip] * 7
         L.ntg_plan_tables.argtypes = [C.c_void_p, dp, ip, dp]
+        L.ntg_plan_grid_tables.argtypes = [C.c_void_p, C.c_int, dp, ip, dp]
         L.ntg_batch_bounds.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.ntg_batch_eval.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6
         L.ntg_batch_solve.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -180,6 +181,16 @@ class Plan:
         blk = np.zeros(nblk); off = np.zeros((sp.nout, sp.nbps), dtype=np.int32)
         A = np.zeros((sp.nC, max(sp.nclin, 1)))
         _check(lib().ntg_plan_tables(self.h, blk.ctypes.data_as(dp), off.ctypes.data_as(ip), A.ctypes.data_as(dp)))
+        return dict(blk=blk, off=off, A=(A.T.copy() if sp.nclin else np.zeros((0, sp.nC))))
+
+    def grid_tables(self, b: int):
+        """tables() of problem b's grid after set_grids: its basis blocks, the plan's offsets, and A [nclin, nC] with the equality and
+        inequality rows the solver reads for that problem.  Raises without per-problem grids or for b outside [0, batch)."""
+        sp = self.spec
+        nblk = sum(sp.nbps * k * d for k, d in zip(sp.order, sp.maxderiv))
+        blk = np.zeros(nblk); off = np.zeros((sp.nout, sp.nbps), dtype=np.int32)
+        A = np.zeros((sp.nC, max(sp.nclin, 1)))
+        _check(lib().ntg_plan_grid_tables(self.h, int(b), blk.ctypes.data_as(dp), off.ctypes.data_as(ip), A.ctypes.data_as(dp)))
         return dict(blk=blk, off=off, A=(A.T.copy() if sp.nclin else np.zeros((0, sp.nC))))
 
     # ---- batched entry points; tensors are torch CUDA(HIP) float64/int32, contiguous ----

@@ -2,7 +2,7 @@
 //
 // ntg() builds its collocation per call (CollocMatrix per output, colloc.c:57-117; LinearConstraintsMatrix, constraints.c:198-261).
 // With per-problem grids the plan's combinatorial structure is shared and the VALUES are per problem (ntg_plan_set_grids, plan.cpp):
-// basis_kernel evaluates the basis blocks of every grid; the two kernels here derive everything else from them without leaving the
+// basis_kernel evaluates the basis blocks of every grid; the kernels here derive everything else from them without leaving the
 // device (round 2 did this algebra on host threads: 0.2 - 1.5 s for 16 384 grids):
 //   grid_rows_kernel  channel rows rowv[chrow[r] + q P + i] = D^r B_{off+q}(bps_i) (the layout eval_kernel / sqp_kernel stage), and
 //                     the check that every breakpoint lies in the plan's knot interval (block[i].offset, colloc.c:104-111)
@@ -10,6 +10,8 @@
 //                     the basis blocks of their breakpoint, constraints.c:225-261) as values of the plan's CSR / CSC patterns, a test
 //                     that nothing of weight falls outside the pattern, S = A A' in LDS, its Cholesky factor, (A A')^-1 on the plan's
 //                     pattern, and the projector Q = A'(A A')^-1 A on the plan's ELL pattern.
+//   grid_ilin_kernel  one wavefront per problem: the linear rows declared as inequalities (ntg_spec.lin_ineq) as values of the plan's
+//                     inequality CSR / CSC patterns, with the same test of weight outside them.
 // A row of A_E has support nout * k (the k basis functions of its breakpoint, for every output): the kernel keeps the m supports in
 // LDS and never forms the dense m x nC matrix.
 #include <hip/hip_runtime.h>
@@ -179,6 +181,69 @@ hipError_t ntg_launch_grid_lin(const NtgDims &D, int batch, const NtgGridLin &g,
 	if (lds > 160 * 1024) return hipErrorInvalidValue;
 	if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)grid_lin_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 	hipLaunchKernelGGL(grid_lin_kernel, dim3(batch), dim3(64), lds, st, D, batch, A);
+	return hipGetLastError();
+}
+
+// ---- linear inequality rows (ntg_spec.lin_ineq) of every grid ----
+// The rows the augmented-Lagrangian loop reads (LinIneq in sqp_kernel: c_j = A_j x, g += A_j' t) as values of the plan's inequality CSR / CSC
+// patterns: the user's row through the basis blocks of its breakpoint, the arithmetic of grid_lin_kernel step 1, with the same refusal of
+// weight outside the pattern (err 4: problem, plan row).  Nothing else: the loop needs no A A' and no projector.  One wavefront per problem,
+// lanes over rows (CSR, and the pattern check) and then over coefficients (CSC); every value is recomputed from the user's row (d products),
+// so the two forms hold the same doubles.  Runs whether or not there are equality rows.
+
+// the user's row behind plan row r of the linear constraints (lic; ltc at every breakpoint; lfc -- constraints.c:225-261) and its breakpoint
+__device__ __forceinline__ const double *grid_linrow(const NtgDims &D, const double *linrows, int r, int &bp)
+{
+	if (r < D.nlic) { bp = 0; return linrows + (size_t)r * D.nz; }
+	if (r < D.nlic + D.nltc * D.P) { const int rr = r - D.nlic; bp = rr % D.P; return linrows + (size_t)(D.nlic + rr / D.P) * D.nz; }
+	bp = D.P - 1;
+	return linrows + (size_t)(D.nlic + D.nltc + (r - D.nlic - D.nltc * D.P)) * D.nz;
+}
+
+// A(row, c) on this grid: sum_l row[iz[o] + l] D^l B_{off+q}(bp), 0 outside the k coefficients of the breakpoint's block
+__device__ __forceinline__ double grid_ival(const NtgDims &D, const double *row, const double *bk, int bp, int off, int c)
+{
+	const int k = D.cls_k[0], d = D.cls_d[0], nco = D.ncoef[0], o = c / nco, q = c - o * nco - off;
+	if (q < 0 || q >= k) return 0.0;
+	double acc = 0.0;
+	for (int l = 0; l < d; l++) acc += row[D.iz[o] + l] * bk[((size_t)bp * k + q) * d + l];
+	return acc;
+}
+
+__global__ void __launch_bounds__(64)
+grid_ilin_kernel(NtgDims D, int batch, NtgGridILin A)
+{
+	const int b = blockIdx.x, lane = threadIdx.x, k = D.cls_k[0], d = D.cls_d[0], nco = D.ncoef[0];
+	if (b >= batch) return;
+	const double *bk = A.blk + (size_t)b * D.P * k * d;
+	double *rv = A.icsr_val + (size_t)b * A.inz, *cv = A.icsc_val + (size_t)b * A.inz;
+	for (int j = lane; j < D.nI; j += 64) {
+		int bp;
+		const double *row = grid_linrow(D, A.linrows, A.irow[j], bp);
+		const int off = A.plan_off[bp];
+		double rmax = 0.0;
+		for (int o = 0; o < D.nout; o++)
+			for (int q = 0; q < k; q++) rmax = fmax(rmax, fabs(grid_ival(D, row, bk, bp, off, o * nco + off + q)));
+		for (int o = 0; o < D.nout; o++)
+			for (int q = 0; q < k; q++) {
+				const int c = o * nco + off + q;
+				bool in = false;
+				for (int e = A.icsr_ptr[j]; e < A.icsr_ptr[j + 1]; e++) if (A.icsr_col[e] == c) { in = true; break; }
+				if (!in && fabs(grid_ival(D, row, bk, bp, off, c)) > 1e-10 * rmax) { if (atomicCAS(&A.err[0], 0, 4) == 0) { A.err[1] = b; A.err[2] = A.irow[j]; } }
+			}
+		for (int e = A.icsr_ptr[j]; e < A.icsr_ptr[j + 1]; e++) rv[e] = grid_ival(D, row, bk, bp, off, A.icsr_col[e]);
+	}
+	for (int c = lane; c < D.nC; c += 64)
+		for (int e = A.icsc_ptr[c]; e < A.icsc_ptr[c + 1]; e++) {
+			int bp;
+			const double *row = grid_linrow(D, A.linrows, A.irow[A.icsc_row[e]], bp);
+			cv[e] = grid_ival(D, row, bk, bp, A.plan_off[bp], c);
+		}
+}
+
+hipError_t ntg_launch_grid_ilin(const NtgDims &D, int batch, const NtgGridILin &g, hipStream_t st)
+{
+	hipLaunchKernelGGL(grid_ilin_kernel, dim3(batch), dim3(64), 0, st, D, batch, g);
 	return hipGetLastError();
 }
 

@@ -116,6 +116,9 @@ struct NtgTables {
 	// per-problem family parameters (ntg_plan_set_params): problem b reads prm + b pp_prm (nullptr / 0: none set).  Read only on the device,
 	// the same row for every lane of a problem; the family callbacks get it through FamCall (families.hpp)
 	const double *prm; long long pp_prm;
+	// per-problem grids with linear inequality rows: problem b reads icsr_val + b pp_ilin and icsc_val + b pp_ilin (0: one shared grid;
+	// grids.hip, grid_ilin_kernel)
+	long long pp_ilin;
 };
 
 // words per column of the column form (see NtgTables::colp)

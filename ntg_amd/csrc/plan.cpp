@@ -369,6 +369,7 @@ extern "C" int ntg_plan_create(const ntg_spec *s, int device, ntg_plan **out)
 			    dev_upload(&d_cp, cptr.data(), cptr.size(), own) || dev_upload(&d_cr, crow.data(), crow.size(), own) ||
 			    dev_upload(&d_cv, cval.data(), cval.size(), own)) { ntg_plan_destroy(p); return NTG_E_HIP; }
 			T.irow = d_ir; T.icsr_ptr = d_rp; T.icsr_col = d_rc; T.icsr_val = d_rv; T.icsc_ptr = d_cp; T.icsc_row = d_cr; T.icsc_val = d_cv;
+			p->h_irow = irow; p->h_icsr_ptr = rptr; p->h_icsr_col = rcol; p->h_icsc_ptr = cptr; p->h_icsc_row = crow;
 		}
 		// S = A_E A_E' -> S^-1
 		std::vector<double> S((size_t)m * m, 0.0);
@@ -734,6 +735,41 @@ extern "C" int ntg_plan_tables(const ntg_plan *p, double *blk, int *off, double 
 	if (A && D.nclin) // column-major nclin x nC
 		for (int r = 0; r < D.nclin; r++)
 			for (int c = 0; c < D.nC; c++) A[(size_t)c * D.nclin + r] = p->h_Adense[(size_t)r * D.nC + c];
+	return 0;
+}
+
+// ntg_plan_tables for one problem's grid (after ntg_plan_set_grids): its basis blocks, and A scattered from the values the device holds
+// for it -- the equality rows' CSR values (grid_lin_kernel) and the inequality rows' (grid_ilin_kernel) -- on the plan's patterns
+extern "C" int ntg_plan_grid_tables(const ntg_plan *p, int problem, double *blk, int *off, double *A)
+{
+	if (!p) return fail(NTG_E_BADARG, "null plan");
+	if (!p->grid_batch) return fail(NTG_E_BADARG, "no per-problem grids are set (ntg_plan_set_grids)");
+	if (problem < 0 || problem >= p->grid_batch) return fail(NTG_E_BADARG, "problem out of range of the per-problem grids");
+	const NtgDims &D = p->D;
+	const NtgTables &T = p->T;
+	HIPCHK(hipSetDevice(p->device));
+	if (blk) {   // one basis class: every output reads the same [bp][q][r] table
+		const size_t nblk = (size_t)D.P * D.cls_k[0] * D.cls_d[0];
+		HIPCHK(hipMemcpy(blk, T.blk + (size_t)problem * T.pp_blk, nblk * 8, hipMemcpyDeviceToHost));
+		for (int o = 1; o < D.nout; o++) std::memcpy(blk + o * nblk, blk, nblk * 8);
+	}
+	if (off)
+		for (int o = 0; o < D.nout; o++) std::memcpy(off + (size_t)o * D.P, p->h_off.data(), (size_t)D.P * 4);
+	if (A && D.nclin) {   // column-major nclin x nC
+		std::fill(A, A + (size_t)D.nclin * D.nC, 0.0);
+		if (D.mE > 0 && D.lin_nnz > 0) {
+			std::vector<double> v(D.lin_nnz);
+			HIPCHK(hipMemcpy(v.data(), T.csr_val + (size_t)problem * T.pp_lin, v.size() * 8, hipMemcpyDeviceToHost));
+			for (int i = 0; i < D.mE; i++)
+				for (int e = p->h_csr_ptr[i]; e < p->h_csr_ptr[i + 1]; e++) A[(size_t)p->h_csr_col[e] * D.nclin + p->h_erow[i]] = v[e];
+		}
+		if (D.nI > 0 && p->h_icsr_ptr[D.nI] > 0) {
+			std::vector<double> v(p->h_icsr_ptr[D.nI]);
+			HIPCHK(hipMemcpy(v.data(), T.icsr_val + (size_t)problem * T.pp_ilin, v.size() * 8, hipMemcpyDeviceToHost));
+			for (int j = 0; j < D.nI; j++)
+				for (int e = p->h_icsr_ptr[j]; e < p->h_icsr_ptr[j + 1]; e++) A[(size_t)p->h_icsr_col[e] * D.nclin + p->h_irow[j]] = v[e];
+		}
+	}
 	return 0;
 }
 
@@ -1357,8 +1393,8 @@ extern "C" int ntg_plan_set_grids(ntg_plan *p, int batch, const double *d_knots,
 	if (D.family == NTG_FAM_HOST) return fail(NTG_E_UNSUPPORTED, "host-callback plans have one grid");
 	if (D.nclass != 1) return fail(NTG_E_UNSUPPORTED, "per-problem grids need one basis class (every output on the same knots / order / multiplicity)");
 	// Nonlinear rows are fine: their evaluation reads the same per-problem tables, and the structured Newton mode / the QP-based SQP step get
-	// the cost model and the free-output factors of every grid (step 4b, grids.hip grid_nwt_kernel).
-	if (D.nI > 0) return fail(NTG_E_UNSUPPORTED, "per-problem grids: plans without linear inequality rows so far");
+	// the cost model and the free-output factors of every grid (step 4b, grids.hip grid_nwt_kernel).  So are linear inequality rows: their
+	// values on the plan's patterns come from every grid too (step 3b, grids.hip grid_ilin_kernel).
 	HIPCHK(hipSetDevice(p->device));
 	ntg_plan_clear_grids(p);
 	if (with_precond) {
@@ -1394,17 +1430,22 @@ extern "C" int ntg_plan_set_grids(ntg_plan *p, int batch, const double *d_knots,
 	// 1. basis blocks and offsets of every problem: one launch of basis_kernel (bsplvd at every collocation point, colloc.c:95-111)
 	double *d_blk = nullptr; int *d_off = nullptr, *d_err = nullptr;
 	double *d_rowv = nullptr, *d_bpsc = nullptr, *d_csr = nullptr, *d_csc = nullptr, *d_sinv = nullptr, *d_q = nullptr, *d_n0b = nullptr, *d_knc = nullptr;
+	double *d_icsr = nullptr, *d_icsc = nullptr;
 	auto fail_free = [&](int code, const std::string &msg) {
-		for (void *q : {(void *)d_blk, (void *)d_off, (void *)d_err, (void *)d_rowv, (void *)d_bpsc, (void *)d_csr, (void *)d_csc, (void *)d_sinv, (void *)d_q, (void *)d_n0b, (void *)d_knc}) if (q) hipFree(q);
+		for (void *q : {(void *)d_blk, (void *)d_off, (void *)d_err, (void *)d_rowv, (void *)d_bpsc, (void *)d_csr, (void *)d_csc, (void *)d_sinv, (void *)d_q, (void *)d_n0b, (void *)d_knc,
+		                (void *)d_icsr, (void *)d_icsc}) if (q) hipFree(q);
 		return fail(code, msg);
 	};
+	const int inz = D.nI > 0 ? std::max(p->h_icsr_ptr[D.nI], 1) : 0;   // entries of the inequality rows (one problem)
 	const size_t n0b_sz = with_precond ? (size_t)p->T.n0b_nblk * p->T.n0b_sp * p->T.n0b_n + 16 : 0;
 	if (hipMalloc((void **)&d_blk, (size_t)batch * nblk * 8) != hipSuccess || hipMalloc((void **)&d_off, (size_t)batch * P * 4) != hipSuccess ||
 	    hipMalloc((void **)&d_err, 16) != hipSuccess || hipMalloc((void **)&d_rowv, (size_t)batch * row_total * 8) != hipSuccess ||
 	    hipMalloc((void **)&d_bpsc, (size_t)batch * P * 8) != hipSuccess || hipMalloc((void **)&d_csr, (size_t)batch * lin_nnz * 8) != hipSuccess ||
 	    hipMalloc((void **)&d_csc, (size_t)batch * lin_nnz * 8) != hipSuccess || hipMalloc((void **)&d_sinv, (size_t)batch * sinv_nnz * 8) != hipSuccess ||
 	    hipMalloc((void **)&d_q, (size_t)batch * std::max(qn, 1) * 8) != hipSuccess || hipMalloc((void **)&d_knc, (size_t)batch * (l + 1) * 8) != hipSuccess ||
-	    (with_precond && hipMalloc((void **)&d_n0b, (size_t)batch * n0b_sz * 8) != hipSuccess)) return fail_free(NTG_E_HIP, "hipMalloc (per-problem grids)");
+	    (with_precond && hipMalloc((void **)&d_n0b, (size_t)batch * n0b_sz * 8) != hipSuccess) ||
+	    (inz > 0 && (hipMalloc((void **)&d_icsr, (size_t)batch * inz * 8) != hipSuccess || hipMalloc((void **)&d_icsc, (size_t)batch * inz * 8) != hipSuccess)))
+		return fail_free(NTG_E_HIP, "hipMalloc (per-problem grids)");
 	hipError_t e = hipMemsetAsync(d_err, 0, 16, st);
 	if (e == hipSuccess) e = hipMemsetAsync(d_rowv, 0, (size_t)batch * row_total * 8, st);
 	if (e == hipSuccess) e = hipMemcpyAsync(d_bpsc, d_bps, (size_t)batch * P * 8, hipMemcpyDeviceToDevice, st);
@@ -1418,6 +1459,11 @@ extern "C" int ntg_plan_set_grids(ntg_plan *p, int batch, const double *d_knots,
 		             p->T.q_col, p->d_qrow2coef, p->d_qpad, d_csr, d_csc, d_sinv, d_q, d_err};
 		e = ntg_launch_grid_lin(D, batch, g, st);
 	}
+	// 3b. the linear inequality rows' values (no projection: the augmented-Lagrangian loop reads them as they are); also when every row is one
+	if (e == hipSuccess && inz > 0) {
+		NtgGridILin g{d_blk, p->d_linrows, p->d_planoff, p->T.irow, p->T.icsr_ptr, p->T.icsr_col, p->T.icsc_ptr, p->T.icsc_row, d_icsr, d_icsc, d_err, inz};
+		e = ntg_launch_grid_ilin(D, batch, g, st);
+	}
 	int herr[4] = {0, 0, 0, 0};
 	if (e == hipSuccess) e = hipMemcpyAsync(herr, d_err, 12, hipMemcpyDeviceToHost, st);
 	if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -1425,6 +1471,7 @@ extern "C" int ntg_plan_set_grids(ntg_plan *p, int batch, const double *d_knots,
 	if (herr[0] == 1) return fail_free(NTG_E_BADARG, "per-problem grid: a breakpoint lies in another knot interval than in the plan's grid (problem " + std::to_string(herr[1]) + ", breakpoint " + std::to_string(herr[2]) + ")");
 	if (herr[0] == 2) return fail_free(NTG_E_UNSUPPORTED, "per-problem grid: a linear-constraint entry outside the plan's sparsity pattern (problem " + std::to_string(herr[1]) + ", row " + std::to_string(herr[2]) + ")");
 	if (herr[0] == 3) return fail_free(NTG_E_BADARG, "per-problem grid: linear constraint rows are rank deficient (problem " + std::to_string(herr[1]) + ")");
+	if (herr[0] == 4) return fail_free(NTG_E_UNSUPPORTED, "per-problem grid: a linear-constraint entry outside the plan's sparsity pattern (problem " + std::to_string(herr[1]) + ", linear row " + std::to_string(herr[2]) + ", declared an inequality)");
 	// 4. the preconditioner blocks of every grid (hessian = 1).  On the device (grids.hip, grid_prec_kernel) when the equality rows that touch
 	//    a block pin whole coefficients -- null(A) is then spanned by unit vectors and W0 is the inverse of a principal submatrix of H0;
 	//    decided once per plan from the shared grid's A.  Otherwise: dense n_o x n_o algebra (Householder null space) on host threads.
@@ -1515,7 +1562,8 @@ extern "C" int ntg_plan_set_grids(ntg_plan *p, int batch, const double *d_knots,
 	hipFree(d_off); hipFree(d_err);   // (d_blk is kept: the receding-horizon shift evaluates the whole flag at a breakpoint)
 	// 5. the kernels add b * stride to the value pointers (NtgTables::pp_*)
 	p->T_shared = p->T;
-	for (void *q : {(void *)d_rowv, (void *)d_bpsc, (void *)d_csr, (void *)d_csc, (void *)d_sinv, (void *)d_q, (void *)d_n0b, (void *)d_knc, (void *)d_blk, (void *)d_k0pp, (void *)d_lfpp}) if (q) p->grid_owned.push_back(q);
+	for (void *q : {(void *)d_rowv, (void *)d_bpsc, (void *)d_csr, (void *)d_csc, (void *)d_sinv, (void *)d_q, (void *)d_n0b, (void *)d_knc, (void *)d_blk, (void *)d_k0pp, (void *)d_lfpp,
+	                (void *)d_icsr, (void *)d_icsc}) if (q) p->grid_owned.push_back(q);
 	p->d_grid_knots = d_knc;
 	NtgTables &T = p->T;
 	T.rowv = d_rowv; T.pp_rowv = row_total;
@@ -1525,6 +1573,7 @@ extern "C" int ntg_plan_set_grids(ntg_plan *p, int batch, const double *d_knots,
 	if (D.q_use) { T.q_val = d_q; T.pp_q = qn; }
 	if (with_precond) { T.n0b = d_n0b; T.pp_n0b = (long long)n0b_sz; T.n0 = nullptr; T.n0c = nullptr; }
 	if (D.nwt_on) { T.nwt_k0 = d_k0pp; T.pp_k0 = (long long)k0_sz; T.nwt_lf = d_lfpp; T.pp_lf = (long long)lf_sz; }
+	if (inz > 0) { T.icsr_val = d_icsr; T.icsc_val = d_icsc; T.pp_ilin = inz; }
 	p->grid_batch = batch;
 	return 0;
 }

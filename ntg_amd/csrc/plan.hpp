@@ -24,6 +24,7 @@ struct ntg_plan {
 	std::vector<ntg_av> icostav, tcostav, fcostav;
 	// host copies of the shared index tables (per-problem grids recompute the values behind them)
 	std::vector<int> h_chrow, h_csr_ptr, h_csr_col, h_csc_ptr, h_csc_row, h_sinv_ptr, h_sinv_col, h_erow, h_qcol;
+	std::vector<int> h_irow, h_icsr_ptr, h_icsr_col, h_icsc_ptr, h_icsc_row;   // ... and of the linear inequality rows (nI > 0)
 	std::vector<short> h_qidx;
 	std::vector<double> h_lic, h_ltc, h_lfc;    // the user's linear rows [n][nz]
 	// per-problem grids (ntg_plan_set_grids): number of problems they were set for (0: shared grid), their device arrays
@@ -81,6 +82,11 @@ struct NtgGridLin {
 };
 hipError_t ntg_launch_grid_rows(const NtgDims &D, int batch, const double *blk, const int *off, const int *plan_off, double *rowv, int *err, hipStream_t st);
 hipError_t ntg_launch_grid_lin(const NtgDims &D, int batch, const NtgGridLin &g, hipStream_t st);
+// the linear inequality rows' values on the plan's CSR / CSC patterns, every grid (grids.hip, grid_ilin_kernel); inz: entries of one problem
+struct NtgGridILin {
+	const double *blk, *linrows; const int *plan_off, *irow, *icsr_ptr, *icsr_col, *icsc_ptr, *icsc_row; double *icsr_val, *icsc_val; int *err; int inz;
+};
+hipError_t ntg_launch_grid_ilin(const NtgDims &D, int batch, const NtgGridILin &g, hipStream_t st);
 // preconditioner blocks of every grid on the device (grids.hip, grid_prec_kernel)
 struct NtgGridPrec { const double *blk, *bps; const int *plan_off, *fidx, *binfo; double *n0b; int *err; int nblk, nb, spad, n0b_sz, nrmax; };
 hipError_t ntg_launch_grid_prec(const NtgDims &D, int batch, const NtgGridPrec &g, hipStream_t st);

@@ -2200,7 +2200,9 @@ sqp_kernel(NtgDims D, NtgTables T, SmemLayout L, SolveParams sp, int batch,
 		NTG_STAMP(3);   // (variant builds: the step and its scalars -- shares the slot with the model assembly, which the QP step seldom runs)
 		__syncthreads();
 	};
-	const LinIneq lin{nI, T.irow, T.icsr_ptr, T.icsr_col, T.icsc_ptr, T.icsc_row, T.icsr_val, T.icsc_val, (double *)(smem_raw + L.tI)};
+	// (per-problem grids: this problem's values of the rows, NtgTables::pp_ilin)
+	const LinIneq lin{nI, T.irow, T.icsr_ptr, T.icsr_col, T.icsc_ptr, T.icsc_row, T.icsr_val + (size_t)b * T.pp_ilin, T.icsc_val + (size_t)b * T.pp_ilin,
+	                  (double *)(smem_raw + L.tI)};
 	int inform = 4, iter = 0, nfev = 0, npairs = 0, state = ST_INIT;
 	// ---- scope check (uniform): linear rows are equalities unless the plan declared them inequalities ----
 	{
