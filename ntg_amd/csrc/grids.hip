@@ -1,7 +1,7 @@
 // grids.hip -- per-problem grids on the device: the setup phase of ntg() (ntg.c:114-229) for every problem of a batch.
 //
 // ntg() builds its collocation per call (CollocMatrix per output, colloc.c:57-117; LinearConstraintsMatrix, constraints.c:198-261).
-// With per-problem grids the plan's combinatorial structure is shared and the VALUES are per problem (ntg_plan_set_grids, plan.cpp):
+// With per-problem grids the plan's combinatorial structure is shared and the VALUES are per problem (ntg_plan_set_grids, plan_grids.cpp):
 // basis_kernel evaluates the basis blocks of every grid; the kernels here derive everything else from them without leaving the
 // device (round 2 did this algebra on host threads: 0.2 - 1.5 s for 16 384 grids):
 //   grid_rows_kernel  channel rows rowv[chrow[r] + q P + i] = D^r B_{off+q}(bps_i) (the layout eval_kernel / sqp_kernel stage), and
@@ -248,7 +248,7 @@ hipError_t ntg_launch_grid_ilin(const NtgDims &D, int batch, const NtgGridILin &
 }
 
 // ---- preconditioner blocks of every grid (hessian = 1 on per-problem grids) ----
-// W0 = Z (Z' H0 Z)^-1 Z' per distinct block (build_precond / precond_block of plan.cpp).  When the equality rows that touch a block pin whole
+// W0 = Z (Z' H0 Z)^-1 Z' per distinct block (build_precond / precond_block of plan_build.cpp).  When the equality rows that touch a block pin whole
 // coefficients (a square invertible system: the usual end conditions), null(A) is the coordinate subspace of the free coefficients, Z can
 // be taken as their unit vectors -- an orthonormal basis like the Householder one of the host routine, and W0 with its regularisation
 // (c I in an orthonormal basis) does not depend on which -- so W0 is the inverse of the principal submatrix of H0 over the free
@@ -384,7 +384,7 @@ hipError_t ntg_launch_grid_prec(const NtgDims &D, int batch, const NtgGridPrec &
 
 
 // ---- structured Newton mode (hessian = 2 / 3) on per-problem grids: the cost model of every grid ----
-// What build_newton_tables() (plan.cpp) does once for the plan's grid, per problem: K0 = sum_i 2 w_i sum_{cost variables (o, r)} m_i m_i'
+// What build_newton_tables() (plan_build.cpp) does once for the plan's grid, per problem: K0 = sum_i 2 w_i sum_{cost variables (o, r)} m_i m_i'
 // on the compact lower band of every coupling group (free coefficients interleaved by output, p = (cl - clo) go + ov; two-sided plans:
 // the rows below the separator in the reversed array), and the band Cholesky factor (diagonal inverted: the layout nwt_solve_wave reads)
 // of every free output's block.  One workgroup per problem; an entry sums over the breakpoints in whose block both coefficients lie

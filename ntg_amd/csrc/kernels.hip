@@ -345,7 +345,7 @@ hipError_t ntg_launch_mpc_shift(const NtgDims &D, const NtgTables &T, int batch,
 }
 
 // ------------------------------------------------------------------------------------------
-// launchers (called from plan.cpp)
+// launchers (called from plan.cpp, plan_build.cpp)
 // ------------------------------------------------------------------------------------------
 static inline int align16(int x) { return (x + 15) & ~15; }
 

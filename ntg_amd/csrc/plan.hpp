@@ -26,7 +26,7 @@ struct ntg_plan {
 	std::vector<int> h_chrow, h_csr_ptr, h_csr_col, h_csc_ptr, h_csc_row, h_sinv_ptr, h_sinv_col, h_erow, h_qcol;
 	std::vector<int> h_irow, h_icsr_ptr, h_icsr_col, h_icsc_ptr, h_icsc_row;   // ... and of the linear inequality rows (nI > 0)
 	std::vector<short> h_qidx;
-	std::vector<double> h_lic, h_ltc, h_lfc;    // the user's linear rows [n][nz]
+	std::vector<double> h_linrows;              // the user's linear rows, stacked [nlic | nltc | nlfc][nz]
 	// per-problem grids (ntg_plan_set_grids): number of problems they were set for (0: shared grid), their device arrays
 	int grid_batch = 0;
 	std::vector<void *> grid_owned;

@@ -1,0 +1,112 @@
+// plan_priv.hpp -- what the host translation units behind include/ntg_amd.h share and nobody else sees: error reporting, the owner
+// of device allocations, the small algebra used by more than one of them, and the functions one unit offers the others.
+//   plan.cpp        entry points of the batched calls, the solve setup (which kernel, which layout, which part of the workspace)
+//   plan_build.cpp  ntg_plan_create: spec validation, basis classes, channel tables, linear rows; the structured-Newton tables; the
+//                   preconditioner; plan queries
+//   plan_grids.cpp  per-problem grids (ntg_plan_set_grids) and per-problem family parameters
+#pragma once
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <type_traits>
+#include <vector>
+#include "ntg_dev.hpp"
+#include "plan.hpp"
+
+static inline int fail(int code, const std::string &msg) { return ntg_fail(code, msg); }
+#define HIPCHK(x)                                                                                 \
+	do {                                                                                          \
+		hipError_t e_ = (x);                                                                      \
+		if (e_ != hipSuccess) return fail(NTG_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
+	} while (0)
+
+// Owner of device allocations: what it allocated is freed when it goes out of scope, unless handed over (to the plan's list) first.
+// A function allocates through one of these, returns on any failure, and hands over on success.
+class DevOwner {
+	std::vector<void *> ptrs_;
+public:
+	DevOwner() = default;
+	DevOwner(const DevOwner &) = delete;
+	DevOwner &operator=(const DevOwner &) = delete;
+	DevOwner(DevOwner &&o) noexcept : ptrs_(std::move(o.ptrs_)) { o.ptrs_.clear(); }
+	~DevOwner() { free_all(); }
+	// n elements, filled from src unless that is null; n == 0 allocates nothing and gives nullptr.  T may be const (a table's field).
+	template <class T> int upload(T **dst, const typename std::remove_const<T>::type *src, size_t n)
+	{
+		*dst = nullptr;
+		if (n == 0) return 0;
+		HIPCHK(hipMalloc((void **)dst, n * sizeof(T)));
+		ptrs_.push_back((void *)*dst);
+		if (src) HIPCHK(hipMemcpy((void *)*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+		return 0;
+	}
+	template <class T> int alloc(T **dst, size_t n) { return upload(dst, nullptr, n); }
+	void free_one(const void *q)   // a temporary that is no longer needed
+	{
+		auto it = std::find(ptrs_.begin(), ptrs_.end(), q);
+		if (it != ptrs_.end()) { (void)hipFree(*it); ptrs_.erase(it); }
+	}
+	void free_all() { for (void *q : ptrs_) (void)hipFree(q); ptrs_.clear(); }
+	void release_into(std::vector<void *> &dst) { dst.insert(dst.end(), ptrs_.begin(), ptrs_.end()); ptrs_.clear(); }   // in allocation order
+};
+
+// ---------------- small algebra with more than one user ----------------
+bool chol_lower(std::vector<double> &a, int n);                      // row-major, in place; false: not positive definite
+void chol_solve(const std::vector<double> &L, int n, double *b);
+
+// Compressed rows of a dense row-major matrix with nc columns, exact zeros dropped.  Row i is row sel[i] of A (sel null: row i).  By
+// rows (CSR: idx = column) or by columns (CSC: idx = position of the row in sel).  nnz counts the entries; an empty pattern gets one
+// dummy entry (index 0, value 0.0) behind it so that the device arrays exist.
+struct Sparse { std::vector<int> ptr, idx; std::vector<double> val; int nnz = 0; };
+Sparse dense_to_csr(const double *A, int nr, int nc, const int *sel = nullptr);
+Sparse dense_to_csc(const double *A, int nr, int nc, const int *sel = nullptr);
+
+// linear row r of the stacked rows [nlic | nltc x P | nlfc] (ntg.c:156): the user's row slot (0 .. nlic + nltc + nlfc) and its breakpoint
+struct LinRow { int slot, bp; };
+static inline LinRow lin_row(const NtgDims &D, int r)
+{
+	if (r < D.nlic) return {r, 0};
+	if (r < D.nlic + D.nltc * D.P) return {D.nlic + (r - D.nlic) / D.P, (r - D.nlic) % D.P};
+	return {D.nlic + D.nltc + (r - D.nlic - D.nltc * D.P), D.P - 1};
+}
+
+// trapezoid weight of breakpoint i
+static inline double trap_weight(const double *bps, int i, int P)
+{
+	double w = 0.0;
+	if (i > 0) w += (bps[i] - bps[i - 1]) / 2;
+	if (i < P - 1) w += (bps[i + 1] - bps[i]) / 2;
+	return w;
+}
+
+// The cost terms a Hessian model sums over: add(active variables, breakpoint, weight) for the running cost at every breakpoint
+// (scale x trapezoid weight), the initial cost and the final cost (scale), in this order.
+template <class F> static inline void for_cost_terms(const ntg_plan *p, const double *bps, double scale, F add)
+{
+	const NtgDims &D = p->D;
+	for (int i = 0; i < D.P; i++) { const double w = trap_weight(bps, i, D.P); if (D.nucf) add(p->tcostav, i, scale * w); }
+	if (D.nicf) add(p->icostav, 0, scale);
+	if (D.nfcf) add(p->fcostav, D.P - 1, scale);
+}
+
+// H0 += w m m' for derivative r of one output at one breakpoint: b = its [k][d] basis block, base = index of the block's first coefficient in H0
+static inline void h0_add(std::vector<double> &H0, int nb, int base, const double *b, int k, int d, int r, double w)
+{
+	for (int q1 = 0; q1 < k; q1++) for (int q2 = 0; q2 < k; q2++) H0[(size_t)(base + q1) * nb + base + q2] += w * b[q1 * d + r] * b[q2 * d + r];
+}
+
+// first output that uses preconditioner block q (NtgDims::n0_blk), -1: none
+static inline int block_output(const NtgDims &D, int q)
+{
+	for (int o = 0; o < D.nout; o++) if (D.n0_blk[o] == q) return o;
+	return -1;
+}
+
+// ---------------- between the units ----------------
+// W0 = Z (Z' H0 Z)^-1 Z' of one block; 0, an error code, or 1: H0 is singular on null(A)  (plan_build.cpp)
+int precond_block(const std::vector<double> &H0, const std::vector<double> &A, int m, int n, std::vector<double> &W0);
+int build_precond(ntg_plan *p);   // the caller holds ntg_plan::precond_mutex
+// per-problem family parameters (plan_grids.cpp): doubles per problem the plan's family needs; are they set, for this batch?
+int param_count(const ntg_plan *p);
+int check_params(const ntg_plan *p, int batch);

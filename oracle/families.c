@@ -266,7 +266,7 @@ static orc_problem *make_from_spec(const orc_batch_spec *s, const double *lowerb
 		s->nicostav, (orc_AV *)s->icostav, s->ntcostav, (orc_AV *)s->tcostav, s->nfcostav, (orc_AV *)s->fcostav);
 	free(lic); free(ltc); free(lfc);
 	p->nlic_hess = orc_family_nlic_hess(s->family); p->nltc_hess = orc_family_nltc_hess(s->family); p->nlfc_hess = orc_family_nlfc_hess(s->family);
-	/* the same table as build_newton_tables() of the product (ntg_amd/csrc/plan.cpp) */
+	/* the same table as nwt_shape() of the product (ntg_amd/csrc/plan_build.cpp) */
 	if (s->family == ORC_FAM_OBSTACLE) { p->couple = 2; p->group_mask = (1ull << 0) | (1ull << 3); }
 	else if (s->family == ORC_FAM_QUADROTOR) { p->couple = 4; p->group_mask = (1ull << 1) | (1ull << 2) | (1ull << 6) | (1ull << 7) | (1ull << 11) | (1ull << 12); }
 	else if (s->family == ORC_FAM_MANIP) { p->couple = 3; p->group_mask = (1ull << 0) | (1ull << 3) | (1ull << 6); }

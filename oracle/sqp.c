@@ -362,7 +362,7 @@ static void nwt_add_bp(nwt_t *w, double *Kb, int bp, const double *B)
 	}
 }
 
-/* The mode applies to the same problems as on the device (build_newton_tables() in ntg_amd/csrc/plan.cpp states the rule):
+/* The mode applies to the same problems as on the device (nwt_shape() / build_newton_tables() in ntg_amd/csrc/plan_build.cpp state the rule):
  * a family with per-group second-order blocks, one spline spec for every output, trajectory nonlinear rows only, on exactly
  * the family's flag entries, no linear inequality rows, equality rows that pin a square block of coefficients -- the same
  * range of every output -- and a band of half width k couple - 1 <= 32.  (The arithmetic below is more general -- any
