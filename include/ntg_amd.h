@@ -23,6 +23,7 @@
  *                        ntg.c:274-280 / ntg.c:337-346  (static NPfunobj / NPfuncon; exported
  *                        under the names BASELINE.json uses, same Fortran-style signature)
  *   ntg_batch_interp     colloc.c:449-484 SplineInterp, for a batch
+ *   ntg_batch_check      SplineInterp + the trajectory rows of NPfuncon (constraints.c:119-160) at arbitrary times + bounds, fused
  *   ntg_batch_kincar_reverse  examples/kincar.c:68-92 kincar_flat_reverse (the example's flat-to-state map), for a batch
  *   ntg(), npsoloption(), linspace(), SplineInterp(), matrix helpers: see include/ntg.h
  */
@@ -222,6 +223,30 @@ int ntg_batch_interp(const ntg_plan *p, int batch, const double *d_x, int ntimes
  * times_stride = 0 on the plan's grid and = ntimes after ntg_plan_set_grids(). */
 int ntg_batch_interp_strided(const ntg_plan *p, int batch, const double *d_x, int ntimes, const double *d_times,
                              long long times_stride, double *d_z, void *stream);
+
+/* Check solved trajectories BETWEEN the breakpoints.  The solvers enforce the trajectory rows at the collocation breakpoints only; this
+ * call evaluates them at any times, fused on the device: for every problem b and every time t of its time vector the flat flag z(t) of
+ * d_x[b] (SplineInterp's arithmetic, colloc.c:476-481), the nltc linear trajectory rows ltc . z, the nnltc nonlinear trajectory rows
+ * (the family's row functions, with the problem's parameter row), each compared with that row function's bounds in d_lower / d_upper
+ * ([batch][nbounds], the order lic, ltc, lfc, nlic, nltc, nlfc of ntg_batch_bounds; a bound with |.| >= NTG_INF_BOUND is absent).  The
+ * violation of a row at a time is max(l - c, c - u, 0).  No flag is written to memory.
+ * Outputs (any may be NULL, not all three):
+ *   d_viol  [batch]     the largest violation over all rows and times, 0 if there is none
+ *   d_where [batch][2]  {row, time index} of that maximum: row in [0, nltc + nnltc), linear rows first; on equal violations the smallest
+ *                       row * ntimes + time index; {-1, -1} where d_viol is 0
+ *   d_rows  [batch][nltc + nnltc][ntimes]  every row value
+ * d_times / times_stride as for ntg_batch_interp_strided: 0 = one [ntimes] vector for the batch (with or without per-problem grids),
+ * >= ntimes = per-problem times (only with per-problem grids; the basis then comes from that problem's knots).  Times must lie inside
+ * the knot range.  The breakpoint index a family callback receives is that of the last breakpoint (the plan's, or the problem's own) at
+ * or before t; the built-in families ignore it.  Results are bit-identical from call to call and do not depend on the batch around a
+ * problem.  Scratch is stream ordered and does not grow with batch * ntimes * nz (per-problem grids: the batch goes through in chunks).
+ * NTG_E_UNSUPPORTED for host-callback plans, for module families with per-breakpoint parameters (NPARAM_BP > 0: their data exists
+ * at breakpoints only), for a plan whose basis tables of one tile of 128 times exceed the LDS (sum over basis classes of order x
+ * maxderiv above about 150) and for a plan shape the family has no check instance for (none among the plans ntg_plan_create accepts); NTG_E_BADARG for a plan without trajectory rows, parameters not set, a batch other than the grids' or the
+ * parameters', a bad times_stride.  batch <= 0 or ntimes <= 0 returns 0. */
+int ntg_batch_check(const ntg_plan *p, int batch, const double *d_x, const double *d_lower, const double *d_upper,
+                    int ntimes, const double *d_times, long long times_stride,
+                    double *d_viol, int *d_where, double *d_rows, void *stream);
 
 /* The flat-to-state map of the kinematic car for a whole ntg_batch_interp result (examples/kincar.c:68-92 kincar_flat_reverse,
  * called per sample by the example's output loop, kincar.c:392-406): d_z [batch][ntimes][nz] -> d_state [batch][ntimes][ncars][5] =

@@ -75,6 +75,8 @@ def lib():
         L.ntg_batch_mpc_shift_multipliers.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
         L.ntg_batch_interp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_batch_interp_strided.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
+        L.ntg_batch_check.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_plan_set_grids.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ntg_plan_clear_grids.argtypes = [C.c_void_p]
         L.ntg_plan_param_count.argtypes = [C.c_void_p, ip]
@@ -257,6 +259,38 @@ class Plan:
         z = torch.empty((batch, ntimes, self.spec.nz), dtype=torch.float64, device=x.device)
         _check(lib().ntg_batch_interp_strided(self.h, batch, _ptr(x), ntimes, _ptr(times.contiguous()), stride, _ptr(z), self._stream()))
         return z
+
+    def _times_stride(self, batch, times):
+        """layout of a time argument: [ntimes] shared by the batch (stride 0) or, after set_grids, [batch, ntimes]"""
+        if times.dim() == 1:
+            return 0                         # one time vector for the batch (with per-problem grids: every problem on its own knots)
+        if times.dim() == 2 and self.grid_batch and times.shape[0] == batch:
+            return times.shape[1]
+        if times.dim() == 2:
+            raise NtgError("per-problem times [batch, ntimes] need per-problem grids of that batch (set_grids); pass a 1-D time vector")
+        raise NtgError("times must be [ntimes] or, after set_grids, [batch, ntimes]")
+
+    def check(self, x, lower, upper, times, want_rows: bool = False):
+        """The trajectory rows of solved problems BETWEEN the breakpoints (ntg_batch_check): x [batch, nC], bounds [batch, nbounds],
+        times [ntimes] or, after set_grids, [batch, ntimes].  Returns dict(viol [batch], where [batch, 2] = (row, time index) of the
+        largest violation or (-1, -1)[, rows [batch, nltc + nnltc, ntimes]]); linear trajectory rows come first."""
+        import torch
+        sp = self.spec
+        dev = x.device
+        _check_tensor(x, dev); _check_tensor(lower, dev); _check_tensor(upper, dev)
+        batch = x.shape[0]
+        if not (times.is_cuda and times.dtype == torch.float64):
+            raise NtgError("times must be a float64 tensor on the plan's device")
+        if lower.shape != (batch, sp.nbounds) or upper.shape != (batch, sp.nbounds):
+            raise NtgError(f"bounds must be [{batch}, {sp.nbounds}]")
+        stride = self._times_stride(batch, times)
+        ntimes = times.shape[-1]
+        out = dict(viol=torch.zeros(batch, dtype=torch.float64, device=dev), where=torch.full((batch, 2), -1, dtype=torch.int32, device=dev))
+        if want_rows:
+            out["rows"] = torch.empty((batch, sp.nltc + sp.nnltc, ntimes), dtype=torch.float64, device=dev)
+        _check(lib().ntg_batch_check(self.h, batch, _ptr(x), _ptr(lower), _ptr(upper), ntimes, _ptr(times.contiguous()), stride,
+                                     _ptr(out["viol"]), _ptr(out["where"]), _ptr(out.get("rows")), self._stream()))
+        return out
 
     def set_grids(self, knots, bps, with_precond: bool = True):
         """Per-problem grids: knots [batch, ninterv+1], bps [batch, nbps] (device, float64).  See ntg_plan_set_grids."""

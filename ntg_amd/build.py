@@ -12,7 +12,7 @@ LIB = os.path.join(HERE, "libntg_amd.so")
 SOURCES = ["kernels.hip", "grids.hip", "fam_kincar.hip", "fam_kincar_chm.hip", "fam_kincar_wave.hip", "fam_vanderpol.hip", "fam_testfam.hip", "fam_obstacle.hip", "fam_quadrotor.hip",
            "fam_manip.hip", "fam_obstacle_field.hip", "plan.cpp", "plan_build.cpp", "plan_grids.cpp", "ntg_host.cpp", "family_registry.cpp"]
 HEADERS = ["ntg_dev.hpp", "solve_impl.hpp", "newton.hpp", "qpdual.hpp", "eval_fast.hpp", "solve_wave.hpp", "families.hpp", "linesearch.hpp", "plan.hpp", "../../include/ntg_amd.h", "../../include/ntg.h",
-           "family_module.hpp", "../../include/ntg_amd_family.hpp", "obstacle_field.hpp", "plan_priv.hpp"]
+           "family_module.hpp", "../../include/ntg_amd_family.hpp", "obstacle_field.hpp", "plan_priv.hpp", "check.hpp"]
 MODULES = os.path.join(HERE, "modules")   # in-tree family modules (ntg_amd/modules/*.hip), built next to their sources
 
 
@@ -90,7 +90,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         if force or family.stale(m):
             out = family.module_path(m)
             log = open(out + ".log", "w")
-            mod_procs.append((m, out, subprocess.Popen(family.module_command(m, out), stdout=log, stderr=subprocess.STDOUT), log))
+            family.write_check_unit(m, out)
+            part1, part2, link = family.module_commands(m, out)   # the two compilations run side by side, the link follows both
+            mod_procs.append((m, out, [subprocess.Popen(c, stdout=log, stderr=subprocess.STDOUT) for c in (part1, part2)], log, link))
     for src in SOURCES:   # one hipcc per translation unit, all at once (the family units are independent)
         path = os.path.join(CSRC, src)
         obj = os.path.join(CSRC, os.path.splitext(src)[0] + ".o")
@@ -115,15 +117,18 @@ def build(force: bool = False, verbose: bool = False) -> str:
         if rc != 0:
             failed.append(src)
             sys.stderr.write(open(obj + ".log").read())
-    for m, out, pr, log in mod_procs:
-        rc = pr.wait()
+    for m, out, prs, log, link in mod_procs:
+        rc = max(abs(pr.wait()) for pr in prs)
+        if rc == 0:
+            rc = subprocess.call(link, stdout=log, stderr=subprocess.STDOUT)
         log.close()
         if rc != 0:
             failed.append(os.path.basename(m))
             sys.stderr.write(open(out + ".log").read())
+            family.remove_check_unit(m, out)
     if failed:
         raise RuntimeError("hipcc failed for " + ", ".join(failed))
-    for m, out, _, _ in mod_procs:
+    for m, out, *_ in mod_procs:
         os.remove(out + ".log")
         family.finish_module(m, out)   # call-boundary audit of the module's device code (removes the .so on a violation)
     # call boundaries of the device code (no generic pointers into the private segment, no FLAT in out-of-line functions, no dynamic

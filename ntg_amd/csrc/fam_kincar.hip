@@ -1,6 +1,7 @@
 // fam_kincar.hip -- eval_kernel / sqp_kernel instances of one problem family (own translation unit: the
 // families compile in parallel).  Tuned instances fix nout and the spline order at compile time.
 #include "solve_impl.hpp"
+#include "check.hpp"
 
 // fam_kincar_chm.hip: 2 or 6 outputs of order 6 whose cost active variables are the second derivative of every output
 hipError_t ntg_launch_eval_kincar_chm(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a);
@@ -31,4 +32,10 @@ hipError_t ntg_launch_sqp_kincar(const NtgDims &D, const NtgTables &T, const Sme
 	if (small && !a.big && D.nout == 6 && ku == 6) return launch_sqp_small<NTG_FAM_KINCAR, 6, 6>(D, T, L, sp, a);
 	if (small && !a.big && D.nout == 2 && ku == 5) return launch_sqp_small<NTG_FAM_KINCAR, 2, 5>(D, T, L, sp, a);
 	return launch_sqp_generic<NTG_FAM_KINCAR>(D, T, L, sp, a);
+}
+
+// the between-breakpoints check (check.hpp): instances by flag size
+hipError_t ntg_launch_check_kincar(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
+{
+	return launch_check<NTG_FAM_KINCAR, 6, 18, NTG_MAX_NZ>(D, T, a);
 }

@@ -1,6 +1,7 @@
 // fam_manip.hip -- eval_kernel / sqp_kernel instances of one problem family (own translation unit: the
 // families compile in parallel).  Tuned instances fix nout and the spline order at compile time.
 #include "solve_impl.hpp"
+#include "check.hpp"
 
 // config E: 12 outputs, order 6 (2196 coefficients, 301 breakpoints): 512 lanes, five coefficients per lane
 hipError_t ntg_launch_eval_manip(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
@@ -34,4 +35,10 @@ hipError_t ntg_launch_sqp_manip(const NtgDims &D, const NtgTables &T, const Smem
 	}
 	return launch_sqp_generic<NTG_FAM_MANIP>(D, T, L, sp, a);
 #endif
+}
+
+// the between-breakpoints check (check.hpp): instances by flag size
+hipError_t ntg_launch_check_manip(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
+{
+	return launch_check<NTG_FAM_MANIP, 48>(D, T, a);
 }

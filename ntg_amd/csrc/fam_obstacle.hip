@@ -1,6 +1,7 @@
 // fam_obstacle.hip -- eval_kernel / sqp_kernel instances of one problem family (own translation unit: the
 // families compile in parallel).  Tuned instances fix nout and the spline order at compile time.
 #include "solve_impl.hpp"
+#include "check.hpp"
 
 hipError_t ntg_launch_eval_obstacle(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
 {
@@ -26,4 +27,10 @@ hipError_t ntg_launch_sqp_obstacle(const NtgDims &D, const NtgTables &T, const S
 	}
 	if (small && !a.big && D.nout == 2 && ku == 6) return launch_sqp_small<NTG_FAM_OBSTACLE, 2, 6>(D, T, L, sp, a);
 	return launch_sqp_generic<NTG_FAM_OBSTACLE>(D, T, L, sp, a);
+}
+
+// the between-breakpoints check (check.hpp): the family has two outputs, a flag of 6
+hipError_t ntg_launch_check_obstacle(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
+{
+	return launch_check<NTG_FAM_OBSTACLE, 6>(D, T, a);
 }

@@ -1,6 +1,7 @@
 // fam_obstacle_field.hip -- eval_kernel / sqp_kernel instances of the obstacle-field family (per-problem obstacle centres, families.hpp,
 // obstacle_field.hpp); the same instances as fam_obstacle.hip.  Tuned instances fix nout and the spline order at compile time.
 #include "solve_impl.hpp"
+#include "check.hpp"
 
 hipError_t ntg_launch_eval_obstacle_field(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
 {
@@ -26,4 +27,10 @@ hipError_t ntg_launch_sqp_obstacle_field(const NtgDims &D, const NtgTables &T, c
 	}
 	if (small && !a.big && D.nout == 2 && ku == 6) return launch_sqp_small<NTG_FAM_OBSTACLE_FIELD, 2, 6>(D, T, L, sp, a);
 	return launch_sqp_generic<NTG_FAM_OBSTACLE_FIELD>(D, T, L, sp, a);
+}
+
+// the between-breakpoints check (check.hpp): the family has two outputs, a flag of 6
+hipError_t ntg_launch_check_obstacle_field(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
+{
+	return launch_check<NTG_FAM_OBSTACLE_FIELD, 6>(D, T, a);
 }

@@ -1,6 +1,7 @@
 // fam_quadrotor.hip -- eval_kernel / sqp_kernel instances of one problem family (own translation unit: the
 // families compile in parallel).  Tuned instances fix nout and the spline order at compile time.
 #include "solve_impl.hpp"
+#include "check.hpp"
 
 // config D: 4 outputs, order 8, maxderiv 5 (656 coefficients, 201 breakpoints): 256 lanes, three coefficients per lane
 hipError_t ntg_launch_eval_quadrotor(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
@@ -27,4 +28,10 @@ hipError_t ntg_launch_sqp_quadrotor(const NtgDims &D, const NtgTables &T, const 
 		return launch_sqp_one<NTG_FAM_QUADROTOR, 4, 8, 256, 4, false>(D, T, L, sp, a);
 	}
 	return launch_sqp_generic<NTG_FAM_QUADROTOR>(D, T, L, sp, a);
+}
+
+// the between-breakpoints check (check.hpp): instances by flag size
+hipError_t ntg_launch_check_quadrotor(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
+{
+	return launch_check<NTG_FAM_QUADROTOR, 20, NTG_MAX_NZ>(D, T, a);
 }

@@ -1,6 +1,7 @@
 // fam_vanderpol.hip -- eval_kernel / sqp_kernel instances of one problem family (own translation unit: the
 // families compile in parallel).  Tuned instances fix nout and the spline order at compile time.
 #include "solve_impl.hpp"
+#include "check.hpp"
 
 hipError_t ntg_launch_eval_vanderpol(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
 {
@@ -18,4 +19,10 @@ hipError_t ntg_launch_sqp_vanderpol(const NtgDims &D, const NtgTables &T, const 
 	(void)ku;
 	if (small && !a.big && ku == 5) return launch_sqp_small<NTG_FAM_VANDERPOL, 1, 5>(D, T, L, sp, a);
 	return launch_sqp_generic<NTG_FAM_VANDERPOL>(D, T, L, sp, a);
+}
+
+// the between-breakpoints check (check.hpp): instances by flag size
+hipError_t ntg_launch_check_vanderpol(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
+{
+	return launch_check<NTG_FAM_VANDERPOL, 3, NTG_MAX_NZ>(D, T, a);
 }

@@ -17,6 +17,7 @@
 
 typedef hipError_t (*ntg_module_eval_fn)(const NtgDims &, const NtgTables &, const SmemLayout &, const EvalArgs &);
 typedef hipError_t (*ntg_module_sqp_fn)(const NtgDims &, const NtgTables &, const SmemLayout &, const SolveParams &, const SqpArgs &);
+typedef hipError_t (*ntg_module_check_fn)(const NtgDims &, const NtgTables &, const CheckArgs &);
 
 struct ntg_family_module_desc {
 	unsigned long long abi;   // NTG_AMD_ABI the module was compiled with (first member in every version of the descriptor)
@@ -28,6 +29,8 @@ struct ntg_family_module_desc {
 	ntg_module_eval_fn launch_eval;
 	ntg_module_sqp_fn launch_sqp;
 	int nparam, nparam_bp;    // per-problem parameters: doubles per problem, doubles per breakpoint (ntg_plan_param_count)
+	int sizeof_check_args;
+	ntg_module_check_fn launch_check;   // the module's check_kernel instance (ntg_batch_check)
 };
 typedef const ntg_family_module_desc *(*ntg_family_module_entry_fn)(void);
 

@@ -69,7 +69,8 @@ extern "C" int ntg_family_load(const char *path, int *family)
 	if (d->sizeof_params != (int)sizeof(SolveParams)) return size_mismatch(rp, "SolveParams", d->sizeof_params, (int)sizeof(SolveParams));
 	if (d->sizeof_eval_args != (int)sizeof(EvalArgs)) return size_mismatch(rp, "EvalArgs", d->sizeof_eval_args, (int)sizeof(EvalArgs));
 	if (d->sizeof_sqp_args != (int)sizeof(SqpArgs)) return size_mismatch(rp, "SqpArgs", d->sizeof_sqp_args, (int)sizeof(SqpArgs));
-	if (!d->name || !d->launch_eval || !d->launch_sqp || d->dm < 1 || d->dm > NTG_MAX_ORDER || d->nnlic < 0 || d->nnltc < 0 || d->nnlfc < 0 ||
+	if (d->sizeof_check_args != (int)sizeof(CheckArgs)) return size_mismatch(rp, "CheckArgs", d->sizeof_check_args, (int)sizeof(CheckArgs));
+	if (!d->name || !d->launch_eval || !d->launch_sqp || !d->launch_check || d->dm < 1 || d->dm > NTG_MAX_ORDER || d->nnlic < 0 || d->nnltc < 0 || d->nnlfc < 0 ||
 	    d->nout < 0 || d->nout > NTG_MAX_OUT || d->nparam < 0 || d->nparam_bp < 0)
 		return ntg_fail(NTG_E_BADARG, "family module " + rp + ": malformed descriptor");
 	g_path[g_count] = rp;

@@ -10,6 +10,8 @@
 //                   constraints.c:88-195, colloc.c:243-316), trapezoid quadrature (integrator.c)
 //   sqp_kernel      the npsol_() call of ntg.c:250: one workgroup owns one problem for the
 //                   whole solve (feasibility, projected inverse-BFGS, line search)
+//   check_kernel    trajectory rows of solved problems between the breakpoints (check.hpp; the
+//                   last step of its reduction, check_final_kernel, is here)
 //
 // Mapping to CDNA4: one workgroup per problem; breakpoints (then coefficients) across the
 // lanes; basis tables, knots/breakpoints and the coefficient vector staged in LDS; the only
@@ -435,6 +437,9 @@ SmemLayout ntg_make_layout(const NtgDims &D, int nthreads, int nvec, int with_x,
 	hipError_t ntg_launch_sqp_##NAME(const NtgDims &, const NtgTables &, const SmemLayout &, const SolveParams &, const SqpArgs &);
 NTG_FAM_DECL(kincar) NTG_FAM_DECL(vanderpol) NTG_FAM_DECL(testfam) NTG_FAM_DECL(obstacle) NTG_FAM_DECL(quadrotor) NTG_FAM_DECL(manip) NTG_FAM_DECL(obstacle_field)
 #undef NTG_FAM_DECL
+#define NTG_FAM_DECL(NAME) hipError_t ntg_launch_check_##NAME(const NtgDims &, const NtgTables &, const CheckArgs &);
+NTG_FAM_DECL(kincar) NTG_FAM_DECL(vanderpol) NTG_FAM_DECL(testfam) NTG_FAM_DECL(obstacle) NTG_FAM_DECL(quadrotor) NTG_FAM_DECL(manip) NTG_FAM_DECL(obstacle_field)
+#undef NTG_FAM_DECL
 // any other id: a family module loaded at run time (family_registry.cpp) launches its own generic instances
 
 hipError_t ntg_launch_eval(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
@@ -467,6 +472,43 @@ hipError_t ntg_launch_sqp(const NtgDims &D, const NtgTables &T, const SmemLayout
 		if (const ntg_family_module_desc *m = ntg_family_module(D.family)) return m->launch_sqp(D, T, L, sp, a);
 	}
 	return hipErrorInvalidValue;
+}
+
+hipError_t ntg_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
+{
+	switch (D.family) {
+	case NTG_FAM_KINCAR: return ntg_launch_check_kincar(D, T, a);
+	case NTG_FAM_VANDERPOL: return ntg_launch_check_vanderpol(D, T, a);
+	case NTG_FAM_TESTFAM: return ntg_launch_check_testfam(D, T, a);
+	case NTG_FAM_OBSTACLE: return ntg_launch_check_obstacle(D, T, a);
+	case NTG_FAM_QUADROTOR: return ntg_launch_check_quadrotor(D, T, a);
+	case NTG_FAM_MANIP: return ntg_launch_check_manip(D, T, a);
+	case NTG_FAM_OBSTACLE_FIELD: return ntg_launch_check_obstacle_field(D, T, a);
+	default:
+		if (const ntg_family_module_desc *m = ntg_family_module(D.family)) return m->launch_check(D, T, a);
+	}
+	return hipErrorInvalidValue;
+}
+
+// ntg_batch_check, last step: the maximum over a problem's time tiles (check_kernel left one (violation, key) pair per tile; key = row *
+// ntimes + time index, -1: none).  Equal violations: the smaller key.  One thread per problem, tiles in order.
+__global__ void check_final_kernel(int batch, int ntiles, int ntimes, const double *__restrict__ pviol, const long long *__restrict__ pkey,
+                                   double *__restrict__ viol, int *__restrict__ where)
+{
+	const int b = blockIdx.x * blockDim.x + threadIdx.x;
+	if (b >= batch) return;
+	double bv = 0.0; long long bk = -1;
+	for (int i = 0; i < ntiles; i++) {
+		const double v = pviol[(size_t)b * ntiles + i]; const long long k = pkey[(size_t)b * ntiles + i];
+		if (v > bv || (v == bv && k >= 0 && (bk < 0 || k < bk))) { bv = v; bk = k; }
+	}
+	if (viol) viol[b] = bv;
+	if (where) { where[2 * b] = bk < 0 ? -1 : (int)(bk / ntimes); where[2 * b + 1] = bk < 0 ? -1 : (int)(bk % ntimes); }
+}
+hipError_t ntg_launch_check_final(int batch, int ntiles, int ntimes, const double *pviol, const long long *pkey, double *viol, int *where, hipStream_t st)
+{
+	hipLaunchKernelGGL(check_final_kernel, dim3((batch + 127) / 128), dim3(128), 0, st, batch, ntiles, ntimes, pviol, pkey, viol, where);
+	return hipGetLastError();
 }
 
 hipError_t ntg_launch_basis(int ngrids, int l, int k, int m, int d, int P, const double *knots, const double *bps,

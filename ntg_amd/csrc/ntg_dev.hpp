@@ -153,4 +153,27 @@ struct SqpArgs {
 	int nt, big, batch; const double *lo, *up; double *x, *obj; int *inf, *it, *nf; double *cl, *hist, *alw, *vecw, *nwtw; hipStream_t st;
 	unsigned int *counter;   // problem queue of the wave kernel (4 bytes inside the workspace)
 };
+// check_kernel (check.hpp): problems [b0, b0 + nb) of the batch at ntimes times each.  tblk / toff: basis_kernel's output at the times,
+// [class][t][q][r] from gbase[c] and [class][t] on the shared grid (pp = 0), [nb][t][q][r] (pp_tab doubles per problem) and [nb][t] on
+// per-problem grids (pp = 1).  lbase[c]: first row of class c in the LDS table, sumkd its rows.  rows / lo, up / pviol, pkey may be null:
+// row values [batch][nltc + nnltc][ntimes]; bounds [batch][nbounds]; per-tile maxima [batch][ntiles] (violation, row * ntimes + time or -1).
+#define NTG_CHECK_NT 128          // lanes of a check_kernel workgroup = times of one tile (host: ntiles and the per-tile pairs' indexing)
+#define NTG_CHECK_LDS_STATIC 64   // upper bound of check_kernel's static LDS (the waves' reduction slots, a family's parameter slot)
+struct CheckArgs {
+	int b0, nb, ntimes, pp, ntiles, ngroups, sumkd;
+	int gbase[NTG_MAX_OUT], lbase[NTG_MAX_OUT];
+	long long pp_tab, times_stride;
+	const double *x, *lo, *up, *times, *tblk, *ltc; const int *toff;
+	double *rows, *pviol; long long *pkey;
+	hipStream_t st;
+};
+// dynamic LDS of check_kernel for a plan: the tile's basis table [sum_c k_c d_c][NT + 1], the coefficient row, the offsets [nclass][NT]
+static inline size_t ntg_check_lds(const NtgDims &D)
+{
+	size_t sumkd = 0;
+	for (int c = 0; c < D.nclass; c++) sumkd += (size_t)D.cls_k[c] * D.cls_d[c];
+	return (sumkd * (NTG_CHECK_NT + 1) + ((D.nC + 1) & ~1)) * 8 + (size_t)D.nclass * NTG_CHECK_NT * 4;
+}
+// ... and what a workgroup may ask for: 160 KiB less the static part
+#define NTG_CHECK_LDS_MAX (160 * 1024 - NTG_CHECK_LDS_STATIC)
 

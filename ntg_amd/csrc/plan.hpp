@@ -32,6 +32,7 @@ struct ntg_plan {
 	std::vector<void *> grid_owned;
 	NtgTables T_shared;                         // the tables of the shared grid, restored by ntg_plan_clear_grids
 	double *d_lic = nullptr;                    // [nlic][nz] kept for the receding-horizon shift
+	double *d_ltc = nullptr;                    // [nltc][nz] kept for ntg_batch_check
 	// per-problem grids on the device (grids.hip): the user's linear rows stacked [nclin][nz], row -> coefficient map and padding mask of
 	// the projector's ELL pattern, the plan's block offsets; the plan's own projector values (host) to tell padding from pattern
 	double *d_linrows = nullptr; int *d_qrow2coef = nullptr, *d_planoff = nullptr, *d_erow = nullptr; unsigned char *d_qpad = nullptr;
@@ -61,6 +62,9 @@ hipError_t ntg_launch_basis(int ngrids, int l, int k, int m, int d, int P, const
                             long long knots_stride, long long bps_stride, double *blk, int *off, hipStream_t st);
 hipError_t ntg_launch_interp(const NtgDims &D, int batch, int ntimes, const double *x, const double *tblk, const int *toff,
                              const int *tblk_base, double *z, hipStream_t st, int pp = 0);
+// trajectory rows at arbitrary times (check.hpp): the family's check_kernel instance, then the maximum over a problem's time tiles
+hipError_t ntg_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a);
+hipError_t ntg_launch_check_final(int batch, int ntiles, int ntimes, const double *pviol, const long long *pkey, double *viol, int *where, hipStream_t st);
 hipError_t ntg_launch_kincar_reverse(long long nsamp, int nz, int ncars, double wheelbase, int reverse_gear, const double *z, double *out, hipStream_t st);
 hipError_t ntg_launch_count_notconv(int batch, const int *inform, int *count, hipStream_t st);
 hipError_t ntg_launch_linrows(const NtgDims &D, const NtgTables &T, const double *lic, const double *ltc,

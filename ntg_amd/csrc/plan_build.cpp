@@ -431,6 +431,7 @@ extern "C" int ntg_plan_create(const ntg_spec *s, int device, ntg_plan **out)
 	else p->lin_ok = true;
 	const int nz = p->D.nz;
 	if (s->nlic > 0 && own.upload(&p->d_lic, s->lic, (size_t)s->nlic * nz)) return NTG_E_HIP;   // kept for the receding-horizon shift
+	if (s->nltc > 0 && own.upload(&p->d_ltc, s->ltc, (size_t)s->nltc * nz)) return NTG_E_HIP;   // kept for ntg_batch_check
 	p->h_linrows.assign((size_t)(s->nlic + s->nltc + s->nlfc) * nz, 0.0);   // the user's rows, stacked [nlic | nltc | nlfc][nz]
 	if (s->nlic > 0) std::copy(s->lic, s->lic + (size_t)s->nlic * nz, p->h_linrows.begin());
 	if (s->nltc > 0) std::copy(s->ltc, s->ltc + (size_t)s->nltc * nz, p->h_linrows.begin() + (size_t)s->nlic * nz);
