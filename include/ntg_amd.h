@@ -24,6 +24,8 @@
  *                        under the names BASELINE.json uses, same Fortran-style signature)
  *   ntg_batch_interp     colloc.c:449-484 SplineInterp, for a batch
  *   ntg_batch_check      SplineInterp + the trajectory rows of NPfuncon (constraints.c:119-160) at arbitrary times + bounds, fused
+ *   ntg_batch_refine     nothing in the reference carries a spline to other knots; the nearest is SplineInterp (colloc.c:449-484), which the
+ *                        result reproduces: the refined coefficients describe the same function
  *   ntg_batch_kincar_reverse  examples/kincar.c:68-92 kincar_flat_reverse (the example's flat-to-state map), for a batch
  *   ntg(), npsoloption(), linspace(), SplineInterp(), matrix helpers: see include/ntg.h
  */
@@ -247,6 +249,27 @@ int ntg_batch_interp_strided(const ntg_plan *p, int batch, const double *d_x, in
 int ntg_batch_check(const ntg_plan *p, int batch, const double *d_x, const double *d_lower, const double *d_upper,
                     int ntimes, const double *d_times, long long times_stride,
                     double *d_viol, int *d_where, double *d_rows, void *stream);
+
+/* Carry spline coefficients to a finer knot grid, exactly: d_x_from [batch][nC(from)] -> d_x_to [batch][nC(to)] (device pointers on the
+ * plans' common device; they must not overlap).  For every problem and output, d_x_to holds the coefficients on `to`'s knots of the same
+ * piecewise polynomial that d_x_from describes on `from`'s knots: knot insertion (the blossom of the coarse spline at the fine knots), no
+ * fitting and no sampling -- SplineInterp (colloc.c:449-484) of d_x_to on `to` reproduces SplineInterp of d_x_from on `from`; the
+ * reference itself has no such operation.  The usual use: ntg_batch_check reports a violation between breakpoints, the caller builds a
+ * plan on more knot intervals and starts its solve from the refined solution; or a hand-made guess on a coarse grid.
+ * Only the two spline spaces matter: family, rows, cost, breakpoints, maxderiv and parameters of the two plans may differ freely.
+ * Conditions, per output (NTG_E_BADARG otherwise; the message names the output and the offending break): same nout, same device, same
+ * order; mult_to <= mult_from (a fine plan may ask for less smoothness, never more); the first and last breaks of the two plans agree and
+ * every interior break of `from` has a partner of its own among `to`'s breaks.  Two breaks are partners when they differ by at most 1e-12
+ * x the knot range (break sequences built by accumulation, like linspace() of the reference, ntg.c:374-389, are not bit-equal where they
+ * should coincide); the arithmetic uses `to`'s value for both, so the inclusion of the knot vectors is exact.  On identical spline spaces
+ * d_x_to is bit-equal to d_x_from.  Results are bit-identical from call to call and do not depend on the batch around a problem.
+ * Both plans on their own grids: checked on the host, the call is stream ordered.  Both plans with per-problem grids (ntg_plan_set_grids)
+ * for exactly `batch` problems: every problem uses its own two break sequences, the conditions are checked on the device and THE CALL
+ * WAITS FOR THE STREAM to read the result; the message names the first offending problem (its d_x_to row is not written, the rows of the
+ * problems that pass are).  NTG_E_BADARG for a batch other than the grids'.  NTG_E_UNSUPPORTED: one plan on its own grid and the other
+ * on per-problem grids; host-callback plans; a pair whose weight tables exceed 64 KiB of LDS.  batch <= 0 returns 0. */
+int ntg_batch_refine(const ntg_plan *from, const ntg_plan *to, int batch,
+                     const double *d_x_from, double *d_x_to, void *stream);
 
 /* The flat-to-state map of the kinematic car for a whole ntg_batch_interp result (examples/kincar.c:68-92 kincar_flat_reverse,
  * called per sample by the example's output loop, kincar.c:392-406): d_z [batch][ntimes][nz] -> d_state [batch][ntimes][ncars][5] =

@@ -77,6 +77,7 @@ def lib():
         L.ntg_batch_interp_strided.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
         L.ntg_batch_check.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ntg_batch_refine.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_plan_set_grids.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ntg_plan_clear_grids.argtypes = [C.c_void_p]
         L.ntg_plan_param_count.argtypes = [C.c_void_p, ip]
@@ -290,6 +291,19 @@ class Plan:
             out["rows"] = torch.empty((batch, sp.nltc + sp.nnltc, ntimes), dtype=torch.float64, device=dev)
         _check(lib().ntg_batch_check(self.h, batch, _ptr(x), _ptr(lower), _ptr(upper), ntimes, _ptr(times.contiguous()), stride,
                                      _ptr(out["viol"]), _ptr(out["where"]), _ptr(out.get("rows")), self._stream()))
+        return out
+
+    def refine(self, to: "Plan", x):
+        """The same splines on the finer knot grid of plan `to` (ntg_batch_refine): x [batch, nC] -> [batch, to.spec.nC], exact knot
+        insertion.  `to` needs the same outputs and orders, every break of this plan among its own, and no more smoothness."""
+        import torch
+        assert x.is_cuda and x.dtype == torch.float64 and x.is_contiguous()
+        _check_tensor(x, torch.device("cuda", self.device))
+        if x.dim() != 2 or x.shape[1] != self.spec.nC:
+            raise NtgError(f"x must be [batch, {self.spec.nC}]")
+        batch = x.shape[0]
+        out = torch.empty((batch, to.spec.nC), dtype=torch.float64, device=x.device)
+        _check(lib().ntg_batch_refine(self.h, to.h, batch, _ptr(x), _ptr(out), self._stream()))
         return out
 
     def set_grids(self, knots, bps, with_precond: bool = True):

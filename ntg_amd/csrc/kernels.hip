@@ -22,6 +22,7 @@
 #include <algorithm>
 #include "solve_impl.hpp"
 #include "family_module.hpp"
+#include "refine.hpp"
 
 
 // ------------------------------------------------------------------------------------------
@@ -568,6 +569,22 @@ hipError_t ntg_launch_interp(const NtgDims &D, int batch, int ntimes, const doub
 	const long long total = (long long)batch * ntimes * D.nz;
 	if (total == 0) return hipSuccess;
 	hipLaunchKernelGGL(interp_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, D, batch, ntimes, x, tblk, toff, tblk_base, z, pp);
+	return hipGetLastError();
+}
+
+// ntg_batch_refine (refine.hpp): coefficients on a finer knot grid.  pp != 0: per-problem grids.  hipErrorInvalidValue: the tables exceed the LDS.
+hipError_t ntg_launch_refine(const RefineArgs &A, int pp, int ncu, hipStream_t st)
+{
+	const size_t lds = ntg_refine_lds(A, pp);
+	if (lds > NTG_REFINE_LDS_MAX) return hipErrorInvalidValue;   // (ntg_batch_refine refuses such a pair before it gets here)
+	if (pp) {
+		const int groups = (A.batch + NTG_REFINE_NT / 64 - 1) / (NTG_REFINE_NT / 64);
+		hipLaunchKernelGGL(refine_pp_kernel<NTG_REFINE_NT>, dim3(std::min(groups, 8 * ncu)), dim3(NTG_REFINE_NT), lds, st, A);
+	} else {
+		// persistent workgroups: each builds its weights once, so each should stream several problems; no more than fill the device
+		const int grid = std::max(1, std::min((A.batch + 7) / 8, 8 * ncu));
+		hipLaunchKernelGGL(refine_shared_kernel<NTG_REFINE_NT>, dim3(grid), dim3(NTG_REFINE_NT), lds, st, A);
+	}
 	return hipGetLastError();
 }
 

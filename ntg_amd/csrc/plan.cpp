@@ -101,7 +101,7 @@ static size_t nwt_doubles(const NtgDims &D, int batch, const SolveParams &sp, in
 }
 
 
-static int plan_ncu(const ntg_plan *p)
+int plan_ncu(const ntg_plan *p)
 {
 	if (p->ncu <= 0) {
 		hipDeviceProp_t prop;

@@ -5,6 +5,7 @@
 #include <mutex>
 #include <string>
 #include "ntg_dev.hpp"
+#include "refine.hpp"
 
 struct ntg_plan {
 	int device = 0;
@@ -62,6 +63,8 @@ hipError_t ntg_launch_basis(int ngrids, int l, int k, int m, int d, int P, const
                             long long knots_stride, long long bps_stride, double *blk, int *off, hipStream_t st);
 hipError_t ntg_launch_interp(const NtgDims &D, int batch, int ntimes, const double *x, const double *tblk, const int *toff,
                              const int *tblk_base, double *z, hipStream_t st, int pp = 0);
+// coefficients on a finer knot grid (refine.hpp); pp: per-problem grids
+hipError_t ntg_launch_refine(const RefineArgs &A, int pp, int ncu, hipStream_t st);
 // trajectory rows at arbitrary times (check.hpp): the family's check_kernel instance, then the maximum over a problem's time tiles
 hipError_t ntg_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a);
 hipError_t ntg_launch_check_final(int batch, int ntiles, int ntimes, const double *pviol, const long long *pkey, double *viol, int *where, hipStream_t st);

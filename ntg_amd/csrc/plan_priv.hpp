@@ -107,6 +107,7 @@ static inline int block_output(const NtgDims &D, int q)
 // W0 = Z (Z' H0 Z)^-1 Z' of one block; 0, an error code, or 1: H0 is singular on null(A)  (plan_build.cpp)
 int precond_block(const std::vector<double> &H0, const std::vector<double> &A, int m, int n, std::vector<double> &W0);
 int build_precond(ntg_plan *p);   // the caller holds ntg_plan::precond_mutex
+int plan_ncu(const ntg_plan *p);   // compute units of the plan's device (plan.cpp)
 // per-problem family parameters (plan_grids.cpp): doubles per problem the plan's family needs; are they set, for this batch?
 int param_count(const ntg_plan *p);
 int check_params(const ntg_plan *p, int batch);
