@@ -69,6 +69,7 @@ struct FamilyDefaults {
 	static constexpr unsigned long long TCON_VARS = ~0ull;   // flag entries a trajectory row can depend on (all: not declared)
 	static constexpr bool PER_OUTPUT_COST = false;      // only the tuned built-in instances use this
 	static constexpr int COUPLE = 0, CG = 1;            // no second-order blocks (modules do not offer them)
+	static constexpr unsigned long long GROUP_VARS = 0; // flag entries of one coupling group (none: COUPLE = 0)
 	static constexpr int NPARAM = 0, NPARAM_BP = 0;     // per-problem parameters: doubles per problem, doubles per breakpoint
 	static NTG_AMD_HD int row_group(int) { return 0; }
 	static NTG_AMD_HD void icf(int nout, const double *, double &f, double *df)

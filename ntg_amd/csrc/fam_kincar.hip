@@ -7,7 +7,7 @@
 hipError_t ntg_launch_eval_kincar_chm(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a);
 hipError_t ntg_launch_sqp_kincar_chm(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const SolveParams &sp, const SqpArgs &a);
 
-hipError_t ntg_launch_eval_kincar(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
+static hipError_t fam_launch_eval(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
 {
 	const bool small = (a.nt == 128 || a.nt == 256) && ntg_all_d(D, 3);
 	const int ku = ntg_uniform_order(D, a.nt, 4);
@@ -21,7 +21,7 @@ hipError_t ntg_launch_eval_kincar(const NtgDims &D, const NtgTables &T, const Sm
 	return launch_eval_generic<NTG_FAM_KINCAR>(D, T, L, a);
 }
 
-hipError_t ntg_launch_sqp_kincar(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const SolveParams &sp, const SqpArgs &a)
+static hipError_t fam_launch_sqp(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const SolveParams &sp, const SqpArgs &a)
 {
 	const bool small = (a.nt == 128 || a.nt == 256) && ntg_all_d(D, 3);
 	const int ku = ntg_uniform_order(D, a.nt, 4);
@@ -35,7 +35,17 @@ hipError_t ntg_launch_sqp_kincar(const NtgDims &D, const NtgTables &T, const Sme
 }
 
 // the between-breakpoints check (check.hpp): instances by flag size
-hipError_t ntg_launch_check_kincar(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
+static hipError_t fam_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
 {
 	return launch_check<NTG_FAM_KINCAR, 6, 18, NTG_MAX_NZ>(D, T, a);
 }
+
+// the family on the host (family_module.hpp): its shape rule, and its descriptor from Family<>'s constants.  Host pass only: the device
+// pass would emit the constant object into the device code as well.
+#ifndef __HIP_DEVICE_COMPILE__
+static const char *shape_rule(const ntg_spec &s)
+{
+	return s.nnlic + s.nnltc * s.nbps + s.nnlfc > 0 ? "family has no nonlinear constraints" : nullptr;
+}
+extern const NtgFamily ntg_fam_kincar = ntg_builtin_family<NTG_FAM_KINCAR>("kincar", 0, shape_rule, fam_launch_eval, fam_launch_sqp, fam_launch_check, true);
+#endif

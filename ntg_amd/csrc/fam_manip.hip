@@ -4,14 +4,14 @@
 #include "check.hpp"
 
 // config E: 12 outputs, order 6 (2196 coefficients, 301 breakpoints): 512 lanes, five coefficients per lane
-hipError_t ntg_launch_eval_manip(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
+static hipError_t fam_launch_eval(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
 {
 	if (a.nt == 512 && ntg_all_d(D, 3) && D.nout == 12 && ntg_uniform_order(D, 512, 5) == 6)
 		return launch_eval_one<NTG_FAM_MANIP, 12, 6, 512, 5>(D, T, L, a);
 	return launch_eval_generic<NTG_FAM_MANIP>(D, T, L, a);
 }
 
-hipError_t ntg_launch_sqp_manip(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const SolveParams &sp, const SqpArgs &a)
+static hipError_t fam_launch_sqp(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const SolveParams &sp, const SqpArgs &a)
 {
 #ifdef NTG_SLIM   // experiments (tools/mkvariant2.sh ... -DNTG_SLIM): config E's Newton-mode instances only -- a fifth of the compile time
 	if (a.nt == 512 && a.big && sp.hessian == 3) return launch_sqp_one<NTG_FAM_MANIP, 12, 6, 512, 5, true, true, 5, true, true>(D, T, L, sp, a);
@@ -38,7 +38,17 @@ hipError_t ntg_launch_sqp_manip(const NtgDims &D, const NtgTables &T, const Smem
 }
 
 // the between-breakpoints check (check.hpp): instances by flag size
-hipError_t ntg_launch_check_manip(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
+static hipError_t fam_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
 {
 	return launch_check<NTG_FAM_MANIP, 48>(D, T, a);
 }
+
+// the family on the host (family_module.hpp): its shape rule, and its descriptor from Family<>'s constants.  Host pass only: the device
+// pass would emit the constant object into the device code as well.
+#ifndef __HIP_DEVICE_COMPILE__
+static const char *shape_rule(const ntg_spec &s)
+{
+	return s.nout % 3 || s.nnlic || s.nnlfc || s.nnltc > s.nout / 3 ? "manipulator family: 3 outputs per arm, at most one trajectory constraint per arm" : nullptr;
+}
+extern const NtgFamily ntg_fam_manip = ntg_builtin_family<NTG_FAM_MANIP>("manip", 0, shape_rule, fam_launch_eval, fam_launch_sqp, fam_launch_check);
+#endif

@@ -4,7 +4,7 @@
 #include "check.hpp"
 
 // config D: 4 outputs, order 8, maxderiv 5 (656 coefficients, 201 breakpoints): 256 lanes, three coefficients per lane
-hipError_t ntg_launch_eval_quadrotor(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
+static hipError_t fam_launch_eval(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
 {
 	if (a.nt == 256 && ntg_all_d(D, 5) && D.nout == 4 && ntg_uniform_order(D, 256, 4) == 8)
 		return launch_eval_one<NTG_FAM_QUADROTOR, 4, 8, 256, 4>(D, T, L, a);
@@ -13,7 +13,7 @@ hipError_t ntg_launch_eval_quadrotor(const NtgDims &D, const NtgTables &T, const
 	return launch_eval_generic<NTG_FAM_QUADROTOR>(D, T, L, a);
 }
 
-hipError_t ntg_launch_sqp_quadrotor(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const SolveParams &sp, const SqpArgs &a)
+static hipError_t fam_launch_sqp(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const SolveParams &sp, const SqpArgs &a)
 {
 	if (a.nt == 256 && ntg_all_d(D, 5) && D.nout == 4 && ntg_uniform_order(D, 256, 4) == 8) {
 		if (sp.hessian == 3) {   // QP-based SQP step on the band model (qpdual.hpp)
@@ -31,7 +31,18 @@ hipError_t ntg_launch_sqp_quadrotor(const NtgDims &D, const NtgTables &T, const 
 }
 
 // the between-breakpoints check (check.hpp): instances by flag size
-hipError_t ntg_launch_check_quadrotor(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
+static hipError_t fam_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
 {
 	return launch_check<NTG_FAM_QUADROTOR, 20, NTG_MAX_NZ>(D, T, a);
 }
+
+// the family on the host (family_module.hpp): its shape rule, and its descriptor from Family<>'s constants.  (x, y, z) couple through thrust and
+// speed; the yaw output appears in no row: the one family whose plans have a free output (free_outputs_ok).  Host pass only: the device
+// pass would emit the constant object into the device code as well.
+#ifndef __HIP_DEVICE_COMPILE__
+static const char *shape_rule(const ntg_spec &s)
+{
+	return s.nout != 4 || s.nnlic || s.nnlfc || s.nnltc > 2 ? "quadrotor family: 4 outputs, at most two trajectory constraints" : nullptr;
+}
+extern const NtgFamily ntg_fam_quadrotor = ntg_builtin_family<NTG_FAM_QUADROTOR>("quadrotor", 4, shape_rule, fam_launch_eval, fam_launch_sqp, fam_launch_check, false, true);
+#endif

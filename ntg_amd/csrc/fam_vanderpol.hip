@@ -3,7 +3,7 @@
 #include "solve_impl.hpp"
 #include "check.hpp"
 
-hipError_t ntg_launch_eval_vanderpol(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
+static hipError_t fam_launch_eval(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
 {
 	const bool small = (a.nt == 128 || a.nt == 256) && ntg_all_d(D, 3);
 	const int ku = ntg_uniform_order(D, a.nt, 4);
@@ -12,7 +12,7 @@ hipError_t ntg_launch_eval_vanderpol(const NtgDims &D, const NtgTables &T, const
 	return launch_eval_generic<NTG_FAM_VANDERPOL>(D, T, L, a);
 }
 
-hipError_t ntg_launch_sqp_vanderpol(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const SolveParams &sp, const SqpArgs &a)
+static hipError_t fam_launch_sqp(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const SolveParams &sp, const SqpArgs &a)
 {
 	const bool small = (a.nt == 128 || a.nt == 256) && ntg_all_d(D, 3);
 	const int ku = ntg_uniform_order(D, a.nt, 4);
@@ -22,7 +22,18 @@ hipError_t ntg_launch_sqp_vanderpol(const NtgDims &D, const NtgTables &T, const 
 }
 
 // the between-breakpoints check (check.hpp): instances by flag size
-hipError_t ntg_launch_check_vanderpol(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
+static hipError_t fam_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
 {
 	return launch_check<NTG_FAM_VANDERPOL, 3, NTG_MAX_NZ>(D, T, a);
 }
+
+// the family on the host (family_module.hpp): its shape rule, and its descriptor from Family<>'s constants.  Host pass only: the device
+// pass would emit the constant object into the device code as well.
+#ifndef __HIP_DEVICE_COMPILE__
+static const char *shape_rule(const ntg_spec &s)
+{
+	if (s.nout != 1) return "vanderpol family has one output";
+	return s.nnlic + s.nnltc * s.nbps + s.nnlfc > 0 ? "family has no nonlinear constraints" : nullptr;
+}
+extern const NtgFamily ntg_fam_vanderpol = ntg_builtin_family<NTG_FAM_VANDERPOL>("vanderpol", 1, shape_rule, fam_launch_eval, fam_launch_sqp, fam_launch_check);
+#endif

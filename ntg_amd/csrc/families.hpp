@@ -23,6 +23,7 @@
 #include "../../include/ntg_amd.h"
 #include "ntg_dev.hpp"
 #include "obstacle_field.hpp"
+#include "family_module.hpp"
 
 template <int FAM> struct Family;
 
@@ -136,6 +137,7 @@ template <> struct Family<NTG_FAM_KINCAR> {
 	static constexpr u64 TCON_VARS = ~0ull;   // flag entries a trajectory constraint row can depend on (all: not declared)
 	static constexpr bool PER_OUTPUT_COST = true;   // ucf(nout, ...) is a sum of identical terms over the outputs: a subset of the outputs gives its share
 	static constexpr int COUPLE = 0, CG = 1;   // no structured Newton mode
+	static constexpr u64 GROUP_VARS = 0;
 	template <int NZMAX> static __device__ __forceinline__ void nltc_block(int, int, const double *, const double *, double, bool, double *) {}
 	static constexpr int NNLIC = 0, NNLTC = 0, NNLFC = 0;
 	static __device__ __forceinline__ void ucf(int nout, int, const double *z, double &f, double *df)
@@ -162,6 +164,7 @@ template <> struct Family<NTG_FAM_VANDERPOL> {
 	static constexpr u64 TCON_VARS = ~0ull;   // flag entries a trajectory constraint row can depend on (all: not declared)
 	static constexpr bool PER_OUTPUT_COST = false;
 	static constexpr int COUPLE = 0, CG = 1;   // no structured Newton mode
+	static constexpr u64 GROUP_VARS = 0;
 	template <int NZMAX> static __device__ __forceinline__ void nltc_block(int, int, const double *, const double *, double, bool, double *) {}
 	static constexpr int NNLIC = 0, NNLTC = 0, NNLFC = 0;
 	static __device__ __forceinline__ void ucf(int, int, const double *zz, double &f, double *df)
@@ -189,6 +192,7 @@ template <> struct Family<NTG_FAM_TESTFAM> {
 	static constexpr u64 TCON_VARS = ~0ull;   // flag entries a trajectory constraint row can depend on (all: not declared)
 	static constexpr bool PER_OUTPUT_COST = false;
 	static constexpr int COUPLE = 0, CG = 1;   // no structured Newton mode
+	static constexpr u64 GROUP_VARS = 0;
 	template <int NZMAX> static __device__ __forceinline__ void nltc_block(int, int, const double *, const double *, double, bool, double *) {}
 	static constexpr int NNLIC = 1, NNLTC = 2, NNLFC = 1;
 	static __device__ __forceinline__ void icf(int nout, const double *z, double &f, double *df)
@@ -256,6 +260,7 @@ template <> struct Family<NTG_FAM_OBSTACLE> {
 	static constexpr u64 TCON_VARS = ~0ull;   // flag entries a trajectory constraint row can depend on (all: not declared)
 	static constexpr bool PER_OUTPUT_COST = false;
 	static constexpr int COUPLE = 2, CG = 2;   // one group (x, y); constraint flag entries x, y
+	static constexpr u64 GROUP_VARS = (1ull << 0) | (1ull << 3);   // ... as a mask over the group's flag entries (the plan's tcav must be exactly these)
 	// B (CG x CG) = mu a a' [row active] + t d2c/dz2 [curv]: the second-order model of the row's augmented-Lagrangian term
 	template <int NZMAX> static __device__ __forceinline__ void nltc_block(int, int, const double *z, const double *t, double mu, bool curv, double *B)
 	{
@@ -286,6 +291,8 @@ template <> struct Family<NTG_FAM_QUADROTOR> {
 	static constexpr u64 TCON_VARS = (1ull << 1) | (1ull << 2) | (1ull << 6) | (1ull << 7) | (1ull << 11) | (1ull << 12);
 	static constexpr bool PER_OUTPUT_COST = false;
 	static constexpr int COUPLE = 3, CG = 6;   // one group (x, y, z), yaw is a free output; constraint flag entries in flag order: x', x'', y', y'', z', z''
+	static constexpr u64 GROUP_VARS = (1ull << 1) | (1ull << 2) | (1ull << 6) | (1ull << 7) | (1ull << 11) | (1ull << 12);
+	static_assert(GROUP_VARS == TCON_VARS, "one coupling group: its flag entries are all a trajectory row can depend on");
 	template <int NZMAX> static __device__ __forceinline__ void nltc_block(int, int, const double *z, const double *t, double mu, bool curv, double *B)
 	{
 		const double a0[6] = {0.0, 2.0 * z[2], 0.0, 2.0 * z[7], 0.0, 2.0 * (z[12] + G)};   // thrust^2
@@ -344,6 +351,7 @@ template <> struct Family<NTG_FAM_MANIP> {
 	static constexpr int MAXARMS = NTG_MAX_OUT / 3, TAPE = 3 * (NTG_MAX_OUT / 3);
 	static constexpr u64 TCON_VARS = ntg_manip_vars(NTG_MAX_OUT / 3);   // the three joint angles of every arm (flag entries 9 j, 9 j + 3, 9 j + 6)
 	static constexpr int COUPLE = 3, CG = 3;   // one group per arm; constraint flag entries qa, qb, qc
+	static constexpr u64 GROUP_VARS = ntg_manip_vars(1);   // ... of ONE arm (TCON_VARS: of every arm)
 	template <int NZMAX> static __device__ __forceinline__ void nltc_block(int, int g, const double *z, const double *t, double mu, bool curv, double *B)
 	{
 		const double a1 = z[9 * g], a2 = a1 + z[9 * g + 3], a3 = a2 + z[9 * g + 6];
@@ -413,6 +421,7 @@ template <> struct Family<NTG_FAM_OBSTACLE_FIELD> {
 	static constexpr u64 TCON_VARS = ~0ull;   // flag entries a trajectory constraint row can depend on (all: not declared)
 	static constexpr bool PER_OUTPUT_COST = false;
 	static constexpr int COUPLE = 2, CG = 2;   // one group (x, y); constraint flag entries x, y
+	static constexpr u64 GROUP_VARS = (1ull << 0) | (1ull << 3);   // ... as a mask over the group's flag entries (the plan's tcav must be exactly these)
 	template <int NZMAX> static __device__ __forceinline__ void nltc_block(int, int, const double *z, const double *t, double mu, bool curv, double *B, const double *prm, int m)
 	{
 		OF::block(m, z, t, mu, curv, B, prm);
@@ -430,3 +439,16 @@ template <> struct Family<NTG_FAM_OBSTACLE_FIELD> {
 		OF::vjp(m, z, t, df, prm);
 	}
 };
+
+// The host's descriptor of a built-in family (NtgFamily, family_module.hpp) from Family<FAM>'s constants -- the host twin of
+// NTG_AMD_MODULE_MAIN_ (include/ntg_amd_family.hpp).  What the constants do not say comes from the family's fam_*.hip: its name, the
+// number of outputs a plan must have (0: any), its shape rule and launchers, and the two flags.
+template <int FAM>
+constexpr NtgFamily ntg_builtin_family(const char *name, int nout, const char *(*shape)(const ntg_spec &), ntg_module_eval_fn launch_eval, ntg_module_sqp_fn launch_sqp,
+                                       ntg_module_check_fn launch_check, bool kincar_flag = false, bool free_outputs_ok = false)
+{
+	using F = Family<FAM>;
+	static_assert((F::COUPLE > 0) == (F::GROUP_VARS != 0), "a family with second-order blocks names the flag entries of one coupling group");
+	return NtgFamily{name, F::DM, F::NNLIC, F::NNLTC, F::NNLFC, nout, F::COUPLE, F::CG, F::GROUP_VARS, free_outputs_ok,
+	                 FamPrmCounts<F>::n, FamPrmCounts<F>::bp, FamPrmRow<F>::value, kincar_flag, shape, launch_eval, launch_sqp, launch_check};
+}

@@ -1,5 +1,6 @@
-// family_module.hpp -- the descriptor a loadable family module exports (include/ntg_amd_family.hpp fills it in, family_registry.cpp
-// checks it and kernels.hip dispatches through it).  Kept out of include/ntg_amd.h: that header declares plain C functions only.
+// family_module.hpp -- what the host knows about a problem family: NtgFamily, the descriptor every reader on the host gets from
+// ntg_family(id), and ntg_family_module_desc, the descriptor a loadable family module exports (include/ntg_amd_family.hpp fills it in,
+// family_registry.cpp checks it and wraps it into an NtgFamily).  Kept out of include/ntg_amd.h: that header declares plain C functions only.
 #pragma once
 #include "ntg_dev.hpp"
 
@@ -34,5 +35,27 @@ struct ntg_family_module_desc {
 };
 typedef const ntg_family_module_desc *(*ntg_family_module_entry_fn)(void);
 
-// the registry (family_registry.cpp): the descriptor of a loaded module family, nullptr for any other id
-const ntg_family_module_desc *ntg_family_module(int family);
+// One problem family as the host sees it.  A built-in family defines its descriptor in its own fam_*.hip, from Family<FAM>'s constants
+// (ntg_builtin_family, families.hpp); a loaded module's is filled from its ntg_family_module_desc at load.
+struct NtgFamily {
+	const char *name;
+	int dm;                    // maxderiv of every output
+	int nnlic, nnltc, nnlfc;   // the most nonlinear rows of each kind a plan may use
+	int nout;                  // outputs a plan must have (0: any)
+	// structured Newton / QP modes (newton.hpp): outputs per coupling group (0: the family has no second-order blocks), size of a group's
+	// block, the flag entries of ONE group its rows depend on (relative to the group's first entry), and whether outputs left over
+	// after the groups -- outputs that appear in no row -- are allowed
+	int couple, cg; u64 group_mask; bool free_outputs_ok;
+	int nparam, nparam_bp, nparam_row;   // per-problem parameters: doubles per problem, per breakpoint, per trajectory row function
+	bool kincar_flag;          // every pair of outputs is the flat flag of examples/kincar.c (ntg_batch_kincar_reverse)
+	// the family's own rule for a plan's shape: the text of the refusal, nullptr if the spec passes.  A module has none: the limits
+	// above are its rule
+	const char *(*shape)(const ntg_spec &);
+	ntg_module_eval_fn launch_eval;
+	ntg_module_sqp_fn launch_sqp;
+	ntg_module_check_fn launch_check;
+};
+
+// the registry (family_registry.cpp): ids 0 .. of the built-in families, ids >= NTG_FAM_MODULE_BASE of loaded modules; nullptr for any
+// other id (NTG_FAM_HOST included: the host-callback path is not a device family)
+const NtgFamily *ntg_family(int family);

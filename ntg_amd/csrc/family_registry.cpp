@@ -1,4 +1,6 @@
-// family_registry.cpp -- user problem families loaded at run time (ntg_family_load / ntg_family_info of include/ntg_amd.h).
+// family_registry.cpp -- the one table of problem families: the built-in ones by id, and user families loaded at run time
+// (ntg_family_load / ntg_family_info of include/ntg_amd.h).  Every reader on the host -- plan construction, the launch dispatch of
+// kernels.hip -- asks ntg_family(id) and gets the family's descriptor (NtgFamily, family_module.hpp).
 //
 // A module is a shared object built from include/ntg_amd_family.hpp (ntg_amd/family.py: build_module): the generic eval_kernel /
 // sqp_kernel instances of one family and one exported entry point that returns its descriptor (family_module.hpp).  Loading is a
@@ -18,16 +20,29 @@
 
 #define NTG_FAM_MODULE_MAX 64   // modules one process may load
 
+// the built-in families, each defined in its own fam_*.hip from Family<FAM>'s constants; indexed by family id
+extern const NtgFamily ntg_fam_kincar, ntg_fam_vanderpol, ntg_fam_testfam, ntg_fam_obstacle, ntg_fam_quadrotor, ntg_fam_manip, ntg_fam_obstacle_field;
+static const NtgFamily *const g_builtin[] = {&ntg_fam_kincar, &ntg_fam_vanderpol, &ntg_fam_testfam, &ntg_fam_obstacle, &ntg_fam_quadrotor, &ntg_fam_manip, &ntg_fam_obstacle_field};
+static_assert(NTG_FAM_KINCAR == 0 && NTG_FAM_VANDERPOL == 1 && NTG_FAM_TESTFAM == 2 && NTG_FAM_OBSTACLE == 3 && NTG_FAM_QUADROTOR == 4 && NTG_FAM_MANIP == 5 &&
+                  NTG_FAM_OBSTACLE_FIELD == 6 && sizeof(g_builtin) / sizeof(g_builtin[0]) == 7, "g_builtin is indexed by family id");
+
 static std::mutex g_mutex;   // serialises loading; lookups read the published descriptors without it
-static std::atomic<const ntg_family_module_desc *> g_desc[NTG_FAM_MODULE_MAX];
+static NtgFamily g_wrapped[NTG_FAM_MODULE_MAX];   // a loaded module's descriptor as an NtgFamily, filled once before it is published
+static std::atomic<const NtgFamily *> g_module[NTG_FAM_MODULE_MAX];
 static std::string g_path[NTG_FAM_MODULE_MAX];   // resolved path of every loaded module (guarded by g_mutex)
 static int g_count = 0;
 
-const ntg_family_module_desc *ntg_family_module(int family)
+static const NtgFamily *module_family(int family)
 {
 	const int j = family - NTG_FAM_MODULE_BASE;
 	if (j < 0 || j >= NTG_FAM_MODULE_MAX) return nullptr;
-	return g_desc[j].load(std::memory_order_acquire);
+	return g_module[j].load(std::memory_order_acquire);
+}
+
+const NtgFamily *ntg_family(int family)
+{
+	if (family >= 0 && family < (int)(sizeof(g_builtin) / sizeof(g_builtin[0]))) return g_builtin[family];
+	return module_family(family);
 }
 
 static std::string hex64(unsigned long long v)
@@ -73,15 +88,20 @@ extern "C" int ntg_family_load(const char *path, int *family)
 	if (!d->name || !d->launch_eval || !d->launch_sqp || !d->launch_check || d->dm < 1 || d->dm > NTG_MAX_ORDER || d->nnlic < 0 || d->nnltc < 0 || d->nnlfc < 0 ||
 	    d->nout < 0 || d->nout > NTG_MAX_OUT || d->nparam < 0 || d->nparam_bp < 0)
 		return ntg_fail(NTG_E_BADARG, "family module " + rp + ": malformed descriptor");
+	NtgFamily &f = g_wrapped[g_count];
+	f = NtgFamily{};   // no coupling blocks, no shape rule of its own, no kincar flag
+	f.name = d->name; f.dm = d->dm; f.nnlic = d->nnlic; f.nnltc = d->nnltc; f.nnlfc = d->nnlfc; f.nout = d->nout; f.cg = 1;
+	f.nparam = d->nparam; f.nparam_bp = d->nparam_bp;
+	f.launch_eval = d->launch_eval; f.launch_sqp = d->launch_sqp; f.launch_check = d->launch_check;
 	g_path[g_count] = rp;
-	g_desc[g_count].store(d, std::memory_order_release);
+	g_module[g_count].store(&f, std::memory_order_release);
 	*family = NTG_FAM_MODULE_BASE + g_count++;
 	return 0;
 }
 
 extern "C" int ntg_family_info(int family, char *name, int name_len, int *maxderiv, int *nnlic, int *nnltc, int *nnlfc, int *nout)
 {
-	const ntg_family_module_desc *d = ntg_family_module(family);
+	const NtgFamily *d = module_family(family);   // (built-in ids are refused: the call describes what ntg_family_load returned)
 	if (!d) return ntg_fail(NTG_E_BADARG, "not a loaded family module: " + std::to_string(family));
 	if (name && name_len > 0) { std::strncpy(name, d->name, (size_t)name_len - 1); name[name_len - 1] = '\0'; }
 	if (maxderiv) *maxderiv = d->dm;

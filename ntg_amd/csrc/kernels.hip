@@ -431,64 +431,24 @@ SmemLayout ntg_make_layout(const NtgDims &D, int nthreads, int nvec, int with_x,
 	return L;
 }
 
-// family dispatch: every family has its own translation unit (fam_*.hip) that picks between its tuned
-// (compile-time nout / order) instances and the generic one
-#define NTG_FAM_DECL(NAME)                                                                                         \
-	hipError_t ntg_launch_eval_##NAME(const NtgDims &, const NtgTables &, const SmemLayout &, const EvalArgs &);   \
-	hipError_t ntg_launch_sqp_##NAME(const NtgDims &, const NtgTables &, const SmemLayout &, const SolveParams &, const SqpArgs &);
-NTG_FAM_DECL(kincar) NTG_FAM_DECL(vanderpol) NTG_FAM_DECL(testfam) NTG_FAM_DECL(obstacle) NTG_FAM_DECL(quadrotor) NTG_FAM_DECL(manip) NTG_FAM_DECL(obstacle_field)
-#undef NTG_FAM_DECL
-#define NTG_FAM_DECL(NAME) hipError_t ntg_launch_check_##NAME(const NtgDims &, const NtgTables &, const CheckArgs &);
-NTG_FAM_DECL(kincar) NTG_FAM_DECL(vanderpol) NTG_FAM_DECL(testfam) NTG_FAM_DECL(obstacle) NTG_FAM_DECL(quadrotor) NTG_FAM_DECL(manip) NTG_FAM_DECL(obstacle_field)
-#undef NTG_FAM_DECL
-// any other id: a family module loaded at run time (family_registry.cpp) launches its own generic instances
-
+// family dispatch: every family, built in (its translation unit fam_*.hip picks between its tuned -- compile-time nout / order -- instances
+// and the generic one) or loaded from a module, launches through its descriptor (family_module.hpp, family_registry.cpp)
 hipError_t ntg_launch_eval(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
 {
-	switch (D.family) {
-	case NTG_FAM_KINCAR: return ntg_launch_eval_kincar(D, T, L, a);
-	case NTG_FAM_VANDERPOL: return ntg_launch_eval_vanderpol(D, T, L, a);
-	case NTG_FAM_TESTFAM: return ntg_launch_eval_testfam(D, T, L, a);
-	case NTG_FAM_OBSTACLE: return ntg_launch_eval_obstacle(D, T, L, a);
-	case NTG_FAM_QUADROTOR: return ntg_launch_eval_quadrotor(D, T, L, a);
-	case NTG_FAM_MANIP: return ntg_launch_eval_manip(D, T, L, a);
-	case NTG_FAM_OBSTACLE_FIELD: return ntg_launch_eval_obstacle_field(D, T, L, a);
-	default:
-		if (const ntg_family_module_desc *m = ntg_family_module(D.family)) return m->launch_eval(D, T, L, a);
-	}
-	return hipErrorInvalidValue;
+	const NtgFamily *f = ntg_family(D.family);
+	return f ? f->launch_eval(D, T, L, a) : hipErrorInvalidValue;
 }
 
 hipError_t ntg_launch_sqp(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const SolveParams &sp, const SqpArgs &a)
 {
-	switch (D.family) {
-	case NTG_FAM_KINCAR: return ntg_launch_sqp_kincar(D, T, L, sp, a);
-	case NTG_FAM_VANDERPOL: return ntg_launch_sqp_vanderpol(D, T, L, sp, a);
-	case NTG_FAM_TESTFAM: return ntg_launch_sqp_testfam(D, T, L, sp, a);
-	case NTG_FAM_OBSTACLE: return ntg_launch_sqp_obstacle(D, T, L, sp, a);
-	case NTG_FAM_QUADROTOR: return ntg_launch_sqp_quadrotor(D, T, L, sp, a);
-	case NTG_FAM_MANIP: return ntg_launch_sqp_manip(D, T, L, sp, a);
-	case NTG_FAM_OBSTACLE_FIELD: return ntg_launch_sqp_obstacle_field(D, T, L, sp, a);
-	default:
-		if (const ntg_family_module_desc *m = ntg_family_module(D.family)) return m->launch_sqp(D, T, L, sp, a);
-	}
-	return hipErrorInvalidValue;
+	const NtgFamily *f = ntg_family(D.family);
+	return f ? f->launch_sqp(D, T, L, sp, a) : hipErrorInvalidValue;
 }
 
 hipError_t ntg_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
 {
-	switch (D.family) {
-	case NTG_FAM_KINCAR: return ntg_launch_check_kincar(D, T, a);
-	case NTG_FAM_VANDERPOL: return ntg_launch_check_vanderpol(D, T, a);
-	case NTG_FAM_TESTFAM: return ntg_launch_check_testfam(D, T, a);
-	case NTG_FAM_OBSTACLE: return ntg_launch_check_obstacle(D, T, a);
-	case NTG_FAM_QUADROTOR: return ntg_launch_check_quadrotor(D, T, a);
-	case NTG_FAM_MANIP: return ntg_launch_check_manip(D, T, a);
-	case NTG_FAM_OBSTACLE_FIELD: return ntg_launch_check_obstacle_field(D, T, a);
-	default:
-		if (const ntg_family_module_desc *m = ntg_family_module(D.family)) return m->launch_check(D, T, a);
-	}
-	return hipErrorInvalidValue;
+	const NtgFamily *f = ntg_family(D.family);
+	return f ? f->launch_check(D, T, a) : hipErrorInvalidValue;
 }
 
 // ntg_batch_check, last step: the maximum over a problem's time tiles (check_kernel left one (violation, key) pair per tile; key = row *

@@ -393,8 +393,8 @@ static int batch_check(const ntg_plan *p, int batch, const double *d_x, const do
 	if (batch <= 0 || ntimes <= 0) return 0;
 	const NtgDims &D = p->D;
 	if (D.family == NTG_FAM_HOST) return fail(NTG_E_UNSUPPORTED, "host-callback plans have no device row functions to check");
-	if (const ntg_family_module_desc *m = ntg_family_module(D.family))
-		if (m->nparam_bp > 0) return fail(NTG_E_UNSUPPORTED, "the plan's family reads parameters per breakpoint: they exist at the breakpoints only, not at the times between them");
+	if (const NtgFamily *f = ntg_family(D.family))
+		if (f->nparam_bp > 0) return fail(NTG_E_UNSUPPORTED, "the plan's family reads parameters per breakpoint: they exist at the breakpoints only, not at the times between them");
 	if (D.nltc + D.nnltc == 0) return fail(NTG_E_BADARG, "no trajectory rows to check");
 	if (!d_x || !d_times) return fail(NTG_E_BADARG, "null argument");
 	if (!d_viol && !d_where && !d_rows) return fail(NTG_E_BADARG, "no output asked for: pass d_viol, d_where or d_rows");
@@ -476,7 +476,8 @@ extern "C" int ntg_batch_kincar_reverse(const ntg_plan *p, int batch, int ntimes
 	if (batch <= 0 || ntimes <= 0) return 0;
 	if (!d_z || !d_state) return fail(NTG_E_BADARG, "null argument");
 	const NtgDims &D = p->D;
-	if ((D.family != NTG_FAM_KINCAR && D.family != NTG_FAM_OBSTACLE && D.family != NTG_FAM_OBSTACLE_FIELD) || D.nout % 2 || D.nz != 3 * D.nout)
+	const NtgFamily *f = ntg_family(D.family);
+	if (!f || !f->kincar_flag || D.nout % 2 || D.nz != 3 * D.nout)
 		return fail(NTG_E_UNSUPPORTED, "kincar_flat_reverse needs a kincar-family plan (two outputs per car, three flag entries per output)");
 	if (!(wheelbase > 0.0)) return fail(NTG_E_BADARG, "wheelbase must be positive");
 	HIPCHK(hipSetDevice(p->device));

@@ -95,30 +95,21 @@ static int dims_from_spec(const ntg_spec *s, NtgDims &D)
 	D.nclin = s->nlic + s->nltc * s->nbps + s->nlfc;           // ntg.c:156
 	D.ncnln = s->nnlic + s->nnltc * s->nbps + s->nnlfc;        // ntg.c:157
 	D.nbounds = s->nlic + s->nltc + s->nlfc + s->nnlic + s->nnltc + s->nnlfc;
-	const ntg_family_module_desc *mod = ntg_family_module(s->family);   // a family loaded by ntg_family_load (nullptr: built in, or unknown)
-	if (s->family != NTG_FAM_KINCAR && s->family != NTG_FAM_VANDERPOL && s->family != NTG_FAM_TESTFAM && s->family != NTG_FAM_OBSTACLE &&
-	    s->family != NTG_FAM_QUADROTOR && s->family != NTG_FAM_MANIP && s->family != NTG_FAM_OBSTACLE_FIELD && s->family != NTG_FAM_HOST && !mod)
-		return fail(NTG_E_BADARG, "unknown problem family");
-	if (mod) {
+	const NtgFamily *fam = ntg_family(s->family);   // nullptr: the host-callback path, or unknown
+	if (!fam && s->family != NTG_FAM_HOST) return fail(NTG_E_BADARG, "unknown problem family");
+	if (fam && fam->shape) {   // built in: the family's own shape rule, with its text
 		for (int o = 0; o < s->nout; o++)
-			if (D.d[o] != mod->dm) return fail(NTG_E_UNSUPPORTED, std::string("family module ") + mod->name + ": wrong maxderiv (the family has " + std::to_string(mod->dm) + ")");
-		if (s->nnlic > mod->nnlic || s->nnltc > mod->nnltc || s->nnlfc > mod->nnlfc)
-			return fail(NTG_E_BADARG, std::string("family module ") + mod->name + " has " + std::to_string(mod->nnlic) + "/" + std::to_string(mod->nnltc) + "/" +
-			                              std::to_string(mod->nnlfc) + " nonlinear constraints (initial/trajectory/final)");
-		if (mod->nout > 0 && s->nout != mod->nout) return fail(NTG_E_BADARG, std::string("family module ") + mod->name + " has " + std::to_string(mod->nout) + " outputs");
-	} else if (s->family != NTG_FAM_HOST) {
-		const int dm = s->family == NTG_FAM_QUADROTOR ? 5 : 3;   // Family<>::DM of families.hpp
+			if (D.d[o] != fam->dm) return fail(NTG_E_UNSUPPORTED, "device family: wrong maxderiv (5 for the quadrotor family, 3 otherwise)");
+		if (const char *why = fam->shape(*s)) return fail(NTG_E_BADARG, why);
+	} else if (fam) {          // a module: the descriptor's limits
+		const std::string who = std::string("family module ") + fam->name;
 		for (int o = 0; o < s->nout; o++)
-			if (D.d[o] != dm) return fail(NTG_E_UNSUPPORTED, "device family: wrong maxderiv (5 for the quadrotor family, 3 otherwise)");
+			if (D.d[o] != fam->dm) return fail(NTG_E_UNSUPPORTED, who + ": wrong maxderiv (the family has " + std::to_string(fam->dm) + ")");
+		if (s->nnlic > fam->nnlic || s->nnltc > fam->nnltc || s->nnlfc > fam->nnlfc)
+			return fail(NTG_E_BADARG, who + " has " + std::to_string(fam->nnlic) + "/" + std::to_string(fam->nnltc) + "/" + std::to_string(fam->nnlfc) +
+			                              " nonlinear constraints (initial/trajectory/final)");
+		if (fam->nout > 0 && s->nout != fam->nout) return fail(NTG_E_BADARG, who + " has " + std::to_string(fam->nout) + " outputs");
 	}
-	if (s->family == NTG_FAM_QUADROTOR && (s->nout != 4 || s->nnlic || s->nnlfc || s->nnltc > 2)) return fail(NTG_E_BADARG, "quadrotor family: 4 outputs, at most two trajectory constraints");
-	if (s->family == NTG_FAM_MANIP && (s->nout % 3 || s->nnlic || s->nnlfc || s->nnltc > s->nout / 3)) return fail(NTG_E_BADARG, "manipulator family: 3 outputs per arm, at most one trajectory constraint per arm");
-	if (s->family == NTG_FAM_VANDERPOL && s->nout != 1) return fail(NTG_E_BADARG, "vanderpol family has one output");
-	if (s->family == NTG_FAM_TESTFAM && (s->nnlic > 1 || s->nnltc > 2 || s->nnlfc > 1)) return fail(NTG_E_BADARG, "testfam has 1/2/1 nonlinear constraints");
-	if ((s->family == NTG_FAM_KINCAR || s->family == NTG_FAM_VANDERPOL) && D.ncnln > 0) return fail(NTG_E_BADARG, "family has no nonlinear constraints");
-	if (s->family == NTG_FAM_OBSTACLE && (s->nout != 2 || s->nnlic || s->nnlfc || s->nnltc > 1)) return fail(NTG_E_BADARG, "obstacle family: 2 outputs, at most one trajectory constraint");
-	if (s->family == NTG_FAM_OBSTACLE_FIELD && (s->nout != 2 || s->nnlic || s->nnlfc || s->nnltc < 1 || s->nnltc > 8))
-		return fail(NTG_E_BADARG, "obstacle-field family: 2 outputs, 1 to 8 trajectory constraints (one per obstacle), no initial or final rows");
 
 	bool ok = true;
 	D.icost_mask = av_mask(D, s->icostav, s->nicostav, &ok);
@@ -447,7 +438,7 @@ extern "C" int ntg_plan_create(const ntg_spec *s, int device, ntg_plan **out)
 }
 
 // ---- structured Newton mode (newton.hpp): does the plan qualify, and its batch-shared tables ----
-// Qualifies when: the family offers the per-group second-order blocks (Family::COUPLE / CG of families.hpp, mirrored here), one
+// Qualifies when: the family offers the per-group second-order blocks (couple > 0 in its descriptor: Family::COUPLE / CG / GROUP_VARS), one
 // spline spec for every output, only trajectory nonlinear rows on exactly the flag entries the family's block covers, no
 // linear inequality rows, and equality rows that pin a square invertible block of coefficients (the usual initial / final
 // conditions): then null(A_E) = {pinned coefficients = 0} and the reduced Hessian is a principal submatrix of the band.
@@ -463,19 +454,15 @@ static bool nwt_shape(const ntg_plan *p, NwtShape &S)
 {
 	const NtgDims &D = p->D;
 	const int dm = D.d[0];
-	switch (D.family) {
-	case NTG_FAM_OBSTACLE:
-	case NTG_FAM_OBSTACLE_FIELD: S.go = 2; S.cg = 2; S.gmask = (1ull << 0) | (1ull << 3); break;
-	// (x, y, z) couple through thrust and speed; the yaw output appears in no row: a FREE output -- its block of the model is the cost
-	// model's, the same for every problem and every refresh, factored once here (nwt_lf) and solved by an otherwise idle wave
-	case NTG_FAM_QUADROTOR: S.go = 3; S.cg = 6; S.gmask = (1ull << 1) | (1ull << 2) | (1ull << 6) | (1ull << 7) | (1ull << 11) | (1ull << 12); break;
-	case NTG_FAM_MANIP: S.go = 3; S.cg = 3; S.gmask = (1ull << 0) | (1ull << 3) | (1ull << 6); break;
-	default: return false;
-	}
+	const NtgFamily *fam = ntg_family(D.family);
+	if (!fam || fam->couple == 0) return false;
+	S.go = fam->couple; S.cg = fam->cg; S.gmask = fam->group_mask;
 	if (!D.uniform || D.nI > 0 || D.nnlic || D.nnlfc || D.nnltc <= 0 || !p->lin_ok) return false;
-	const int go = S.go, ngrp = D.nout / go, nfo = D.nout - ngrp * go;   // coupling groups; outputs left over are free (only the quadrotor family has one)
+	// coupling groups; outputs left over appear in no row: FREE outputs -- their block of the model is the cost model's, the same for
+	// every problem and every refresh, factored once here (nwt_lf) and solved by an otherwise idle wave
+	const int go = S.go, ngrp = D.nout / go, nfo = D.nout - ngrp * go;
 	S.ngrp = ngrp; S.nfo = nfo;
-	if (ngrp < 1 || (nfo && D.family != NTG_FAM_QUADROTOR)) return false;
+	if (ngrp < 1 || (nfo && !fam->free_outputs_ok)) return false;
 	const int k = D.order[0], nco = D.ncoef[0], n = D.nC, m = D.mE;
 	if (k * go - 1 > 32 || ngrp + nfo > 8) return false;
 	u64 want = 0;

@@ -16,9 +16,8 @@
 // doubles per problem the plan's family needs, 0 for a family without
 int param_count(const ntg_plan *p)
 {
-	if (p->D.family == NTG_FAM_OBSTACLE_FIELD) return 2 * p->D.nnltc;   // (cx_j, cy_j) per trajectory row function
-	if (const ntg_family_module_desc *m = ntg_family_module(p->D.family)) return m->nparam + m->nparam_bp * p->D.P;
-	return 0;
+	const NtgFamily *f = ntg_family(p->D.family);
+	return f ? f->nparam + f->nparam_bp * p->D.P + f->nparam_row * p->D.nnltc : 0;
 }
 
 // the callbacks of eval / solve / mpc_run read problem b's parameter row: the family's parameters must be set, for this batch
