@@ -250,6 +250,37 @@ int ntg_batch_check(const ntg_plan *p, int batch, const double *d_x, const doubl
                     int ntimes, const double *d_times, long long times_stride,
                     double *d_viol, int *d_where, double *d_rows, void *stream);
 
+/* Audit a batch of points: the first-order optimality (KKT) residuals of  min F(x)  s.t.  bl <= (A x, c(x)) <= bu  at d_x with the
+ * multipliers d_clambda, whoever produced them -- ntg_batch_solve stopped by its own rule (inform 0), capped by itlim or run with
+ * fixed_iters (inform 4 by design), a receding-horizon loop, a warm re-solve, or the caller's own estimate.  It replaces what a caller of
+ * the reference does by hand with the clambda, g and cJac outputs of npsol_ (ntg.c:250-253); the reference has no such audit, and the dense
+ * Jacobian it would need is never formed here: the pass runs on the banded rows of ntg_batch_eval.
+ * d_x [batch][nC]; d_lower / d_upper [batch][nbounds] as for ntg_batch_solve; d_clambda [batch][nC + nclin + ncnln] as ntg_batch_solve
+ * writes it: lam_A = entries nC .. nC + nclin of a problem, lam_c = the ncnln entries behind them, in ntg_batch_eval's row order.  The first
+ * nC entries are NEVER READ (the coefficients are unbounded, and the diagnostic builds park counters there).  Sign convention (NPSOL's):
+ * g = A' lam_A + J' lam_c; a multiplier >= 0 belongs to an active lower bound, <= 0 to an active upper bound.  (bl, bu) is the expansion
+ * ntg_batch_bounds produces; a bound with |.| >= NTG_INF_BOUND is absent.  The values of A are the ones the solver reads: every linear
+ * row, equality or declared inequality, on the plan's grid or, after ntg_plan_set_grids, on that problem's own.  Per-problem parameters
+ * are honoured (the evaluation is ntg_batch_eval's).  Built-in families and loaded modules alike.
+ * Outputs (either may be NULL, not both):
+ *   d_r   [batch][nC]            r = g(x) - A' lam_A - J(x)' lam_c
+ *   d_res [batch][NTG_KKT_NRES]
+ *     [0] max |r|                [1] max |g|  (the usual test is res[0] / max(1, res[1]) <= tolerance)
+ *     [2] largest violation max(bl - a . x, a . x - bu, 0) of a linear row       [3] the same of a nonlinear row, c(x) for a . x; 0 if ncnln = 0
+ *     [4] complementarity with signs, the largest over all rows of  lam+ s_lo + lam- s_up  with lam+ = max(lam, 0), lam- = max(-lam, 0),
+ *         s_lo = min(max(v - bl, 0), 1), s_up = min(max(bu - v, 0), 1) for the row value v, an absent bound giving slack 1: a multiplier
+ *         on a bound that is not active counts with the slack (at most 1), one of the wrong sign at full size.  No activity tolerance.
+ *     [5] max |lam| over the nclin + ncnln rows
+ *   A NaN among the inputs of a maximum stays in it.
+ * Stream ordered.  Scratch is stream ordered, released on every path and does not grow with the batch beyond 256 MiB (the batch goes
+ * through in chunks of problems).  Results are bit-identical from call to call and do not depend on the batch around a problem.
+ * NTG_E_UNSUPPORTED for host-callback plans (ntg() returns clambda itself) and for a plan with nC above about 10000 (r and x of a problem
+ * stay in LDS); NTG_E_BADARG for null d_x, bounds or d_clambda, both outputs null, parameters not set, a batch other than the grids' or
+ * the parameters'.  batch <= 0 returns 0. */
+#define NTG_KKT_NRES 6
+int ntg_batch_kkt(const ntg_plan *p, int batch, const double *d_x, const double *d_lower, const double *d_upper,
+                  const double *d_clambda, double *d_res, double *d_r, void *stream);
+
 /* Carry spline coefficients to a finer knot grid, exactly: d_x_from [batch][nC(from)] -> d_x_to [batch][nC(to)] (device pointers on the
  * plans' common device; they must not overlap).  For every problem and output, d_x_to holds the coefficients on `to`'s knots of the same
  * piecewise polynomial that d_x_from describes on `from`'s knots: knot insertion (the blossom of the coarse spline at the fine knots), no

@@ -77,6 +77,7 @@ def lib():
         L.ntg_batch_interp_strided.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
         L.ntg_batch_check.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ntg_batch_kkt.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
         L.ntg_batch_refine.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_plan_set_grids.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ntg_plan_clear_grids.argtypes = [C.c_void_p]
@@ -291,6 +292,29 @@ class Plan:
             out["rows"] = torch.empty((batch, sp.nltc + sp.nnltc, ntimes), dtype=torch.float64, device=dev)
         _check(lib().ntg_batch_check(self.h, batch, _ptr(x), _ptr(lower), _ptr(upper), ntimes, _ptr(times.contiguous()), stride,
                                      _ptr(out["viol"]), _ptr(out["where"]), _ptr(out.get("rows")), self._stream()))
+        return out
+
+    def kkt(self, x, lower, upper, clambda, want_residual: bool = False):
+        """First-order optimality residuals of a batch of points (ntg_batch_kkt): x [batch, nC], bounds [batch, nbounds], clambda
+        [batch, nC + nclin + ncnln] as solve(want_lambda=True) returns it (its first nC entries are not read).  Returns dict(res
+        [batch, 6] = max |r|, max |g|, linear violation, nonlinear violation, signed complementarity, max |lambda|[, r [batch, nC] =
+        g - A' lam_A - J' lam_c])."""
+        import torch
+        sp = self.spec
+        dev = x.device
+        _check_tensor(x, dev); _check_tensor(lower, dev); _check_tensor(upper, dev); _check_tensor(clambda, dev)
+        batch = x.shape[0]
+        if x.dim() != 2 or x.shape[1] != sp.nC:
+            raise NtgError(f"x must be [batch, {sp.nC}]")
+        if lower.shape != (batch, sp.nbounds) or upper.shape != (batch, sp.nbounds):
+            raise NtgError(f"bounds must be [{batch}, {sp.nbounds}]")
+        if clambda.shape != (batch, sp.nC + sp.nclin + sp.ncnln):
+            raise NtgError(f"clambda must be [{batch}, {sp.nC + sp.nclin + sp.ncnln}]")
+        out = dict(res=torch.empty((batch, 6), dtype=torch.float64, device=dev))
+        if want_residual:
+            out["r"] = torch.empty((batch, sp.nC), dtype=torch.float64, device=dev)
+        _check(lib().ntg_batch_kkt(self.h, batch, _ptr(x), _ptr(lower), _ptr(upper), _ptr(clambda), _ptr(out["res"]), _ptr(out.get("r")),
+                                   self._stream()))
         return out
 
     def refine(self, to: "Plan", x):

@@ -12,6 +12,7 @@
 //                   whole solve (feasibility, projected inverse-BFGS, line search)
 //   check_kernel    trajectory rows of solved problems between the breakpoints (check.hpp; the
 //                   last step of its reduction, check_final_kernel, is here)
+//   kkt_kernel      first-order optimality residuals of a batch on the banded Jacobian (kkt.hpp)
 //
 // Mapping to CDNA4: one workgroup per problem; breakpoints (then coefficients) across the
 // lanes; basis tables, knots/breakpoints and the coefficient vector staged in LDS; the only
@@ -23,6 +24,7 @@
 #include "solve_impl.hpp"
 #include "family_module.hpp"
 #include "refine.hpp"
+#include "kkt.hpp"
 
 
 // ------------------------------------------------------------------------------------------
@@ -471,6 +473,9 @@ hipError_t ntg_launch_check_final(int batch, int ntiles, int ntimes, const doubl
 	hipLaunchKernelGGL(check_final_kernel, dim3((batch + 127) / 128), dim3(128), 0, st, batch, ntiles, ntimes, pviol, pkey, viol, where);
 	return hipGetLastError();
 }
+
+// ntg_batch_kkt (kkt.hpp): one pass for every family, built in or loaded.  hipErrorInvalidValue: one problem's vectors exceed the LDS.
+hipError_t ntg_launch_kkt(const NtgDims &D, const NtgTables &T, const KktArgs &a) { return launch_kkt(D, T, a); }
 
 hipError_t ntg_launch_basis(int ngrids, int l, int k, int m, int d, int P, const double *knots, const double *bps,
                             long long knots_stride, long long bps_stride, double *blk, int *off, hipStream_t st)

@@ -177,3 +177,18 @@ static inline size_t ntg_check_lds(const NtgDims &D)
 // ... and what a workgroup may ask for: 160 KiB less the static part
 #define NTG_CHECK_LDS_MAX (160 * 1024 - NTG_CHECK_LDS_STATIC)
 
+// kkt_kernel (kkt.hpp): problems [b0, b0 + nb) of the batch, grid persistent workgroups.  x, lam ([batch][nC + nclin + ncnln], the first nC
+// entries of a problem never read), res ([batch][NTG_KKT_NRES]) and r ([batch][nC]) are the caller's, indexed by the problem of the batch;
+// either of res, r may be null.  g, c, jband (ntg_launch_eval's output) and bl, bu (ntg_launch_bounds') are the chunk's scratch, indexed by
+// the problem within the launch.
+#define NTG_KKT_NT 256
+struct KktArgs {
+	int b0, nb, grid;
+	const double *x, *lam, *g, *c, *jband, *bl, *bu;
+	double *res, *r;
+	hipStream_t st;
+};
+// dynamic LDS of kkt_kernel for a plan: r and x, the offset table [nclass][P]; what a workgroup may ask for: 160 KiB less the static part
+// (the waves' reduction slots)
+static inline size_t ntg_kkt_lds(const NtgDims &D) { return (size_t)2 * ((D.nC + 1) & ~1) * 8 + (size_t)D.nclass * D.P * 4; }
+#define NTG_KKT_LDS_MAX (160 * 1024 - 256)

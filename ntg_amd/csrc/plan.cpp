@@ -184,6 +184,25 @@ extern "C" long long ntg_batch_workspace_bytes(const ntg_plan *p, int batch, con
 	return solve_setup(p, batch, o, true).bytes;
 }
 
+// launch shape of the evaluation of `batch` problems (ntg_batch_eval, and ntg_batch_kkt for each of its chunks)
+int eval_shape(const ntg_plan *p, int batch, EvalShape *s)
+{
+	const NtgDims &D = p->D;
+	int nt = auto_threads(D);
+	SmemLayout L = ntg_make_layout(D, nt, 0, 1);
+	if (nt == 256 && L.total > 80 * 1024) { nt = 512; L = ntg_make_layout(D, nt, 0, 1); }   // one workgroup per CU anyway: give it more waves
+	if (L.total > 160 * 1024) return fail(NTG_E_UNSUPPORTED, "problem tables exceed 160 KiB of LDS");
+	// persistent grid = what is resident at once: LDS-limited workgroups per CU, capped by the waves a
+	// CU holds (32) and by the register budget the kernel was compiled for (NTG_EVAL_WAVES per SIMD is a
+	// lower bound; 8 workgroups of 128 threads = 4 waves per SIMD is the most that can ever be resident)
+	const int ncu = plan_ncu(p);
+	const int wg_per_cu = std::max(1, std::min(std::min(8, 32 / (nt / 64)), (160 * 1024) / std::max(L.total, 1)));
+	int grid = std::min(batch, ncu * wg_per_cu);
+	if (const char *eg = getenv("NTG_AMD_EVAL_GRID")) grid = std::max(1, std::min(grid, atoi(eg)));   // experiments only
+	s->nt = nt; s->grid = grid; s->L = L;
+	return 0;
+}
+
 extern "C" int ntg_batch_bounds(const ntg_plan *p, int batch, const double *d_lower, const double *d_upper,
                                 double *d_bl, double *d_bu, void *stream)
 {
@@ -205,21 +224,12 @@ extern "C" int ntg_batch_eval(const ntg_plan *p, int batch, const double *d_x, i
 	if (int rc = check_params(p, batch)) return rc;
 	HIPCHK(hipSetDevice(p->device));
 	const NtgDims &D = p->D;
-	int nt = auto_threads(D);
-	SmemLayout L = ntg_make_layout(D, nt, 0, 1);
-	if (nt == 256 && L.total > 80 * 1024) { nt = 512; L = ntg_make_layout(D, nt, 0, 1); }   // one workgroup per CU anyway: give it more waves
-	if (L.total > 160 * 1024) return fail(NTG_E_UNSUPPORTED, "problem tables exceed 160 KiB of LDS");
+	EvalShape es;
+	if (int rc = eval_shape(p, batch, &es)) return rc;
 	hipStream_t st = (hipStream_t)stream;
 	if (d_cjac && D.ncnln) HIPCHK(hipMemsetAsync(d_cjac, 0, (size_t)batch * D.ncnln * D.nC * 8, st)); // GcJac starts zeroed (ntg.c:217)
-	// persistent grid = what is resident at once: LDS-limited workgroups per CU, capped by the waves a
-	// CU holds (32) and by the register budget the kernel was compiled for (NTG_EVAL_WAVES per SIMD is a
-	// lower bound; 8 workgroups of 128 threads = 4 waves per SIMD is the most that can ever be resident)
-	const int ncu = plan_ncu(p);
-	const int wg_per_cu = std::max(1, std::min(std::min(8, 32 / (nt / 64)), (160 * 1024) / std::max(L.total, 1)));
-	int grid = std::min(batch, ncu * wg_per_cu);
-	if (const char *eg = getenv("NTG_AMD_EVAL_GRID")) grid = std::max(1, std::min(grid, atoi(eg)));   // experiments only
-	EvalArgs ea{nt, grid, ncu, batch, mode, d_x, d_f, d_g, d_c, d_jband, d_cjac, st};
-	HIPCHK(ntg_launch_eval(D, p->T, L, ea));
+	EvalArgs ea{es.nt, es.grid, plan_ncu(p), batch, mode, d_x, d_f, d_g, d_c, d_jband, d_cjac, st};
+	HIPCHK(ntg_launch_eval(D, p->T, es.L, ea));
 	return 0;
 }
 

@@ -68,6 +68,8 @@ hipError_t ntg_launch_refine(const RefineArgs &A, int pp, int ncu, hipStream_t s
 // trajectory rows at arbitrary times (check.hpp): the family's check_kernel instance, then the maximum over a problem's time tiles
 hipError_t ntg_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a);
 hipError_t ntg_launch_check_final(int batch, int ntiles, int ntimes, const double *pviol, const long long *pkey, double *viol, int *where, hipStream_t st);
+// first-order optimality residuals (kkt.hpp): one chunk of problems, after ntg_launch_eval (mode 2) and ntg_launch_bounds filled its scratch
+hipError_t ntg_launch_kkt(const NtgDims &D, const NtgTables &T, const KktArgs &a);
 hipError_t ntg_launch_kincar_reverse(long long nsamp, int nz, int ncars, double wheelbase, int reverse_gear, const double *z, double *out, hipStream_t st);
 hipError_t ntg_launch_count_notconv(int batch, const int *inform, int *count, hipStream_t st);
 hipError_t ntg_launch_linrows(const NtgDims &D, const NtgTables &T, const double *lic, const double *ltc,

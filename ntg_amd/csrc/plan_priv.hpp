@@ -4,6 +4,7 @@
 //   plan_build.cpp  ntg_plan_create: spec validation, basis classes, channel tables, linear rows; the structured-Newton tables; the
 //                   preconditioner; plan queries
 //   plan_grids.cpp  per-problem grids (ntg_plan_set_grids) and per-problem family parameters
+//   plan_kkt.cpp    ntg_batch_kkt: first-order optimality residuals of a batch
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -111,3 +112,6 @@ int plan_ncu(const ntg_plan *p);   // compute units of the plan's device (plan.c
 // per-problem family parameters (plan_grids.cpp): doubles per problem the plan's family needs; are they set, for this batch?
 int param_count(const ntg_plan *p);
 int check_params(const ntg_plan *p, int batch);
+// launch shape of the evaluation of `batch` problems: workgroup size, persistent grid, LDS layout; 0 or an error code  (plan.cpp)
+struct EvalShape { int nt, grid; SmemLayout L; };
+int eval_shape(const ntg_plan *p, int batch, EvalShape *s);

@@ -1,4 +1,6 @@
-"""Diagnostic (not a test): KKT residuals of the structured Newton mode at BASELINE sizes.  python tools/kkt.py [D|E] [batch]"""
+"""Diagnostic (not a test): KKT residuals of the structured Newton mode at BASELINE sizes, computed on the host from the dense Jacobian
+(8 problems at a time) and, next to them, by ntg_batch_kkt on the device (Plan.kkt; tools/kkt_rate.py times the two routes).
+python tools/kkt.py [D|E] [batch]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -37,3 +39,9 @@ for hess in (2, 1):
     stat, feas, comp, lin = map(np.array, (stat, feas, comp, lin))
     print(f"{which} hessian={hess}: inform {np.bincount(inf)} stationarity max {stat.max():.2e} median {np.median(stat):.2e}; nonlinear violation max {feas.max():.2e}; "
           f"complementarity max {comp.max():.2e}; linear residual max {lin.max():.2e}; majors max {out['iters'].max().item()}")
+    # the same audit on the device: res = max |r|, max |g|, linear violation, nonlinear violation, signed complementarity, max |lambda|
+    # (violations absolute, complementarity not divided by max |lambda|: include/ntg_amd.h)
+    res = p.kkt(x, torch.tensor(lo, device=dev), torch.tensor(up, device=dev), out["clambda"])["res"].cpu().numpy()
+    dstat = res[:, 0] / np.maximum(1.0, res[:, 1])
+    print(f"{which} hessian={hess}: device  stationarity max {dstat.max():.2e} median {np.median(dstat):.2e}; nonlinear violation max {res[:, 3].max():.2e}; "
+          f"complementarity max {res[:, 4].max():.2e}; linear violation max {res[:, 2].max():.2e}; max |lambda| {res[:, 5].max():.2e}")
