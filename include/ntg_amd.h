@@ -24,6 +24,8 @@
  *                        under the names BASELINE.json uses, same Fortran-style signature)
  *   ntg_batch_interp     colloc.c:449-484 SplineInterp, for a batch
  *   ntg_batch_check      SplineInterp + the trajectory rows of NPfuncon (constraints.c:119-160) at arbitrary times + bounds, fused
+ *   ntg_batch_cost       SplineInterp + the integrand of IntegratedCost (cost.c with integrator.c, reached through NPfunobj, ntg.c:274-280) at
+ *                        arbitrary nodes under the caller's quadrature weights, fused; the reference integrates by the trapezoid rule on the breakpoints only
  *   ntg_batch_refine     nothing in the reference carries a spline to other knots; the nearest is SplineInterp (colloc.c:449-484), which the
  *                        result reproduces: the refined coefficients describe the same function
  *   ntg_batch_kincar_reverse  examples/kincar.c:68-92 kincar_flat_reverse (the example's flat-to-state map), for a batch
@@ -249,6 +251,32 @@ int ntg_batch_interp_strided(const ntg_plan *p, int batch, const double *d_x, in
 int ntg_batch_check(const ntg_plan *p, int batch, const double *d_x, const double *d_lower, const double *d_upper,
                     int ntimes, const double *d_times, long long times_stride,
                     double *d_viol, int *d_where, double *d_rows, void *stream);
+
+/* Audit the running cost BETWEEN the breakpoints.  The solvers minimise the trapezoid sum of the running cost on the collocation
+ * breakpoints (IntegratedCost, cost.c with integrator.c); this call evaluates the same integrand at any times and sums it under any
+ * quadrature, fused on the device: for every problem b and every time t_i of its time vector the flat flag z(t_i) of d_x[b] (SplineInterp's
+ * arithmetic, colloc.c:476-481, exactly as ntg_batch_check computes it) and the family's running cost L_i = ucf(z(t_i)), with the problem's
+ * parameter row.  No flag and no gradient is written to memory.
+ * Outputs (either may be NULL, not both):
+ *   d_cost [batch]          sum_i w_i L_i
+ *   d_vals [batch][ntimes]  the unweighted L_i; d_vals[b][i] does not depend on ntimes or on the other times
+ * The initial and final cost functions are NOT part of the result: f of ntg_batch_eval minus d_cost at the plan's own trapezoid nodes and
+ * weights is what they contribute.
+ * d_times and d_weights share one layout, stated by times_stride as for ntg_batch_check: 0 = one [ntimes] vector pair for the batch (with
+ * or without per-problem grids), >= ntimes = per-problem vectors (only with per-problem grids; the basis then comes from that problem's
+ * knots).  d_weights may be NULL only if d_cost is NULL.  Times must lie inside the knot range.  The breakpoint index the callback
+ * receives is that of the last breakpoint (the plan's, or the problem's own) at or before t_i; the built-in families ignore it.
+ * The sum has a fixed order: within a tile of 128 times the lanes' terms w_i L_i, a fixed butterfly over the 64 lanes of a wave, the waves
+ * in index order; then the tiles of a problem in tile order.  No floating-point atomics: results are bit-identical from call to call and
+ * do not depend on the batch around a problem.  Scratch is stream ordered, released on every path and does not grow with batch * ntimes
+ * * nz (per-problem grids: the batch goes through in chunks).
+ * NTG_E_UNSUPPORTED for host-callback plans, for module families with per-breakpoint parameters (NPARAM_BP > 0: their data exists at
+ * breakpoints only) and for a plan whose basis tables of one tile of 128 times exceed the LDS (ntg_batch_check's limit); NTG_E_BADARG for
+ * a plan without a running cost (nucf == 0), null d_x or d_times, both outputs null, d_cost without d_weights, parameters not set, a batch
+ * other than the grids' or the parameters', a bad times_stride.  batch <= 0 or ntimes <= 0 returns 0. */
+int ntg_batch_cost(const ntg_plan *p, int batch, const double *d_x,
+                   int ntimes, const double *d_times, const double *d_weights, long long times_stride,
+                   double *d_cost, double *d_vals, void *stream);
 
 /* Audit a batch of points: the first-order optimality (KKT) residuals of  min F(x)  s.t.  bl <= (A x, c(x)) <= bu  at d_x with the
  * multipliers d_clambda, whoever produced them -- ntg_batch_solve stopped by its own rule (inform 0), capped by itlim or run with

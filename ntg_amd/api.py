@@ -78,6 +78,7 @@ def lib():
         L.ntg_batch_check.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_batch_kkt.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        L.ntg_batch_cost.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_batch_refine.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_plan_set_grids.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ntg_plan_clear_grids.argtypes = [C.c_void_p]
@@ -292,6 +293,35 @@ class Plan:
             out["rows"] = torch.empty((batch, sp.nltc + sp.nnltc, ntimes), dtype=torch.float64, device=dev)
         _check(lib().ntg_batch_check(self.h, batch, _ptr(x), _ptr(lower), _ptr(upper), ntimes, _ptr(times.contiguous()), stride,
                                      _ptr(out["viol"]), _ptr(out["where"]), _ptr(out.get("rows")), self._stream()))
+        return out
+
+    def cost(self, x, times, weights, want_vals: bool = False):
+        """The running cost of a batch of trajectories under any quadrature (ntg_batch_cost): x [batch, nC]; times and weights [ntimes]
+        or, after set_grids, both [batch, ntimes] (ntg_amd.quadrature builds such pairs).  Returns dict(cost [batch] = sum_i w_i L(t_i)
+        [, vals [batch, ntimes] = L(t_i)]).  The initial and final cost are not part of it.  weights may be None with want_vals: the
+        result is then dict(vals) alone."""
+        import torch
+        sp = self.spec
+        dev = x.device
+        _check_tensor(x, dev)
+        if x.dim() != 2 or x.shape[1] != sp.nC:
+            raise NtgError(f"x must be [batch, {sp.nC}]")
+        batch = x.shape[0]
+        if not (times.is_cuda and times.dtype == torch.float64):
+            raise NtgError("times must be a float64 tensor on the plan's device")
+        if weights is None and not want_vals:
+            raise NtgError("nothing asked for: pass weights, want_vals or both")
+        if weights is not None and not (weights.is_cuda and weights.dtype == torch.float64 and weights.shape == times.shape):
+            raise NtgError("weights must be a float64 tensor on the plan's device, of the shape of times")
+        stride = self._times_stride(batch, times)
+        ntimes = times.shape[-1]
+        out = {}
+        if weights is not None:
+            out["cost"] = torch.empty(batch, dtype=torch.float64, device=dev)
+        if want_vals:
+            out["vals"] = torch.empty((batch, ntimes), dtype=torch.float64, device=dev)
+        _check(lib().ntg_batch_cost(self.h, batch, _ptr(x), ntimes, _ptr(times.contiguous()), _ptr(None if weights is None else weights.contiguous()),
+                                    stride, _ptr(out.get("cost")), _ptr(out.get("vals")), self._stream()))
         return out
 
     def kkt(self, x, lower, upper, clambda, want_residual: bool = False):

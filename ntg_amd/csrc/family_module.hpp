@@ -19,6 +19,7 @@
 typedef hipError_t (*ntg_module_eval_fn)(const NtgDims &, const NtgTables &, const SmemLayout &, const EvalArgs &);
 typedef hipError_t (*ntg_module_sqp_fn)(const NtgDims &, const NtgTables &, const SmemLayout &, const SolveParams &, const SqpArgs &);
 typedef hipError_t (*ntg_module_check_fn)(const NtgDims &, const NtgTables &, const CheckArgs &);
+typedef hipError_t (*ntg_module_cost_fn)(const NtgDims &, const NtgTables &, const CostArgs &);
 
 struct ntg_family_module_desc {
 	unsigned long long abi;   // NTG_AMD_ABI the module was compiled with (first member in every version of the descriptor)
@@ -32,6 +33,8 @@ struct ntg_family_module_desc {
 	int nparam, nparam_bp;    // per-problem parameters: doubles per problem, doubles per breakpoint (ntg_plan_param_count)
 	int sizeof_check_args;
 	ntg_module_check_fn launch_check;   // the module's check_kernel instance (ntg_batch_check)
+	int sizeof_cost_args;
+	ntg_module_cost_fn launch_cost;     // the module's cost_kernel instance (ntg_batch_cost)
 };
 typedef const ntg_family_module_desc *(*ntg_family_module_entry_fn)(void);
 
@@ -54,6 +57,7 @@ struct NtgFamily {
 	ntg_module_eval_fn launch_eval;
 	ntg_module_sqp_fn launch_sqp;
 	ntg_module_check_fn launch_check;
+	ntg_module_cost_fn launch_cost;
 };
 
 // the registry (family_registry.cpp): ids 0 .. of the built-in families, ids >= NTG_FAM_MODULE_BASE of loaded modules; nullptr for any

@@ -12,6 +12,8 @@
 //                   whole solve (feasibility, projected inverse-BFGS, line search)
 //   check_kernel    trajectory rows of solved problems between the breakpoints (check.hpp; the
 //                   last step of its reduction, check_final_kernel, is here)
+//   cost_kernel     running cost of solved problems at arbitrary times, weighted sum per problem
+//                   (cost.hpp; the sum over the time tiles, cost_final_kernel, is here)
 //   kkt_kernel      first-order optimality residuals of a batch on the banded Jacobian (kkt.hpp)
 //
 // Mapping to CDNA4: one workgroup per problem; breakpoints (then coefficients) across the
@@ -471,6 +473,29 @@ __global__ void check_final_kernel(int batch, int ntiles, int ntimes, const doub
 hipError_t ntg_launch_check_final(int batch, int ntiles, int ntimes, const double *pviol, const long long *pkey, double *viol, int *where, hipStream_t st)
 {
 	hipLaunchKernelGGL(check_final_kernel, dim3((batch + 127) / 128), dim3(128), 0, st, batch, ntiles, ntimes, pviol, pkey, viol, where);
+	return hipGetLastError();
+}
+
+// ntg_batch_cost (cost.hpp): the family's cost_kernel instance ...
+hipError_t ntg_launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a)
+{
+	const NtgFamily *f = ntg_family(D.family);
+	return f ? f->launch_cost(D, T, a) : hipErrorInvalidValue;
+}
+
+// ... and its last step: the sum over a problem's time tiles (cost_kernel left one weighted partial sum per tile).  One thread per
+// problem, tiles in order.
+__global__ void cost_final_kernel(int batch, int ntiles, const double *__restrict__ pcost, double *__restrict__ cost)
+{
+	const int b = blockIdx.x * blockDim.x + threadIdx.x;
+	if (b >= batch) return;
+	double s = pcost[(size_t)b * ntiles];
+	for (int i = 1; i < ntiles; i++) s += pcost[(size_t)b * ntiles + i];
+	cost[b] = s;
+}
+hipError_t ntg_launch_cost_final(int batch, int ntiles, const double *pcost, double *cost, hipStream_t st)
+{
+	hipLaunchKernelGGL(cost_final_kernel, dim3((batch + 127) / 128), dim3(128), 0, st, batch, ntiles, pcost, cost);
 	return hipGetLastError();
 }
 

@@ -177,6 +177,16 @@ static inline size_t ntg_check_lds(const NtgDims &D)
 // ... and what a workgroup may ask for: 160 KiB less the static part
 #define NTG_CHECK_LDS_MAX (160 * 1024 - NTG_CHECK_LDS_STATIC)
 
+// cost_kernel (cost.hpp): the family's running cost at the times of the tile.  t: the tile fields of CheckArgs (b0 .. sumkd, gbase, lbase,
+// pp_tab, times_stride, x, times, tblk, toff, st), filled by the walk ntg_batch_check and ntg_batch_cost share and read by the steps of
+// time_tile.hpp; its row, bound and maxima fields are not used.  weights in the layout of times (null: no sum); vals [batch][ntimes] and pcost [batch][ntiles] (one weighted partial
+// sum per tile) may be null.  LDS: that of check_kernel (ntg_check_lds; the static part is the waves' sums and a family's parameter slot).
+struct CostArgs {
+	CheckArgs t;
+	const double *weights;
+	double *vals, *pcost;
+};
+
 // kkt_kernel (kkt.hpp): problems [b0, b0 + nb) of the batch, grid persistent workgroups.  x, lam ([batch][nC + nclin + ncnln], the first nC
 // entries of a problem never read), res ([batch][NTG_KKT_NRES]) and r ([batch][nC]) are the caller's, indexed by the problem of the batch;
 // either of res, r may be null.  g, c, jband (ntg_launch_eval's output) and bl, bu (ntg_launch_bounds') are the chunk's scratch, indexed by

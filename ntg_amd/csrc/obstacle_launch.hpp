@@ -4,6 +4,7 @@
 #pragma once
 #include "solve_impl.hpp"
 #include "check.hpp"
+#include "cost.hpp"
 
 template <int FAM>
 static hipError_t obstacle_launch_eval(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
@@ -38,4 +39,11 @@ template <int FAM>
 static hipError_t obstacle_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
 {
 	return launch_check<FAM, 6>(D, T, a);
+}
+
+// the running cost under a quadrature (cost.hpp): the same instance
+template <int FAM>
+static hipError_t obstacle_launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a)
+{
+	return launch_cost<FAM, 6>(D, T, a);
 }

@@ -389,11 +389,68 @@ extern "C" int ntg_batch_interp_strided(const ntg_plan *p, int batch, const doub
 	return 0;
 }
 
+// ---- the kernels with times on the lanes (time_tile.hpp): ntg_batch_check here, ntg_batch_cost in plan_cost.cpp ----
+// What a call with a time vector refuses, in the order the two calls document; 0: go on.
+int time_args_check(const ntg_plan *p, int batch, int ntimes, long long times_stride)
+{
+	if (p->grid_batch && batch != p->grid_batch) return fail(NTG_E_BADARG, "the plan carries per-problem grids for another batch size");
+	if (times_stride != 0 && times_stride < ntimes) return fail(NTG_E_BADARG, "times_stride must be 0 (one time vector for the batch) or >= ntimes");
+	if (times_stride != 0 && !p->grid_batch) return fail(NTG_E_BADARG, "per-problem times need per-problem grids (ntg_plan_set_grids); pass times_stride = 0");
+	if (int rc = check_params(p, batch)) return rc;
+	if (ntg_check_lds(p->D) > NTG_CHECK_LDS_MAX) return fail(NTG_E_UNSUPPORTED, "basis tables of one time tile exceed 160 KiB of LDS");
+	return 0;
+}
+
+// The walk over the batch: fills the tile fields of `a` (the caller set x, st and its own fields), builds the basis at the times (the
+// tables ntg_batch_interp builds) in scratch, stream ordered and released on every path, and calls launch(a) for every chunk of problems.
+// On the shared grid the tables do not depend on the batch: one launch.  On per-problem grids they are as large as the flags would be, so
+// the batch is processed in chunks of problems whose tables stay under scratch_cap bytes (at least one problem per chunk).
+hipError_t time_tile_walk(const ntg_plan *p, int batch, int ntimes, const double *d_times, long long times_stride, long long scratch_cap,
+                          CheckArgs &a, const std::function<hipError_t(const CheckArgs &)> &launch)
+{
+	const NtgDims &D = p->D;
+	hipStream_t st = a.st;
+	a.ntimes = ntimes; a.pp = p->grid_batch ? 1 : 0; a.ntiles = (ntimes + NTG_CHECK_NT - 1) / NTG_CHECK_NT;
+	a.times_stride = times_stride; a.times = d_times; a.sumkd = 0;
+	size_t tot = 0;   // doubles of one set of time tables: every class on the shared grid, the one class of a problem on per-problem grids
+	for (int c = 0; c < D.nclass; c++) { a.gbase[c] = (int)tot; a.lbase[c] = a.sumkd; tot += (size_t)ntimes * D.cls_k[c] * D.cls_d[c]; a.sumkd += D.cls_k[c] * D.cls_d[c]; }
+	a.pp_tab = (long long)tot;
+	const size_t per_tab = tot * 8 + (size_t)(a.pp ? 1 : D.nclass) * ntimes * 4;   // bytes of one set
+	const int chunk = a.pp ? (int)std::max<long long>(1, std::min<long long>(batch, scratch_cap / (long long)per_tab)) : batch;
+	const int ntab = a.pp ? chunk : 1;
+	double *d_tblk = nullptr; int *d_toff = nullptr;
+	hipError_t e = hipMallocAsync((void **)&d_tblk, (size_t)ntab * tot * 8, st);
+	if (e == hipSuccess) e = hipMallocAsync((void **)&d_toff, (size_t)ntab * (a.pp ? 1 : D.nclass) * ntimes * 4, st);
+	a.tblk = d_tblk; a.toff = d_toff;
+	// workgroups: (time tile, group of problems); a group's problems share the staged tile on the shared grid, so no more groups than
+	// fill the device a few times over
+	const int want_groups = std::max(1, (8 * plan_ncu(p) + a.ntiles - 1) / a.ntiles);
+	if (!a.pp) {
+		for (int c = 0; c < D.nclass && e == hipSuccess; c++)
+			e = ntg_launch_basis(1, D.cls_l[c], D.cls_k[c], D.cls_m[c], D.cls_d[c], ntimes, p->d_knots[c], d_times, 0, 0, d_tblk + a.gbase[c], d_toff + (size_t)c * ntimes, st);
+		a.b0 = 0; a.nb = batch; a.ngroups = std::min(std::min(batch, want_groups), 65535);
+		if (e == hipSuccess) e = launch(a);
+	} else {
+		// per-problem grids: every problem on its own knots (one basis class), at its own times or, times_stride == 0, all at the same
+		const int l = D.cls_l[0];
+		for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += chunk) {
+			const int nb = std::min(chunk, batch - b0);
+			for (int g0 = 0; g0 < nb && e == hipSuccess; g0 += 65535) {   // (basis_kernel takes at most 65535 grids per launch)
+				const int ng = std::min(65535, nb - g0);
+				e = ntg_launch_basis(ng, l, D.cls_k[0], D.cls_m[0], D.cls_d[0], ntimes, p->d_grid_knots + (size_t)(b0 + g0) * (l + 1),
+				                     d_times + (size_t)(b0 + g0) * times_stride, l + 1, times_stride, d_tblk + (size_t)g0 * tot, d_toff + (size_t)g0 * ntimes, st);
+			}
+			a.b0 = b0; a.nb = nb; a.ngroups = std::min(std::min(nb, want_groups), 65535);
+			if (e == hipSuccess) e = launch(a);
+		}
+	}
+	if (d_tblk) (void)hipFreeAsync(d_tblk, st);
+	if (d_toff) (void)hipFreeAsync(d_toff, st);
+	return e;
+}
+
 // ---- ntg_batch_check: the trajectory rows of solved problems between the breakpoints (check.hpp) ----
-// Scratch, stream ordered and released on every path: the basis at the times (the tables ntg_batch_interp builds) and one (violation,
-// key) pair per problem and tile of NTG_CHECK_NT times.  On the shared grid the tables do not depend on the batch.  On per-problem grids
-// they are as large as the flags would be, so the batch is processed in chunks of problems whose tables stay under scratch_cap bytes
-// (at least one problem per chunk).
+// Scratch besides the walk's: one (violation, key) pair per problem and tile of NTG_CHECK_NT times.
 #define NTG_CHECK_SCRATCH_CAP (64ll << 20)
 static int batch_check(const ntg_plan *p, int batch, const double *d_x, const double *d_lower, const double *d_upper, int ntimes,
                        const double *d_times, long long times_stride, double *d_viol, int *d_where, double *d_rows, void *stream,
@@ -409,56 +466,22 @@ static int batch_check(const ntg_plan *p, int batch, const double *d_x, const do
 	if (!d_x || !d_times) return fail(NTG_E_BADARG, "null argument");
 	if (!d_viol && !d_where && !d_rows) return fail(NTG_E_BADARG, "no output asked for: pass d_viol, d_where or d_rows");
 	if ((d_viol || d_where) && (!d_lower || !d_upper)) return fail(NTG_E_BADARG, "violations need the bounds (d_lower, d_upper)");
-	if (p->grid_batch && batch != p->grid_batch) return fail(NTG_E_BADARG, "the plan carries per-problem grids for another batch size");
-	if (times_stride != 0 && times_stride < ntimes) return fail(NTG_E_BADARG, "times_stride must be 0 (one time vector for the batch) or >= ntimes");
-	if (times_stride != 0 && !p->grid_batch) return fail(NTG_E_BADARG, "per-problem times need per-problem grids (ntg_plan_set_grids); pass times_stride = 0");
-	if (int rc = check_params(p, batch)) return rc;
 	if (scratch_cap <= 0) return fail(NTG_E_BADARG, "scratch cap must be positive");
+	if (int rc = time_args_check(p, batch, ntimes, times_stride)) return rc;
 	HIPCHK(hipSetDevice(p->device));
 	hipStream_t st = (hipStream_t)stream;
 	const bool want_max = d_viol || d_where;
+	const int ntiles = (ntimes + NTG_CHECK_NT - 1) / NTG_CHECK_NT;
 	CheckArgs a{};
-	a.ntimes = ntimes; a.pp = p->grid_batch ? 1 : 0; a.ntiles = (ntimes + NTG_CHECK_NT - 1) / NTG_CHECK_NT;
-	a.times_stride = times_stride; a.x = d_x; a.lo = want_max ? d_lower : nullptr; a.up = want_max ? d_upper : nullptr;
-	a.times = d_times; a.ltc = p->d_ltc; a.rows = d_rows; a.st = st;
-	size_t tot = 0;   // doubles of one set of time tables: every class on the shared grid, the one class of a problem on per-problem grids
-	for (int c = 0; c < D.nclass; c++) { a.gbase[c] = (int)tot; a.lbase[c] = a.sumkd; tot += (size_t)ntimes * D.cls_k[c] * D.cls_d[c]; a.sumkd += D.cls_k[c] * D.cls_d[c]; }
-	if (ntg_check_lds(D) > NTG_CHECK_LDS_MAX) return fail(NTG_E_UNSUPPORTED, "basis tables of one time tile exceed 160 KiB of LDS");
-	a.pp_tab = (long long)tot;
-	const size_t per_tab = tot * 8 + (size_t)(a.pp ? 1 : D.nclass) * ntimes * 4;   // bytes of one set
-	const int chunk = a.pp ? (int)std::max<long long>(1, std::min<long long>(batch, scratch_cap / (long long)per_tab)) : batch;
-	const int ntab = a.pp ? chunk : 1;
-	double *d_tblk = nullptr, *d_pv = nullptr; int *d_toff = nullptr; long long *d_pk = nullptr;
-	hipError_t e = hipMallocAsync((void **)&d_tblk, (size_t)ntab * tot * 8, st);
-	if (e == hipSuccess) e = hipMallocAsync((void **)&d_toff, (size_t)ntab * (a.pp ? 1 : D.nclass) * ntimes * 4, st);
-	if (e == hipSuccess && want_max) e = hipMallocAsync((void **)&d_pv, (size_t)batch * a.ntiles * 8, st);
-	if (e == hipSuccess && want_max) e = hipMallocAsync((void **)&d_pk, (size_t)batch * a.ntiles * 8, st);
-	a.tblk = d_tblk; a.toff = d_toff; a.pviol = d_pv; a.pkey = d_pk;
-	// workgroups: (time tile, group of problems); a group's problems share the staged tile on the shared grid, so no more groups than
-	// fill the device a few times over
-	const int want_groups = std::max(1, (8 * plan_ncu(p) + a.ntiles - 1) / a.ntiles);
-	if (!a.pp) {
-		for (int c = 0; c < D.nclass && e == hipSuccess; c++)
-			e = ntg_launch_basis(1, D.cls_l[c], D.cls_k[c], D.cls_m[c], D.cls_d[c], ntimes, p->d_knots[c], d_times, 0, 0, d_tblk + a.gbase[c], d_toff + (size_t)c * ntimes, st);
-		a.b0 = 0; a.nb = batch; a.ngroups = std::min(std::min(batch, want_groups), 65535);
-		if (e == hipSuccess) e = ntg_launch_check(D, p->T, a);
-	} else {
-		// per-problem grids: every problem on its own knots (one basis class), at its own times or, times_stride == 0, all at the same
-		const int l = D.cls_l[0];
-		for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += chunk) {
-			const int nb = std::min(chunk, batch - b0);
-			for (int g0 = 0; g0 < nb && e == hipSuccess; g0 += 65535) {   // (basis_kernel takes at most 65535 grids per launch)
-				const int ng = std::min(65535, nb - g0);
-				e = ntg_launch_basis(ng, l, D.cls_k[0], D.cls_m[0], D.cls_d[0], ntimes, p->d_grid_knots + (size_t)(b0 + g0) * (l + 1),
-				                     d_times + (size_t)(b0 + g0) * times_stride, l + 1, times_stride, d_tblk + (size_t)g0 * tot, d_toff + (size_t)g0 * ntimes, st);
-			}
-			a.b0 = b0; a.nb = nb; a.ngroups = std::min(std::min(nb, want_groups), 65535);
-			if (e == hipSuccess) e = ntg_launch_check(D, p->T, a);
-		}
-	}
-	if (e == hipSuccess && want_max) e = ntg_launch_check_final(batch, a.ntiles, ntimes, d_pv, d_pk, d_viol, d_where, st);
-	if (d_tblk) (void)hipFreeAsync(d_tblk, st);
-	if (d_toff) (void)hipFreeAsync(d_toff, st);
+	a.x = d_x; a.lo = want_max ? d_lower : nullptr; a.up = want_max ? d_upper : nullptr;
+	a.ltc = p->d_ltc; a.rows = d_rows; a.st = st;
+	double *d_pv = nullptr; long long *d_pk = nullptr;
+	hipError_t e = hipSuccess;
+	if (want_max) e = hipMallocAsync((void **)&d_pv, (size_t)batch * ntiles * 8, st);
+	if (e == hipSuccess && want_max) e = hipMallocAsync((void **)&d_pk, (size_t)batch * ntiles * 8, st);
+	a.pviol = d_pv; a.pkey = d_pk;
+	if (e == hipSuccess) e = time_tile_walk(p, batch, ntimes, d_times, times_stride, scratch_cap, a, [&](const CheckArgs &c) { return ntg_launch_check(D, p->T, c); });
+	if (e == hipSuccess && want_max) e = ntg_launch_check_final(batch, ntiles, ntimes, d_pv, d_pk, d_viol, d_where, st);
 	if (d_pv) (void)hipFreeAsync(d_pv, st);
 	if (d_pk) (void)hipFreeAsync(d_pk, st);
 	if (e == hipErrorInvalidValue) return fail(NTG_E_UNSUPPORTED, "the plan's family has no check instance for this shape");

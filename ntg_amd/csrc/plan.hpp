@@ -68,6 +68,9 @@ hipError_t ntg_launch_refine(const RefineArgs &A, int pp, int ncu, hipStream_t s
 // trajectory rows at arbitrary times (check.hpp): the family's check_kernel instance, then the maximum over a problem's time tiles
 hipError_t ntg_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a);
 hipError_t ntg_launch_check_final(int batch, int ntiles, int ntimes, const double *pviol, const long long *pkey, double *viol, int *where, hipStream_t st);
+// running cost at arbitrary times (cost.hpp): the family's cost_kernel instance, launched like check_kernel, then the sum over a problem's time tiles
+hipError_t ntg_launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a);
+hipError_t ntg_launch_cost_final(int batch, int ntiles, const double *pcost, double *cost, hipStream_t st);
 // first-order optimality residuals (kkt.hpp): one chunk of problems, after ntg_launch_eval (mode 2) and ntg_launch_bounds filled its scratch
 hipError_t ntg_launch_kkt(const NtgDims &D, const NtgTables &T, const KktArgs &a);
 hipError_t ntg_launch_kincar_reverse(long long nsamp, int nz, int ncars, double wheelbase, int reverse_gear, const double *z, double *out, hipStream_t st);

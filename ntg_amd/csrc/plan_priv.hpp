@@ -5,10 +5,12 @@
 //                   preconditioner; plan queries
 //   plan_grids.cpp  per-problem grids (ntg_plan_set_grids) and per-problem family parameters
 //   plan_kkt.cpp    ntg_batch_kkt: first-order optimality residuals of a batch
+//   plan_cost.cpp   ntg_batch_cost: the running cost of a batch at arbitrary times under a quadrature
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
+#include <functional>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -115,3 +117,8 @@ int check_params(const ntg_plan *p, int batch);
 // launch shape of the evaluation of `batch` problems: workgroup size, persistent grid, LDS layout; 0 or an error code  (plan.cpp)
 struct EvalShape { int nt, grid; SmemLayout L; };
 int eval_shape(const ntg_plan *p, int batch, EvalShape *s);
+// calls with a time vector (ntg_batch_check, ntg_batch_cost; plan.cpp): what they refuse about the batch, the stride, the parameters and
+// the LDS; and the walk over the batch with the basis at the times in stream-ordered scratch, launch(a) once per chunk of problems
+int time_args_check(const ntg_plan *p, int batch, int ntimes, long long times_stride);
+hipError_t time_tile_walk(const ntg_plan *p, int batch, int ntimes, const double *d_times, long long times_stride, long long scratch_cap,
+                          CheckArgs &a, const std::function<hipError_t(const CheckArgs &)> &launch);

@@ -47,7 +47,7 @@ def stale(source: str, out: str | None = None) -> bool:
 
 
 def _check_unit(source: str, out: str) -> tuple[str, str, str]:
-    """files of a module's second compilation (its check_kernel instance, NTG_AMD_MODULE_PART = 2): a one-line wrapper source next to
+    """files of a module's second compilation (its check_kernel and cost_kernel instances, NTG_AMD_MODULE_PART = 2): a one-line wrapper source next to
     the output -- a name of its own, so that hipcc -save-temps keeps its device assembly apart -- its object, and the first part's object"""
     stem = os.path.splitext(os.path.basename(source))[0]
     d = os.path.dirname(os.path.abspath(out))
@@ -62,7 +62,7 @@ def write_check_unit(source: str, out: str) -> None:
 
 def module_commands(source: str, out: str, abi: str | None = None) -> tuple[list[str], list[str], list[str]]:
     """hipcc command lines of one module (abi: another header stamp than this tree's -- tests of the refusal only): the two
-    compilations of the source, independent of each other -- everything but the check instance (part 1), the check instance from the
+    compilations of the source, independent of each other -- everything but the check and cost instances (part 1), those two from the
     wrapper of write_check_unit (part 2) -- and the link of their objects"""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     wrap, cobj, mobj = _check_unit(source, out)
