@@ -28,6 +28,15 @@ __device__ __forceinline__ void static_for(F &&f)
 {
 	if constexpr (J < N) { f(std::integral_constant<int, J>{}); static_for<J + 1, N>(f); }
 }
+// the same, nested: step J runs only if c(J) holds and steps J + 1 .. N - 1 only inside it (a monotone test such as J < n is made once
+// per step that runs, plus once at the first that does not)
+template <int J, int N, class C, class F>
+__device__ __forceinline__ void static_while(C &&c, F &&f)
+{
+	if constexpr (J < N) {
+		if (c(J)) { f(std::integral_constant<int, J>{}); static_while<J + 1, N>(c, f); }
+	}
+}
 
 // value of the previous / next lane of the wavefront (DPP wave_shr:1 / wave_shl:1; lane 0 / lane 63 receive 0)
 __device__ __forceinline__ double from_prev(double v)
@@ -482,9 +491,22 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 	// buffers, link by link (t += d_i (e delta_{i+1} + f delta_i) + d_{i+1} e delta_i), the first round requested before the on-chip
 	// passes start -- its latency hides behind them.  (Round 4 tried the two-pass form for the HBM tier as well -- one FMA per element
 	// instead of two, 16 dot products per butterfly instead of a reduction per round: fewer instructions, but the tier is bound by its
-	// loads, and reading it twice made the headline 7 % and the cold start to convergence 32 % slower.  Measured, dropped.)
+	// loads, and reading it twice made the headline 7 % and the cold start to convergence 32 % slower.  Measured, dropped.  Requesting the
+	// second round before the on-chip passes as well holds 24 more registers across them: the allocator then parks values in its own
+	// accumulator registers, +1 to +2 % on the headline.  Measured, dropped.)
+	// On the instances with one wave per SIMD (PIPE) no load of the on-chip tiers is waited for where it is issued: the LDS tier runs
+	// load-ahead through LB register buffers in both passes (the first LB - 1 slots are requested before the register tier of the same pass
+	// starts and land behind it; slot u + LB - 1 is requested before slot u is used), kappa's six operands are read in one round trip, and
+	// pass 1 visits the register tier in DESCENDING order so that slots 0 .. RK-1 are still in VGPRs when pass 2 starts with them.  Nothing
+	// of this changes a sum: every delta has its own accumulator, every butterfly carries the same group of 16 slots, tv accumulates over
+	// ascending slots.
 	constexpr int H0 = NREG + NLDS, HG = 2;   // chain slots per round of the HBM tier (two register buffers of HG vectors; other round sizes were never
 	                                          // validated -- variant builds with 3 and 4 faulted on the GPU, profiles/r04_incidents -- so this is not a knob)
+	// LB, RK: the most the register allocator takes without moving into the accumulator range or spilling more scalars (ntg_amd/isa_audit.py
+	// and tests/test_wave_sweep_isa.py hold it there; the per-problem-grid instances have no register to spare for RK).  The instances with
+	// two waves per SIMD keep the plain loops: they have no spare registers, and the other wave hides the latency.
+	constexpr bool PIPE = MINW == 1;
+	constexpr int LB = 2, RK = (PIPE && NREG > 0 && !PPG) ? (4 < NREG ? 4 : NREG) : 0;
 	auto sweep = [&](int ns, const double (&v)[EPL], double (&tv)[EPL]) {
 		if (ns < 2) return;   // a chain of one vector carries no update yet
 		const int nso = min(ns, H0);   // on-chip slots; the links nso-1 .. ns-2 belong to the HBM rounds
@@ -501,6 +523,13 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 		double acc[16];
 #pragma unroll
 		for (int k = 0; k < 16; k++) acc[k] = 0.0;
+		// PIPE: the LDS tier's register buffers, the register slots kept from pass 1 to pass 2, and the request for the first LDS slots
+		double lb[LB][EPL], keep[RK > 0 ? RK : 1][EPL];
+		int nso1 = nso;
+		if constexpr (PIPE && NLDS > 0) asm volatile("" : "+s"(nso1));
+		auto lds_ahead = [&](int n) __attribute__((always_inline)) {
+			if (NREG < n) static_for<0, (LB - 1 < NLDS ? LB - 1 : NLDS)>([&](auto Uc) __attribute__((always_inline)) { constexpr int U = decltype(Uc)::value; lds_get(NREG + U, lb[U]); });
+		};
 		auto flush = [&](int base) __attribute__((always_inline)) {   // slots base .. base+15 -> delta
 			int ln = lane;
 			asm volatile("" : "+v"(ln));   // (see wave_sums)
@@ -510,18 +539,36 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 			for (int k = 0; k < 16; k++) acc[k] = 0.0;
 		};
 		// pass 1: delta_j = d_j . v
+		if constexpr (PIPE && NLDS > 0) lds_ahead(nso1);
 		if constexpr (NREG > 0) {
+			// RK > 0: slots in descending order -- the RK oldest are read last and stay in registers for pass 2.  Every delta has its own
+			// accumulator and every butterfly carries the same group of 16 slots in either order.
 			static_for<0, NREG>([&](auto Jc) __attribute__((always_inline)) {
-				constexpr int J = decltype(Jc)::value;
+				constexpr int J = RK > 0 ? NREG - 1 - decltype(Jc)::value : decltype(Jc)::value;
 				if (J < nso) {
 					double h[EPL];
 					static_for<0, EPL>([&](auto Ec) __attribute__((always_inline)) { constexpr int E = decltype(Ec)::value; h[E] = areg_read<ABASE, J * EPL + E>(); });
+					if constexpr (J < RK) {
+#pragma unroll
+						for (int e = 0; e < EPL; e++) keep[J][e] = h[e];
+					}
 					acc[J & 15] = dot(h, v);
 				}
-				if ((J & 15) == 15 || J == NREG - 1) { if (J - (J & 15) < nso) flush(J - (J & 15)); }
+				// the group's butterfly after its last slot: the group's base when descending, its top (or the tier's last slot) when ascending
+				if constexpr (RK > 0 ? (J & 15) == 0 : ((J & 15) == 15 || J == NREG - 1)) { if (J - (J & 15) < nso) flush(J - (J & 15)); }
 			});
 		}
-		if constexpr (NLDS > 0) {
+		if constexpr (PIPE && NLDS > 0) {
+			if (NREG < nso1) {
+				static_while<0, NLDS>([&](int u) __attribute__((always_inline)) { return NREG + u < nso1; }, [&](auto Uc) __attribute__((always_inline)) {
+					constexpr int U = decltype(Uc)::value;
+					if constexpr (U + LB - 1 < NLDS) lds_get(NREG + U + LB - 1, lb[(U + LB - 1) % LB]);
+					acc[U] = dot(lb[U % LB], v);
+					asm volatile("" : "+v"(acc[U]));   // (pins the dot product here: left free, all of them sank below the last load -- NLDS buffers live)
+				});
+				flush(NREG);
+			}
+		} else if constexpr (NLDS > 0) {
 			for (int base = NREG; base < nso; base += 16) {
 #pragma unroll
 				for (int u = 0; u < 16; u++) {
@@ -535,13 +582,25 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 		// kappa_j = f_j delta_j + e_j delta_{j+1} + e_{j-1} delta_{j-1}; link i = (e_i, f_i) joins slots i and i + 1.  Lane j keeps kappa_j
 		// for the broadcasts of pass 2 (the on-chip tiers hold fewer than 64 slots)
 		static_assert(H0 <= 64, "kappa of the on-chip slots lives in one register");
+		static_assert(!PIPE || (NLDS <= 16 && H0 >= 2), "pipelined sweep: the LDS tier is one group of at most 16 accumulators, and kappa's clamped reads need two on-chip slots");
 		double kap0 = 0.0;
-		for (int j = lane; j < nso; j += 64) {
-			const double dj = s_dl[j];
+		if constexpr (PIPE) {
+			// all six reads at once, unconditionally, from clamped indices (a lane past the chain reads the last slot's), selected afterwards:
+			// one LDS round trip instead of two or three dependent ones behind lane branches
+			const int j = lane, jc = min(j, nso - 1), jn = min(jc + 1, nso - 1), jp = max(jc - 1, 0);
+			const double dj = s_dl[jc], dn = s_dl[jn], dp = s_dl[jp], lf = s_lk[2 * jc + 1], le = s_lk[2 * jc], lp = s_lk[2 * jp];
 			double k = 0.0;
-			if (j < nso - 1) k += s_lk[2 * j + 1] * dj + s_lk[2 * j] * s_dl[j + 1];
-			if (j > 0) k += s_lk[2 * j - 2] * s_dl[j - 1];
-			if (j == lane) kap0 = k;
+			if (j < nso - 1) k += lf * dj + le * dn;
+			if (j > 0) k += lp * dp;
+			if (j < nso) kap0 = k;
+		} else {
+			for (int j = lane; j < nso; j += 64) {
+				const double dj = s_dl[j];
+				double k = 0.0;
+				if (j < nso - 1) k += s_lk[2 * j + 1] * dj + s_lk[2 * j] * s_dl[j + 1];
+				if (j > 0) k += s_lk[2 * j - 2] * s_dl[j - 1];
+				if (j == lane) kap0 = k;
+			}
 		}
 		auto kappa_of = [&](int j) -> double {   // uniform j < 64
 			return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(kap0), j), __builtin_amdgcn_readlane(__double2loint(kap0), j));
@@ -551,6 +610,7 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 		// a round of four slots are read from their lanes together: the reads fill each other's wait states before the first FMA uses one.)
 		int nso2 = nso;
 		asm volatile("" : "+s"(nso2));
+		if constexpr (PIPE && NLDS > 0) lds_ahead(nso2);
 		if constexpr (NREG > 0) {
 			static_for<0, (NREG + 3) / 4>([&](auto Gc) __attribute__((always_inline)) {
 				constexpr int J0 = 4 * decltype(Gc)::value;
@@ -561,13 +621,30 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 					static_for<0, 4>([&](auto Uc) __attribute__((always_inline)) {
 						constexpr int U = decltype(Uc)::value, J = J0 + U;
 						if constexpr (J < NREG) {
-							if (J < nso2) static_for<0, EPL>([&](auto Ec) __attribute__((always_inline)) { constexpr int E = decltype(Ec)::value; tv[E] += kq[U] * areg_read<ABASE, J * EPL + E>(); });
+							if constexpr (J < RK) {   // still in registers from pass 1
+								if (J < nso2) static_for<0, EPL>([&](auto Ec) __attribute__((always_inline)) { constexpr int E = decltype(Ec)::value; tv[E] += kq[U] * keep[J][E]; });
+							} else {
+								if (J < nso2) static_for<0, EPL>([&](auto Ec) __attribute__((always_inline)) { constexpr int E = decltype(Ec)::value; tv[E] += kq[U] * areg_read<ABASE, J * EPL + E>(); });
+							}
 						}
 					});
 				}
 			});
 		}
-		if constexpr (NLDS > 0) {
+		if constexpr (PIPE && NLDS > 0) {
+			double kq[4];
+			static_while<0, NLDS>([&](int u) __attribute__((always_inline)) { return NREG + u < nso2; }, [&](auto Uc) __attribute__((always_inline)) {
+				constexpr int U = decltype(Uc)::value;
+				if constexpr (U % 4 == 0) {
+					static_for<0, 4>([&](auto Qc) __attribute__((always_inline)) { constexpr int Q = decltype(Qc)::value; kq[Q] = bcast(kap0, NREG + U + Q < 63 ? NREG + U + Q : 63); });
+				}
+				if constexpr (U + LB - 1 < NLDS) lds_get(NREG + U + LB - 1, lb[(U + LB - 1) % LB]);
+#pragma unroll
+				for (int e = 0; e < EPL; e++) tv[e] += kq[U % 4] * lb[U % LB][e];
+#pragma unroll
+				for (int e = 0; e < EPL; e++) asm volatile("" : "+v"(tv[e]));   // (pins the axpy here, see pass 1)
+			});
+		} else if constexpr (NLDS > 0) {
 			for (int j = NREG; j < nso; j++) {
 				const double kj = kappa_of(j);
 				double h[EPL]; lds_get(j, h);
