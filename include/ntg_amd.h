@@ -26,6 +26,8 @@
  *   ntg_batch_check      SplineInterp + the trajectory rows of NPfuncon (constraints.c:119-160) at arbitrary times + bounds, fused
  *   ntg_batch_cost       SplineInterp + the integrand of IntegratedCost (cost.c with integrator.c, reached through NPfunobj, ntg.c:274-280) at
  *                        arbitrary nodes under the caller's quadrature weights, fused; the reference integrates by the trapezoid rule on the breakpoints only
+ *   ntg_batch_verify     NPSOL's derivative verification behind npsol_() (ntg.c:249-253: "derivative level = 3" is declared and the verification
+ *                        left on), for a batch: the family's analytic derivatives against central differences, plus the active-variable lists
  *   ntg_batch_refine     nothing in the reference carries a spline to other knots; the nearest is SplineInterp (colloc.c:449-484), which the
  *                        result reproduces: the refined coefficients describe the same function
  *   ntg_batch_kincar_reverse  examples/kincar.c:68-92 kincar_flat_reverse (the example's flat-to-state map), for a batch
@@ -277,6 +279,45 @@ int ntg_batch_check(const ntg_plan *p, int batch, const double *d_x, const doubl
 int ntg_batch_cost(const ntg_plan *p, int batch, const double *d_x,
                    int ntimes, const double *d_times, const double *d_weights, long long times_stride,
                    double *d_cost, double *d_vals, void *stream);
+
+/* Audit the PROBLEM DEFINITION before anybody solves: the analytic derivatives the plan's family returns against central differences, and
+ * the plan's active-variable lists against what the callbacks depend on.  Every solver mode trusts both; the reference gets the first check
+ * from NPSOL's derivative verification (ntg.c:249-253).  d_x [batch][nC]: any coefficients -- a random point, a guess, a solution.
+ * For every problem the full flat flag z, all nz entries, is built by SplineInterp's arithmetic (colloc.c:476-481) on the plan's basis, or
+ * after ntg_plan_set_grids on that problem's own.  The six callback slots, in this order everywhere below: icf, ucf, fcf, nlicf, nltcf,
+ * nlfcf (NTG_VERIFY_NSLOT).  Initial slots (icf, nlicf) are audited at breakpoint 0, trajectory slots (ucf, nltcf) at every breakpoint,
+ * final slots (fcf, nlfcf) at the last breakpoint; a slot the plan does not use (nicf == 0, nnltc == 0, ...) is not called at all.  The
+ * callback receives the breakpoint index and the problem's parameter row exactly as in ntg_batch_eval (parameters per problem, per row
+ * function and per breakpoint alike: the points are the breakpoints, so families with NPARAM_BP > 0 are audited too).
+ * Definition.  For every point, every function of a slot (the cost, or constraint row j) and every flag entry v:
+ *   h = 2^-17 * max(1, |z_v|),  zp = z_v + h,  zm = z_v - h,  fd = (f(zp) - f(zm)) / (zp - zm)       only entry v moves
+ *   an = the analytic df[v] or dc[j][v] at the unperturbed z
+ *   scale = max(1, |f(z)|, |an|, |fd|),  e = |fd - an| / scale
+ * 2^-17 ~ 7.6e-6 is eps^(1/3) rounded to a power of two, the step that balances a central difference's truncation error against its
+ * rounding error; the division is by the step actually taken.
+ * Outputs (any may be NULL, not all four):
+ *   d_err        [batch][6]     per slot the largest e over the points, functions and entries v THAT THE SLOT'S OWN ACTIVE-VARIABLE LIST
+ *                               NAMES (icostav / tcostav / fcostav for the costs, icav / tcav / fcav for the rows); 0 for an unused slot
+ *   d_where      [batch][6][3]  {function (0 for a cost, the row for constraints), breakpoint, flag entry} of that maximum; on equal
+ *                               values the smallest (function * nbps + breakpoint) * nz + entry wins; {-1, -1, -1} where d_err is 0
+ *   d_leak       [batch][6]     per slot the largest max(|an|, |fd|) / scale over the entries v the slot's list does NOT name: anything
+ *                               above rounding means the callback depends on an entry the solver never gives it (the kernels only
+ *                               materialise the entries some list names; a missing ntg_av entry makes the callback read a zero,
+ *                               silently); 0 for an unused slot or a list that names every entry
+ *   d_leak_where [batch][6][3]  as d_where, for d_leak
+ * A NaN among the inputs of a maximum stays in it (ntg_batch_kkt's rule); its place is that of the first NaN in the order above.
+ * There is NO threshold inside the library: the caller decides what counts as wrong.  A wrong derivative shows at the size of its relative
+ * error (a sign error near 1, a factor 1 + 1/64 near 1e-2, a dependence on an unlisted entry at the size of that derivative), while the
+ * arithmetic noise of a correct family sits many orders of magnitude below that (DESIGN.md 2g states the floor).
+ * Stream ordered.  Scratch is stream ordered, released on every path and does not grow with batch * nbps * nz (per-problem grids: the batch
+ * goes through in chunks).  Maxima with a total order on ties, no floating-point atomics: results are bit-identical from call to call and
+ * do not depend on the batch around a problem.
+ * NTG_E_UNSUPPORTED for host-callback plans, for a plan whose basis tables of one tile of 128 breakpoints exceed the LDS
+ * (ntg_batch_check's limit) and for a plan shape the family has no instance for; NTG_E_BADARG for a null plan, null d_x, all outputs null,
+ * parameters needed but not set, a batch other than the grids' or the parameters'.  batch <= 0 returns 0. */
+#define NTG_VERIFY_NSLOT 6   /* icf, ucf, fcf, nlicf, nltcf, nlfcf -- in this order */
+int ntg_batch_verify(const ntg_plan *p, int batch, const double *d_x,
+                     double *d_err, int *d_where, double *d_leak, int *d_leak_where, void *stream);
 
 /* Audit a batch of points: the first-order optimality (KKT) residuals of  min F(x)  s.t.  bl <= (A x, c(x)) <= bu  at d_x with the
  * multipliers d_clambda, whoever produced them -- ntg_batch_solve stopped by its own rule (inform 0), capped by itlim or run with

@@ -53,6 +53,7 @@
 #include "../ntg_amd/csrc/solve_impl.hpp"
 #include "../ntg_amd/csrc/check.hpp"
 #include "../ntg_amd/csrc/cost.hpp"
+#include "../ntg_amd/csrc/verify.hpp"
 #include "../ntg_amd/csrc/family_module.hpp"
 #else
 #define NTG_AMD_FAMILY_DEVICE 0
@@ -111,12 +112,12 @@ struct FamilyDefaults {
 #if NTG_AMD_FAMILY_DEVICE
 // FAMILY: the family struct; NAME: a string literal; NOUT_REQUIRED: the number of outputs a plan must have, 0 = any.
 // Instantiates the generic kernels (run-time nout and spline order) for FAMILY -- evaluation at 128 / 256 / 512 threads, solve at
-// 128 / 256 / 512 threads plus the HBM-resident (BIG) form at 256 / 512, the between-breakpoints check (check.hpp) and the running cost
-// under a quadrature (cost.hpp) -- and exports one
+// 128 / 256 / 512 threads plus the HBM-resident (BIG) form at 256 / 512, the between-breakpoints check (check.hpp), the running cost
+// under a quadrature (cost.hpp) and the derivative audit at the breakpoints (verify.hpp) -- and exports one
 // symbol, the entry point ntg_family_module_v1, which returns the descriptor the library checks at load (family_module.hpp).  Use it
 // once per module.
 // A module is built from two compilations of the same source (ntg_amd/family.py does both): NTG_AMD_MODULE_PART = 1, the evaluation
-// and solve instances, the descriptor and the entry point; NTG_AMD_MODULE_PART = 2, the check and cost instances and their launchers alone.  Each
+// and solve instances, the descriptor and the entry point; NTG_AMD_MODULE_PART = 2, the check, cost and verify instances and their launchers alone.  Each
 // part keeps its own device assembly.  NTG_AMD_MODULE_PART = 0 (the default) is the whole module in one compilation.
 #ifndef NTG_AMD_MODULE_PART
 #define NTG_AMD_MODULE_PART 0
@@ -126,13 +127,15 @@ struct FamilyDefaults {
 	static_assert(FAMILY::DM >= 1 && FAMILY::NNLIC >= 0 && FAMILY::NNLTC >= 0 && FAMILY::NNLFC >= 0, "bad family constants");           \
 	static_assert(FamPrmCounts<FAMILY>::n >= 0 && FamPrmCounts<FAMILY>::bp >= 0 && FamPrmRow<FAMILY>::value == 0, "bad parameter counts");  \
 	template <> struct Family<NTG_FAM_MODULE_SLOT> : FAMILY {};
-// the check and cost launchers: hidden like everything but the entry point, with names of their own so that the two parts can refer to them
+// the check, cost and verify launchers: hidden like everything but the entry point, with names of their own so that the two parts can refer to them
 #define NTG_AMD_MODULE_CHECK_DECL_                                                                                                         \
 	hipError_t ntg_module_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a);                                         \
-	hipError_t ntg_module_launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a)
+	hipError_t ntg_module_launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a);                                            \
+	hipError_t ntg_module_launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a)
 #define NTG_AMD_MODULE_CHECK_                                                                                                              \
 	hipError_t ntg_module_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a) { return launch_check<NTG_FAM_MODULE_SLOT, NTG_MAX_NZ>(D, T, a); } \
-	hipError_t ntg_module_launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a) { return launch_cost<NTG_FAM_MODULE_SLOT, NTG_MAX_NZ>(D, T, a); }
+	hipError_t ntg_module_launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a) { return launch_cost<NTG_FAM_MODULE_SLOT, NTG_MAX_NZ>(D, T, a); } \
+	hipError_t ntg_module_launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a) { return launch_verify<NTG_FAM_MODULE_SLOT, NTG_MAX_NZ>(D, T, a); }
 #define NTG_AMD_MODULE_MAIN_(FAMILY, NAME, NOUT_REQUIRED)                                                                                  \
 	namespace {                                                                                                                            \
 	hipError_t ntg_module_launch_eval(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)                      \
@@ -147,7 +150,7 @@ struct FamilyDefaults {
 		NTG_AMD_ABI, (int)sizeof(NtgDims), (int)sizeof(NtgTables), (int)sizeof(SmemLayout), (int)sizeof(SolveParams),                     \
 		(int)sizeof(EvalArgs), (int)sizeof(SqpArgs), NAME, FAMILY::DM, FAMILY::NNLIC, FAMILY::NNLTC, FAMILY::NNLFC, (NOUT_REQUIRED),        \
 		&ntg_module_launch_eval, &ntg_module_launch_sqp, FamPrmCounts<FAMILY>::n, FamPrmCounts<FAMILY>::bp, (int)sizeof(CheckArgs),     \
-		&ntg_module_launch_check, (int)sizeof(CostArgs), &ntg_module_launch_cost};                                                                                                      \
+		&ntg_module_launch_check, (int)sizeof(CostArgs), &ntg_module_launch_cost, (int)sizeof(VerifyArgs), &ntg_module_launch_verify};                                                                                                  \
 	}                                                                                                                                      \
 	extern "C" __attribute__((visibility("default"))) const ntg_family_module_desc *ntg_family_module_v1(void) { return &ntg_module_desc; }
 #if NTG_AMD_MODULE_PART == 0

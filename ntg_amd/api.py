@@ -79,6 +79,7 @@ def lib():
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_batch_kkt.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
         L.ntg_batch_cost.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ntg_batch_verify.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_batch_refine.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_plan_set_grids.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ntg_plan_clear_grids.argtypes = [C.c_void_p]
@@ -322,6 +323,26 @@ class Plan:
             out["vals"] = torch.empty((batch, ntimes), dtype=torch.float64, device=dev)
         _check(lib().ntg_batch_cost(self.h, batch, _ptr(x), ntimes, _ptr(times.contiguous()), _ptr(None if weights is None else weights.contiguous()),
                                     stride, _ptr(out.get("cost")), _ptr(out.get("vals")), self._stream()))
+        return out
+
+    def verify(self, x, want_leak: bool = True):
+        """Audit the family's analytic derivatives and the plan's active-variable lists at x [batch, nC] (ntg_batch_verify): central
+        differences of the six callback slots (icf, ucf, fcf, nlicf, nltcf, nlfcf) at the breakpoints.  Returns dict(err [batch, 6],
+        where [batch, 6, 3] = (function, breakpoint, flag entry) [, leak [batch, 6], leak_where [batch, 6, 3]]).  No threshold is applied:
+        a wrong derivative shows at the size of its relative error, a correct family at rounding noise."""
+        import torch
+        sp = self.spec
+        dev = x.device
+        _check_tensor(x, dev)
+        if x.dim() != 2 or x.shape[1] != sp.nC:
+            raise NtgError(f"x must be [batch, {sp.nC}]")
+        batch = x.shape[0]
+        out = dict(err=torch.zeros((batch, 6), dtype=torch.float64, device=dev), where=torch.full((batch, 6, 3), -1, dtype=torch.int32, device=dev))
+        if want_leak:
+            out["leak"] = torch.zeros((batch, 6), dtype=torch.float64, device=dev)
+            out["leak_where"] = torch.full((batch, 6, 3), -1, dtype=torch.int32, device=dev)
+        _check(lib().ntg_batch_verify(self.h, batch, _ptr(x), _ptr(out["err"]), _ptr(out["where"]), _ptr(out.get("leak")), _ptr(out.get("leak_where")),
+                                      self._stream()))
         return out
 
     def kkt(self, x, lower, upper, clambda, want_residual: bool = False):

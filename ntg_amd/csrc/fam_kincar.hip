@@ -3,6 +3,7 @@
 #include "solve_impl.hpp"
 #include "check.hpp"
 #include "cost.hpp"
+#include "verify.hpp"
 
 // fam_kincar_chm.hip: 2 or 6 outputs of order 6 whose cost active variables are the second derivative of every output
 hipError_t ntg_launch_eval_kincar_chm(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a);
@@ -45,6 +46,11 @@ static hipError_t fam_launch_cost(const NtgDims &D, const NtgTables &T, const Co
 {
 	return launch_cost<NTG_FAM_KINCAR, 6, 18, NTG_MAX_NZ>(D, T, a);
 }
+// the derivative audit at the breakpoints (verify.hpp): the same instances
+static hipError_t fam_launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a)
+{
+	return launch_verify<NTG_FAM_KINCAR, 6, 18, NTG_MAX_NZ>(D, T, a);
+}
 
 // the family on the host (family_module.hpp): its shape rule, and its descriptor from Family<>'s constants.  Host pass only: the device
 // pass would emit the constant object into the device code as well.
@@ -53,5 +59,5 @@ static const char *shape_rule(const ntg_spec &s)
 {
 	return s.nnlic + s.nnltc * s.nbps + s.nnlfc > 0 ? "family has no nonlinear constraints" : nullptr;
 }
-extern const NtgFamily ntg_fam_kincar = ntg_builtin_family<NTG_FAM_KINCAR>("kincar", 0, shape_rule, fam_launch_eval, fam_launch_sqp, fam_launch_check, fam_launch_cost, true);
+extern const NtgFamily ntg_fam_kincar = ntg_builtin_family<NTG_FAM_KINCAR>("kincar", 0, shape_rule, fam_launch_eval, fam_launch_sqp, fam_launch_check, fam_launch_cost, fam_launch_verify, true);
 #endif

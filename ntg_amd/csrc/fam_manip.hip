@@ -3,6 +3,7 @@
 #include "solve_impl.hpp"
 #include "check.hpp"
 #include "cost.hpp"
+#include "verify.hpp"
 
 // config E: 12 outputs, order 6 (2196 coefficients, 301 breakpoints): 512 lanes, five coefficients per lane
 static hipError_t fam_launch_eval(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
@@ -48,6 +49,11 @@ static hipError_t fam_launch_cost(const NtgDims &D, const NtgTables &T, const Co
 {
 	return launch_cost<NTG_FAM_MANIP, 48>(D, T, a);
 }
+// the derivative audit at the breakpoints (verify.hpp): the same instances
+static hipError_t fam_launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a)
+{
+	return launch_verify<NTG_FAM_MANIP, 48>(D, T, a);
+}
 
 // the family on the host (family_module.hpp): its shape rule, and its descriptor from Family<>'s constants.  Host pass only: the device
 // pass would emit the constant object into the device code as well.
@@ -56,5 +62,5 @@ static const char *shape_rule(const ntg_spec &s)
 {
 	return s.nout % 3 || s.nnlic || s.nnlfc || s.nnltc > s.nout / 3 ? "manipulator family: 3 outputs per arm, at most one trajectory constraint per arm" : nullptr;
 }
-extern const NtgFamily ntg_fam_manip = ntg_builtin_family<NTG_FAM_MANIP>("manip", 0, shape_rule, fam_launch_eval, fam_launch_sqp, fam_launch_check, fam_launch_cost);
+extern const NtgFamily ntg_fam_manip = ntg_builtin_family<NTG_FAM_MANIP>("manip", 0, shape_rule, fam_launch_eval, fam_launch_sqp, fam_launch_check, fam_launch_cost, fam_launch_verify);
 #endif

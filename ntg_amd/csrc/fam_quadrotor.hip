@@ -3,6 +3,7 @@
 #include "solve_impl.hpp"
 #include "check.hpp"
 #include "cost.hpp"
+#include "verify.hpp"
 
 // config D: 4 outputs, order 8, maxderiv 5 (656 coefficients, 201 breakpoints): 256 lanes, three coefficients per lane
 static hipError_t fam_launch_eval(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
@@ -41,6 +42,11 @@ static hipError_t fam_launch_cost(const NtgDims &D, const NtgTables &T, const Co
 {
 	return launch_cost<NTG_FAM_QUADROTOR, 20, NTG_MAX_NZ>(D, T, a);
 }
+// the derivative audit at the breakpoints (verify.hpp): the same instances
+static hipError_t fam_launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a)
+{
+	return launch_verify<NTG_FAM_QUADROTOR, 20, NTG_MAX_NZ>(D, T, a);
+}
 
 // the family on the host (family_module.hpp): its shape rule, and its descriptor from Family<>'s constants.  (x, y, z) couple through thrust and
 // speed; the yaw output appears in no row: the one family whose plans have a free output (free_outputs_ok).  Host pass only: the device
@@ -50,5 +56,5 @@ static const char *shape_rule(const ntg_spec &s)
 {
 	return s.nout != 4 || s.nnlic || s.nnlfc || s.nnltc > 2 ? "quadrotor family: 4 outputs, at most two trajectory constraints" : nullptr;
 }
-extern const NtgFamily ntg_fam_quadrotor = ntg_builtin_family<NTG_FAM_QUADROTOR>("quadrotor", 4, shape_rule, fam_launch_eval, fam_launch_sqp, fam_launch_check, fam_launch_cost, false, true);
+extern const NtgFamily ntg_fam_quadrotor = ntg_builtin_family<NTG_FAM_QUADROTOR>("quadrotor", 4, shape_rule, fam_launch_eval, fam_launch_sqp, fam_launch_check, fam_launch_cost, fam_launch_verify, false, true);
 #endif

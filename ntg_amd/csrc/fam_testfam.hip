@@ -3,6 +3,7 @@
 #include "solve_impl.hpp"
 #include "check.hpp"
 #include "cost.hpp"
+#include "verify.hpp"
 
 static hipError_t fam_launch_eval(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
 {
@@ -32,6 +33,11 @@ static hipError_t fam_launch_cost(const NtgDims &D, const NtgTables &T, const Co
 {
 	return launch_cost<NTG_FAM_TESTFAM, 9, NTG_MAX_NZ>(D, T, a);
 }
+// the derivative audit at the breakpoints (verify.hpp): the same instances
+static hipError_t fam_launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a)
+{
+	return launch_verify<NTG_FAM_TESTFAM, 9, NTG_MAX_NZ>(D, T, a);
+}
 
 // the family on the host (family_module.hpp): its shape rule, and its descriptor from Family<>'s constants.  Host pass only: the device
 // pass would emit the constant object into the device code as well.
@@ -40,5 +46,5 @@ static const char *shape_rule(const ntg_spec &s)
 {
 	return s.nnlic > 1 || s.nnltc > 2 || s.nnlfc > 1 ? "testfam has 1/2/1 nonlinear constraints" : nullptr;
 }
-extern const NtgFamily ntg_fam_testfam = ntg_builtin_family<NTG_FAM_TESTFAM>("testfam", 0, shape_rule, fam_launch_eval, fam_launch_sqp, fam_launch_check, fam_launch_cost);
+extern const NtgFamily ntg_fam_testfam = ntg_builtin_family<NTG_FAM_TESTFAM>("testfam", 0, shape_rule, fam_launch_eval, fam_launch_sqp, fam_launch_check, fam_launch_cost, fam_launch_verify);
 #endif

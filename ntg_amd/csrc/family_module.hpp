@@ -20,6 +20,7 @@ typedef hipError_t (*ntg_module_eval_fn)(const NtgDims &, const NtgTables &, con
 typedef hipError_t (*ntg_module_sqp_fn)(const NtgDims &, const NtgTables &, const SmemLayout &, const SolveParams &, const SqpArgs &);
 typedef hipError_t (*ntg_module_check_fn)(const NtgDims &, const NtgTables &, const CheckArgs &);
 typedef hipError_t (*ntg_module_cost_fn)(const NtgDims &, const NtgTables &, const CostArgs &);
+typedef hipError_t (*ntg_module_verify_fn)(const NtgDims &, const NtgTables &, const VerifyArgs &);
 
 struct ntg_family_module_desc {
 	unsigned long long abi;   // NTG_AMD_ABI the module was compiled with (first member in every version of the descriptor)
@@ -35,6 +36,8 @@ struct ntg_family_module_desc {
 	ntg_module_check_fn launch_check;   // the module's check_kernel instance (ntg_batch_check)
 	int sizeof_cost_args;
 	ntg_module_cost_fn launch_cost;     // the module's cost_kernel instance (ntg_batch_cost)
+	int sizeof_verify_args;
+	ntg_module_verify_fn launch_verify; // the module's verify_kernel instance (ntg_batch_verify)
 };
 typedef const ntg_family_module_desc *(*ntg_family_module_entry_fn)(void);
 
@@ -58,6 +61,7 @@ struct NtgFamily {
 	ntg_module_sqp_fn launch_sqp;
 	ntg_module_check_fn launch_check;
 	ntg_module_cost_fn launch_cost;
+	ntg_module_verify_fn launch_verify;
 };
 
 // the registry (family_registry.cpp): ids 0 .. of the built-in families, ids >= NTG_FAM_MODULE_BASE of loaded modules; nullptr for any

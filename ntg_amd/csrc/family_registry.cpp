@@ -86,14 +86,15 @@ extern "C" int ntg_family_load(const char *path, int *family)
 	if (d->sizeof_sqp_args != (int)sizeof(SqpArgs)) return size_mismatch(rp, "SqpArgs", d->sizeof_sqp_args, (int)sizeof(SqpArgs));
 	if (d->sizeof_check_args != (int)sizeof(CheckArgs)) return size_mismatch(rp, "CheckArgs", d->sizeof_check_args, (int)sizeof(CheckArgs));
 	if (d->sizeof_cost_args != (int)sizeof(CostArgs)) return size_mismatch(rp, "CostArgs", d->sizeof_cost_args, (int)sizeof(CostArgs));
-	if (!d->name || !d->launch_eval || !d->launch_sqp || !d->launch_check || !d->launch_cost || d->dm < 1 || d->dm > NTG_MAX_ORDER || d->nnlic < 0 || d->nnltc < 0 || d->nnlfc < 0 ||
+	if (d->sizeof_verify_args != (int)sizeof(VerifyArgs)) return size_mismatch(rp, "VerifyArgs", d->sizeof_verify_args, (int)sizeof(VerifyArgs));
+	if (!d->name || !d->launch_eval || !d->launch_sqp || !d->launch_check || !d->launch_cost || !d->launch_verify || d->dm < 1 || d->dm > NTG_MAX_ORDER || d->nnlic < 0 || d->nnltc < 0 || d->nnlfc < 0 ||
 	    d->nout < 0 || d->nout > NTG_MAX_OUT || d->nparam < 0 || d->nparam_bp < 0)
 		return ntg_fail(NTG_E_BADARG, "family module " + rp + ": malformed descriptor");
 	NtgFamily &f = g_wrapped[g_count];
 	f = NtgFamily{};   // no coupling blocks, no shape rule of its own, no kincar flag
 	f.name = d->name; f.dm = d->dm; f.nnlic = d->nnlic; f.nnltc = d->nnltc; f.nnlfc = d->nnlfc; f.nout = d->nout; f.cg = 1;
 	f.nparam = d->nparam; f.nparam_bp = d->nparam_bp;
-	f.launch_eval = d->launch_eval; f.launch_sqp = d->launch_sqp; f.launch_check = d->launch_check; f.launch_cost = d->launch_cost;
+	f.launch_eval = d->launch_eval; f.launch_sqp = d->launch_sqp; f.launch_check = d->launch_check; f.launch_cost = d->launch_cost; f.launch_verify = d->launch_verify;
 	g_path[g_count] = rp;
 	g_module[g_count].store(&f, std::memory_order_release);
 	*family = NTG_FAM_MODULE_BASE + g_count++;

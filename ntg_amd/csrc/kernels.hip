@@ -14,6 +14,8 @@
 //                   last step of its reduction, check_final_kernel, is here)
 //   cost_kernel     running cost of solved problems at arbitrary times, weighted sum per problem
 //                   (cost.hpp; the sum over the time tiles, cost_final_kernel, is here)
+//   verify_kernel   a family's analytic derivatives against central differences at the breakpoints
+//                   (verify.hpp; the maximum over the breakpoint tiles, verify_final_kernel, is here)
 //   kkt_kernel      first-order optimality residuals of a batch on the banded Jacobian (kkt.hpp)
 //
 // Mapping to CDNA4: one workgroup per problem; breakpoints (then coefficients) across the
@@ -27,6 +29,7 @@
 #include "family_module.hpp"
 #include "refine.hpp"
 #include "kkt.hpp"
+#include "verify.hpp"
 
 
 // ------------------------------------------------------------------------------------------
@@ -496,6 +499,41 @@ __global__ void cost_final_kernel(int batch, int ntiles, const double *__restric
 hipError_t ntg_launch_cost_final(int batch, int ntiles, const double *pcost, double *cost, hipStream_t st)
 {
 	hipLaunchKernelGGL(cost_final_kernel, dim3((batch + 127) / 128), dim3(128), 0, st, batch, ntiles, pcost, cost);
+	return hipGetLastError();
+}
+
+// ntg_batch_verify (verify.hpp): the family's verify_kernel instance ...
+hipError_t ntg_launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a)
+{
+	const NtgFamily *f = ntg_family(D.family);
+	return f ? f->launch_verify(D, T, a) : hipErrorInvalidValue;
+}
+
+// ... and its last step: the maximum over a problem's breakpoint tiles (verify_kernel left one (value, key) pair per tile, slot and kind),
+// tiles in order under verify_take's total order, and the key taken apart into {function, breakpoint, flag entry}.  One thread per problem
+// and (slot, kind); kind 0 goes to err / where, kind 1 to leak / leak_where, each of which may be null.
+__global__ void verify_final_kernel(int batch, int ntiles, int nbps, int nz, const double *__restrict__ pval, const long long *__restrict__ pkey,
+                                    double *__restrict__ err, int *__restrict__ where, double *__restrict__ leak, int *__restrict__ leak_where)
+{
+	constexpr int NQ = 2 * NTG_VERIFY_NSLOT;
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= batch * NQ) return;
+	const int b = i / NQ, q = i - b * NQ, slot = q >> 1, kind = q & 1;
+	double bv = pval[(size_t)b * ntiles * NQ + q]; long long bk = pkey[(size_t)b * ntiles * NQ + q];
+	for (int t = 1; t < ntiles; t++) verify_take(bv, bk, pval[((size_t)b * ntiles + t) * NQ + q], pkey[((size_t)b * ntiles + t) * NQ + q]);
+	double *ov = kind ? leak : err; int *ow = kind ? leak_where : where;
+	const size_t o = (size_t)b * NTG_VERIFY_NSLOT + slot;
+	if (ov) ov[o] = bv;
+	if (ow) {
+		const long long pt = bk >= 0 ? bk / nz : -1;
+		ow[3 * o] = bk >= 0 ? (int)(pt / nbps) : -1; ow[3 * o + 1] = bk >= 0 ? (int)(pt % nbps) : -1; ow[3 * o + 2] = bk >= 0 ? (int)(bk % nz) : -1;
+	}
+}
+hipError_t ntg_launch_verify_final(int batch, int ntiles, int nbps, int nz, const double *pval, const long long *pkey, double *err, int *where, double *leak,
+                                   int *leak_where, hipStream_t st)
+{
+	const long long n = (long long)batch * 2 * NTG_VERIFY_NSLOT;
+	hipLaunchKernelGGL(verify_final_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, batch, ntiles, nbps, nz, pval, pkey, err, where, leak, leak_where);
 	return hipGetLastError();
 }
 

@@ -187,6 +187,17 @@ struct CostArgs {
 	double *vals, *pcost;
 };
 
+// verify_kernel (verify.hpp): the family's six callbacks against central differences at the breakpoints.  t: the tile fields of CheckArgs as
+// for cost_kernel, filled by the same walk with the plan's (or every problem's own) breakpoints as the times.  pval / pkey
+// [batch][ntiles][2 NTG_VERIFY_NSLOT]: per tile and slot the maxima (err, leak) and their keys (function * nbps + breakpoint) * nz + entry, -1: none.
+// LDS: that of check_kernel (ntg_check_lds) plus a static part of its own: the waves' maxima and keys, a family's parameter slot.
+#define NTG_VERIFY_LDS_STATIC 512
+#define NTG_VERIFY_LDS_MAX (160 * 1024 - NTG_VERIFY_LDS_STATIC)
+struct VerifyArgs {
+	CheckArgs t;
+	double *pval; long long *pkey;
+};
+
 // kkt_kernel (kkt.hpp): problems [b0, b0 + nb) of the batch, grid persistent workgroups.  x, lam ([batch][nC + nclin + ncnln], the first nC
 // entries of a problem never read), res ([batch][NTG_KKT_NRES]) and r ([batch][nC]) are the caller's, indexed by the problem of the batch;
 // either of res, r may be null.  g, c, jband (ntg_launch_eval's output) and bl, bu (ntg_launch_bounds') are the chunk's scratch, indexed by

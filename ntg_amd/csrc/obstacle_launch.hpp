@@ -5,6 +5,7 @@
 #include "solve_impl.hpp"
 #include "check.hpp"
 #include "cost.hpp"
+#include "verify.hpp"
 
 template <int FAM>
 static hipError_t obstacle_launch_eval(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)
@@ -46,4 +47,11 @@ template <int FAM>
 static hipError_t obstacle_launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a)
 {
 	return launch_cost<FAM, 6>(D, T, a);
+}
+
+// the derivative audit at the breakpoints (verify.hpp): the same instance
+template <int FAM>
+static hipError_t obstacle_launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a)
+{
+	return launch_verify<FAM, 6>(D, T, a);
 }

@@ -71,6 +71,11 @@ hipError_t ntg_launch_check_final(int batch, int ntiles, int ntimes, const doubl
 // running cost at arbitrary times (cost.hpp): the family's cost_kernel instance, launched like check_kernel, then the sum over a problem's time tiles
 hipError_t ntg_launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a);
 hipError_t ntg_launch_cost_final(int batch, int ntiles, const double *pcost, double *cost, hipStream_t st);
+// a family's derivatives against central differences at the breakpoints (verify.hpp): the family's verify_kernel instance, launched like
+// check_kernel with the breakpoints as the times, then the maximum over a problem's tiles and the keys taken apart
+hipError_t ntg_launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a);
+hipError_t ntg_launch_verify_final(int batch, int ntiles, int nbps, int nz, const double *pval, const long long *pkey, double *err, int *where, double *leak,
+                                   int *leak_where, hipStream_t st);
 // first-order optimality residuals (kkt.hpp): one chunk of problems, after ntg_launch_eval (mode 2) and ntg_launch_bounds filled its scratch
 hipError_t ntg_launch_kkt(const NtgDims &D, const NtgTables &T, const KktArgs &a);
 hipError_t ntg_launch_kincar_reverse(long long nsamp, int nz, int ncars, double wheelbase, int reverse_gear, const double *z, double *out, hipStream_t st);

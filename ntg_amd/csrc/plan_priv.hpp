@@ -6,6 +6,7 @@
 //   plan_grids.cpp  per-problem grids (ntg_plan_set_grids) and per-problem family parameters
 //   plan_kkt.cpp    ntg_batch_kkt: first-order optimality residuals of a batch
 //   plan_cost.cpp   ntg_batch_cost: the running cost of a batch at arbitrary times under a quadrature
+//   plan_verify.cpp ntg_batch_verify: a family's analytic derivatives against central differences at the breakpoints
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
