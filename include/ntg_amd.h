@@ -30,6 +30,8 @@
  *                        left on), for a batch: the family's analytic derivatives against central differences, plus the active-variable lists
  *   ntg_batch_refine     nothing in the reference carries a spline to other knots; the nearest is SplineInterp (colloc.c:449-484), which the
  *                        result reproduces: the refined coefficients describe the same function
+ *   ntg_batch_envelope   nothing in the reference bounds a trajectory between samples; its only dense output is SplineInterp (colloc.c:449-484),
+ *                        point by point, which the result encloses: bounds of every flag entry and linear trajectory row over whole pieces of time
  *   ntg_batch_kincar_reverse  examples/kincar.c:68-92 kincar_flat_reverse (the example's flat-to-state map), for a batch
  *   ntg(), npsoloption(), linspace(), SplineInterp(), matrix helpers: see include/ntg.h
  */
@@ -370,6 +372,55 @@ int ntg_batch_kkt(const ntg_plan *p, int batch, const double *d_x, const double 
  * on per-problem grids; host-callback plans; a pair whose weight tables exceed 64 KiB of LDS.  batch <= 0 returns 0. */
 int ntg_batch_refine(const ntg_plan *from, const ntg_plan *to, int batch,
                      const double *d_x_from, double *d_x_to, void *stream);
+
+/* Certify a trajectory OVER TIME: bounds of every flag entry and of every linear trajectory row that hold at every time of the horizon,
+ * not at sampled times.  ntg_batch_check tells what the rows are at the times passed in; this call makes the statement "for all t" for the
+ * rows a guarantee is cheap for -- the linear rows ltc on flat outputs and their derivatives (a corridor ceiling, a velocity or acceleration
+ * limit, declared as ranges through ntg_spec.lin_ineq) -- because the trajectory is a B-spline: on each knot interval every flag entry
+ * D^r z_o is a polynomial, its Bezier control polygon on that interval encloses it, and halving the interval shrinks the enclosure
+ * quadratically.  No family callback is involved: every built-in family and every loaded module alike, per-breakpoint-parameter families
+ * included; per-problem parameters are ignored.  d_x [batch][nC]: any coefficients.
+ * Pieces.  Output o has l_o = kninterv[o] knot intervals [a_j, b_j] (after ntg_plan_set_grids: those of the problem's own knots).  Each
+ * interval is cut into 2^nsub equal parts in the local parameter s = (t - a_j) / (b_j - a_j); piece q = (j << nsub) + i is
+ * s in [i / 2^nsub, (i + 1) / 2^nsub].  0 <= nsub <= NTG_ENVELOPE_MAX_NSUB.  npc = (max_o l_o) << nsub is the piece stride of every output.
+ * Entry envelope d_lo / d_hi [batch][nz][npc], entry iz[o] + r in the layout of ntg_batch_interp.  With k = order[o]:
+ *   1. On interval j, z_o is a polynomial of degree k - 1 in the k coefficients of that span.  Its Bezier control points on [a_j, b_j] are
+ *      the blossom of the spline at (a_j repeated k-1-i, b_j repeated i), i = 0 .. k-1 (the de Boor triangle ntg_batch_refine uses, with
+ *      these arguments).  The weights do not depend on the coefficients.
+ *   2. The control points of D^r z_o on the interval come from r rounds of beta'_i = d / (b_j - a_j) * (beta_{i+1} - beta_i), d the degree
+ *      before the round.
+ *   3. The control points on a piece come from that polygon by de Casteljau at the dyadic ends of the piece, in the local parameter: at
+ *      (i + 1) / 2^nsub keeping the left polygon, then at i / (i + 1) of what is left keeping the right one.  No knot enters this step.
+ *   lo is the minimum and hi the maximum of the piece's k - r control points.  For r >= k both are 0.  For pieces q >= l_o << nsub,
+ *   lo = +inf and hi = -inf, an empty set.  A NaN among the control points stays in both (ntg_batch_kkt's rule).
+ * Row envelope d_row_lo / d_row_hi [batch][nltc][npc] for the linear trajectory rows: row i is sum_v ltc[i][v] z_v(t).  All outputs the row
+ * names (non-zero ltc[i][v]) must belong to one basis class (same knots, order, mult, maxderiv); the row's pieces are that class's.  On a
+ * piece, each named entry's polygon is degree-elevated to the largest degree among the named entries, b'_i = i/(d+1) b_{i-1} +
+ * (1 - i/(d+1)) b_i, and the polygons are summed with the row's coefficients, v ascending; min and max of the summed polygon are the row's
+ * bounds on that piece.  This is the row's own Bezier polygon, not interval arithmetic: a row such as x' - y' whose terms cancel gets a
+ * tight bound.
+ * Certified violation.  d_viol [batch]: the largest max(l - row_lo, row_hi - u, 0) over rows and pieces, with the bounds taken from
+ * d_lower / d_upper [batch][nbounds] at the ltc columns exactly as ntg_batch_check reads them (|bound| >= NTG_INF_BOUND: absent).
+ * d_where [batch][2] = {row, piece} of that maximum; ties go to the smallest row * npc + piece; {-1, -1} where d_viol is 0.  A NaN in a
+ * row's bounds on a piece makes d_viol NaN, at the place of the first NaN in that order.  d_viol == 0 certifies, up to the rounding stated
+ * next, that every linear trajectory row holds at every time of the horizon.
+ * Rounding.  The enclosure is exact in exact arithmetic.  In double precision every control point is a chain of at most k + nsub convex
+ * combinations and r scaled differences: with S = max_i |c_{o,i}| * (2 (k-1) / h_min)^r (h_min the shortest knot interval of the output)
+ * each step loses at most a few units in the last place of S; 2^-42 * S covers the chain with a factor of ten to spare.
+ * Any output pointer may be NULL, but not all six; d_lower / d_upper are required only when d_viol or d_where is asked for.
+ * Stream ordered.  The call allocates no scratch at all (a problem is reduced inside one workgroup), so nothing grows with
+ * batch * nz * npc and nothing is left to release on any path.  No floating-point atomics: results are bit-identical from call to call
+ * and do not depend on the batch around a problem.
+ * batch <= 0 returns 0.  NTG_E_BADARG for a null plan or null d_x, nsub out of range, all outputs null, violation outputs without bounds,
+ * row or violation outputs on a plan with nltc == 0, a batch other than the per-problem grids'.  NTG_E_UNSUPPORTED for host-callback plans,
+ * for row or violation outputs when some linear trajectory row names outputs of different basis classes (the entry envelope of such a plan
+ * is still served), and for a plan whose extraction tables exceed 64 KiB of LDS (sum over basis classes of l (k^2 + 1), plus nC). */
+#define NTG_ENVELOPE_MAX_NSUB 6
+int ntg_batch_envelope(const ntg_plan *p, int batch, const double *d_x, int nsub,
+                       const double *d_lower, const double *d_upper,
+                       double *d_lo, double *d_hi,
+                       double *d_row_lo, double *d_row_hi,
+                       double *d_viol, int *d_where, void *stream);
 
 /* The flat-to-state map of the kinematic car for a whole ntg_batch_interp result (examples/kincar.c:68-92 kincar_flat_reverse,
  * called per sample by the example's output loop, kincar.c:392-406): d_z [batch][ntimes][nz] -> d_state [batch][ntimes][ncars][5] =

@@ -80,6 +80,7 @@ def lib():
         L.ntg_batch_kkt.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
         L.ntg_batch_cost.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_batch_verify.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ntg_batch_envelope.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 9
         L.ntg_batch_refine.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_plan_set_grids.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ntg_plan_clear_grids.argtypes = [C.c_void_p]
@@ -381,6 +382,39 @@ class Plan:
         _check(lib().ntg_batch_refine(self.h, to.h, batch, _ptr(x), _ptr(out), self._stream()))
         return out
 
+    def envelope(self, x, nsub: int = 0, lower=None, upper=None, want_entries: bool = True, want_rows: bool = False):
+        """Bounds of a batch of trajectories that hold at EVERY time (ntg_batch_envelope): x [batch, nC]; every knot interval is cut into
+        2^nsub pieces, npc = max(kninterv) << nsub (envelope_pieces gives their ends).  Returns a dict: lo, hi [batch, nz, npc] (the flag
+        entries, want_entries), row_lo, row_hi [batch, nltc, npc] (the linear trajectory rows, want_rows), and with bounds [batch, nbounds]
+        viol [batch] and where [batch, 2] = (row, piece) of the largest certified violation or (-1, -1).  Pieces past an output's own are
+        the empty set (lo = +inf, hi = -inf).  viol == 0 certifies every linear trajectory row over the whole horizon."""
+        import torch
+        sp = self.spec
+        dev = x.device
+        _check_tensor(x, dev); _check_tensor(lower, dev); _check_tensor(upper, dev)
+        if x.dim() != 2 or x.shape[1] != sp.nC:
+            raise NtgError(f"x must be [batch, {sp.nC}]")
+        batch = x.shape[0]
+        if (lower is None) != (upper is None):
+            raise NtgError("pass both bounds or neither")
+        if lower is not None and (lower.shape != (batch, sp.nbounds) or upper.shape != (batch, sp.nbounds)):
+            raise NtgError(f"bounds must be [{batch}, {sp.nbounds}]")
+        if not 0 <= int(nsub) <= ENVELOPE_MAX_NSUB:
+            raise NtgError(f"nsub must lie in 0 .. {ENVELOPE_MAX_NSUB} (NTG_ENVELOPE_MAX_NSUB)")
+        if (want_rows or lower is not None) and sp.nltc == 0:   # (empty row tensors would reach the library as null pointers)
+            raise NtgError("the plan has no linear trajectory rows (nltc == 0): there is no row envelope and no violation to ask for")
+        npc = max(sp.kninterv) << int(nsub)
+        out = {}
+        if want_entries:
+            out["lo"] = torch.empty((batch, sp.nz, npc), dtype=torch.float64, device=dev); out["hi"] = torch.empty_like(out["lo"])
+        if want_rows:
+            out["row_lo"] = torch.empty((batch, sp.nltc, npc), dtype=torch.float64, device=dev); out["row_hi"] = torch.empty_like(out["row_lo"])
+        if lower is not None:
+            out["viol"] = torch.zeros(batch, dtype=torch.float64, device=dev); out["where"] = torch.full((batch, 2), -1, dtype=torch.int32, device=dev)
+        _check(lib().ntg_batch_envelope(self.h, batch, _ptr(x), int(nsub), _ptr(lower), _ptr(upper), _ptr(out.get("lo")), _ptr(out.get("hi")),
+                                        _ptr(out.get("row_lo")), _ptr(out.get("row_hi")), _ptr(out.get("viol")), _ptr(out.get("where")), self._stream()))
+        return out
+
     def set_grids(self, knots, bps, with_precond: bool = True):
         """Per-problem grids: knots [batch, ninterv+1], bps [batch, nbps] (device, float64).  See ntg_plan_set_grids."""
         _check_tensor(knots, knots.device); _check_tensor(bps, bps.device)
@@ -485,6 +519,26 @@ class Plan:
                                      _ptr(out["objective"]), _ptr(out["inform"]), _ptr(out["iters"]), _ptr(out["nfev"]),
                                      _ptr(out.get("clambda")), _ptr(work), work.numel() * work.element_size(), self._stream()))
         return out
+
+
+ENVELOPE_MAX_NSUB = 6   # NTG_ENVELOPE_MAX_NSUB
+
+
+def envelope_pieces(spec_or_knots, o: int = 0, nsub: int = 0) -> np.ndarray:
+    """The ends [npc + 1] of the pieces Plan.envelope reports for output o: piece q of that output covers [ends[q], ends[q + 1]].  Takes a
+    Spec (npc = max(kninterv) << nsub; the entries past the output's own pieces are NaN) or one break sequence [l + 1] (npc = l << nsub,
+    e.g. a problem's own knots after set_grids)."""
+    if hasattr(spec_or_knots, "knots"):
+        kn = np.asarray(spec_or_knots.knots[o], dtype=np.float64); npc = max(spec_or_knots.kninterv) << nsub
+    else:
+        kn = np.asarray(spec_or_knots, dtype=np.float64); npc = (len(kn) - 1) << nsub
+    n = 1 << nsub
+    a, h = kn[:-1], np.diff(kn)
+    ends = np.full(npc + 1, np.nan)
+    own = (a[:, None] + h[:, None] * (np.arange(n)[None, :] / n)).reshape(-1)
+    ends[:own.size] = own
+    ends[own.size] = kn[-1]
+    return ends
 
 
 def load_family(path: str) -> int:

@@ -17,6 +17,8 @@
 //   verify_kernel   a family's analytic derivatives against central differences at the breakpoints
 //                   (verify.hpp; the maximum over the breakpoint tiles, verify_final_kernel, is here)
 //   kkt_kernel      first-order optimality residuals of a batch on the banded Jacobian (kkt.hpp)
+//   envelope_*      bounds of every flag entry and linear trajectory row over whole pieces of the
+//                   knot intervals, from the Bezier control polygons (envelope.hpp)
 //
 // Mapping to CDNA4: one workgroup per problem; breakpoints (then coefficients) across the
 // lanes; basis tables, knots/breakpoints and the coefficient vector staged in LDS; the only
@@ -28,6 +30,7 @@
 #include "solve_impl.hpp"
 #include "family_module.hpp"
 #include "refine.hpp"
+#include "envelope.hpp"
 #include "kkt.hpp"
 #include "verify.hpp"
 
@@ -614,6 +617,29 @@ hipError_t ntg_launch_refine(const RefineArgs &A, int pp, int ncu, hipStream_t s
 		hipLaunchKernelGGL(refine_shared_kernel<NTG_REFINE_NT>, dim3(grid), dim3(NTG_REFINE_NT), lds, st, A);
 	}
 	return hipGetLastError();
+}
+
+// ntg_batch_envelope (envelope.hpp): the instance with the smallest private polygons that hold the plan's largest order.
+// hipErrorInvalidValue: the tables exceed the LDS.
+template <int KM>
+static hipError_t launch_envelope(const EnvArgs &A, int ncu, size_t lds, hipStream_t st)
+{
+	if (A.pp) {
+		const int groups = (A.batch + NTG_ENVELOPE_NT / 64 - 1) / (NTG_ENVELOPE_NT / 64);
+		hipLaunchKernelGGL((envelope_pp_kernel<NTG_ENVELOPE_NT, KM>), dim3(std::min(groups, 8 * ncu)), dim3(NTG_ENVELOPE_NT), lds, st, A);
+	} else {
+		// persistent workgroups: each builds its weights once, so each should stream several problems; no more than fill the device
+		const int grid = std::max(1, std::min((A.batch + 3) / 4, 8 * ncu));
+		hipLaunchKernelGGL((envelope_shared_kernel<NTG_ENVELOPE_NT, KM>), dim3(grid), dim3(NTG_ENVELOPE_NT), lds, st, A);
+	}
+	return hipGetLastError();
+}
+hipError_t ntg_launch_envelope(const EnvArgs &A, int ncu, hipStream_t st)
+{
+	const size_t lds = ntg_envelope_lds(A);
+	if (lds > NTG_ENVELOPE_LDS_MAX || A.kmax > NTG_MAX_ORDER) return hipErrorInvalidValue;   // (ntg_batch_envelope refuses such a plan before it gets here)
+	if (A.batch <= 0) return hipSuccess;
+	return A.kmax <= 6 ? launch_envelope<6>(A, ncu, lds, st) : launch_envelope<NTG_MAX_ORDER>(A, ncu, lds, st);
 }
 
 // Flat flag -> state and input of the kinematic car, the map of examples/kincar.c:68-92 (kincar_flat_reverse), for every car

@@ -213,3 +213,24 @@ struct KktArgs {
 // (the waves' reduction slots)
 static inline size_t ntg_kkt_lds(const NtgDims &D) { return (size_t)2 * ((D.nC + 1) & ~1) * 8 + (size_t)D.nclass * D.P * 4; }
 #define NTG_KKT_LDS_MAX (160 * 1024 - 256)
+
+// envelope kernels (envelope.hpp): certified bounds of every flag entry and every linear trajectory row on the pieces of the knot intervals.
+// c[cl]: a basis class, its extraction weights [l][k][k] at eoff and interval lengths [l] at hoff in the LDS table of ne doubles.  knots[cl]:
+// the class's break sequence (shared grids); knots[0] = [batch][l + 1] on per-problem grids (pp = 1, one class).  Outputs as documented at
+// ntg_batch_envelope, any may be null; ltc [nltc][nz]; lower / upper [batch][nbounds], the linear trajectory rows' slots start at slot0.
+#define NTG_ENVELOPE_NT 256
+#define NTG_ENVELOPE_LDS_MAX (64 * 1024)
+struct EnvClass { int k, m, l, eoff, hoff; };
+struct EnvArgs {
+	int nout, nz, nC, nclass, batch, nsub, npc, nltc, nbounds, slot0, pp, ne, lmax, kmax;
+	int cls[NTG_MAX_OUT], d[NTG_MAX_OUT], iC[NTG_MAX_OUT], iz[NTG_MAX_OUT];
+	EnvClass c[NTG_MAX_OUT];
+	const double *knots[NTG_MAX_OUT];
+	const double *x, *ltc, *lower, *upper;
+	double *lo, *hi, *row_lo, *row_hi, *viol; int *where;
+};
+// dynamic LDS: the tables, one coefficient row and one break sequence -- of the workgroup (shared grids) or of each of its waves
+static inline size_t ntg_envelope_lds(const EnvArgs &A)
+{
+	return (size_t)(A.pp ? NTG_ENVELOPE_NT / 64 : 1) * (size_t)(A.ne + A.nC + A.lmax + 1) * 8;
+}

@@ -7,6 +7,7 @@
 //   plan_kkt.cpp    ntg_batch_kkt: first-order optimality residuals of a batch
 //   plan_cost.cpp   ntg_batch_cost: the running cost of a batch at arbitrary times under a quadrature
 //   plan_verify.cpp ntg_batch_verify: a family's analytic derivatives against central differences at the breakpoints
+//   plan_envelope.cpp ntg_batch_envelope: certified bounds of the flag entries and linear trajectory rows over the whole horizon
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
