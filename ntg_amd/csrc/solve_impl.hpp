@@ -95,13 +95,21 @@ __device__ __forceinline__ double dpp_mov(double v, double old)
 	const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(v), CTRL, 0xf, BANK, false);
 	return __hiloint2double(hi, lo);
 }
+// a permutation inside a row (every lane has a source): no "old" operand, so no register is zeroed in front of the move
+template <int CTRL>
+__device__ __forceinline__ double dpp_perm(double v)
+{
+	const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, true);
+	const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, true);
+	return __hiloint2double(hi, lo);
+}
 template <int BIT>
 __device__ __forceinline__ double lane_xchg(double v)
 {
-	if (BIT == 1) return dpp_mov<0xB1, 0xf>(v, 0.0);                       // quad_perm [1,0,3,2]
-	if (BIT == 2) return dpp_mov<0x4E, 0xf>(v, 0.0);                       // quad_perm [2,3,0,1]
+	if (BIT == 1) return dpp_perm<0xB1>(v);                                // quad_perm [1,0,3,2]
+	if (BIT == 2) return dpp_perm<0x4E>(v);                                // quad_perm [2,3,0,1]
 	if (BIT == 4) return dpp_mov<0x114, 0xA>(v, dpp_mov<0x104, 0x5>(v, 0.0)); // row_shl:4 into banks 0,2 ; row_shr:4 into banks 1,3
-	if (BIT == 8) return dpp_mov<0x128, 0xf>(v, 0.0);                      // row_ror:8
+	if (BIT == 8) return dpp_perm<0x128>(v);                               // row_ror:8
 	if (BIT == 16) {
 		const int lo = __builtin_amdgcn_ds_swizzle(__double2loint(v), 0x401F), hi = __builtin_amdgcn_ds_swizzle(__double2hiint(v), 0x401F);
 		return __hiloint2double(hi, lo);

@@ -38,17 +38,19 @@ __device__ __forceinline__ void static_while(C &&c, F &&f)
 	}
 }
 
-// value of the previous / next lane of the wavefront (DPP wave_shr:1 / wave_shl:1; lane 0 / lane 63 receive 0)
+// value of the previous / next lane of the wavefront (DPP wave_shr:1 / wave_shl:1; lane 0 / lane 63 receive 0).  bound_ctrl: a lane whose
+// source is out of range (or disabled) reads 0 from the DPP unit itself -- the same value in the same lanes as an "old" operand of 0, without
+// the v_mov_b32 v, 0 that operand costs in front of every shift (solve_impl.hpp: dpp_rot)
 __device__ __forceinline__ double from_prev(double v)
 {
-	const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x138, 0xf, 0xf, false);
-	const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x138, 0xf, 0xf, false);
+	const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x138, 0xf, 0xf, true);
+	const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x138, 0xf, 0xf, true);
 	return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ double from_next(double v)
 {
-	const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x130, 0xf, 0xf, false);
-	const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x130, 0xf, 0xf, false);
+	const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x130, 0xf, 0xf, true);
+	const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x130, 0xf, 0xf, true);
 	return __hiloint2double(hi, lo);
 }
 

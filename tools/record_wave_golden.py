@@ -1,9 +1,10 @@
-"""Record tests/golden/wave_instances.npz (tests/test_gpu_wave_golden_instances.py) with the library named by NTG_AMD_LIB -- meant
-for the library of the commit BEFORE a change that must not move a bit.
+"""Record tests/golden/wave_instances.npz (tests/test_gpu_wave_golden_instances.py) or, with --restarts, tests/golden/wave_restarts.npz
+(tests/test_gpu_wave_golden_restarts.py) with the library named by NTG_AMD_LIB -- meant for the library of the commit BEFORE a change
+that must not move a bit.
 
   python tools/record_wave_golden.py --audit LIB     where LIB was built (no GPU): audit the device assembly of its wave kernels
                                                      (ntg_amd/isa_audit.py, ntg_amd/call_audit.py) and write LIB.audited
-  NTG_AMD_LIB=LIB python tools/record_wave_golden.py [OUT.npz]     on the GPU: refuses a library without a matching LIB.audited
+  NTG_AMD_LIB=LIB python tools/record_wave_golden.py [--restarts] [OUT.npz]     on the GPU: refuses a library without a matching LIB.audited
 
 A library whose wave kernels failed the audit may corrupt the chain or fault on the GPU: it is never run."""
 import hashlib
@@ -58,10 +59,16 @@ def main():
     if not ok:
         sys.exit("%s has no matching .audited stamp (run --audit where it was built): not run" % lib)
     import numpy as np
-    import wave_golden_cases as wc
+    args = [a for a in sys.argv[1:] if a != "--restarts"]
+    if "--restarts" in sys.argv[1:]:
+        import wave_golden_restart_cases as wc
+        default = "wave_restarts.npz"
+    else:
+        import wave_golden_cases as wc
+        default = "wave_instances.npz"
     from ntg_amd import api
     assert os.path.abspath(api.LIB_PATH) == lib
-    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "tests", "golden", "wave_instances.npz")
+    out = args[0] if args else os.path.join(ROOT, "tests", "golden", default)
     arrays = {}
     for name in wc.CASES:
         res = wc.run_case(name)
