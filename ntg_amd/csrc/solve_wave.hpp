@@ -124,7 +124,7 @@ struct WaveArgs {
 	const double *lower, *upper;
 	double *xio, *objective;
 	int *inform, *iters, *nfev;
-	double *clambda, *hist;   // hist: HBM tier of the chain, [wave][slot - on-chip slots][EPL][64]
+	double *clambda, *hist;   // hist: HBM tier of the chain, [wave][slot - on-chip slots][EPL][64] ([EPL/2][64][2] where H16, see slot_store)
 	unsigned int *counter;    // problem queue (zeroed before the launch)
 	int hbm_slots;            // slots per wave in hist
 };
@@ -453,6 +453,11 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 	// (Tried: the register tier as a plain local array with static indices, left to the register allocator.  It first sank the NREG
 	// conditional stores into one store through a pointer phi -- the whole tier went to scratch -- and, with that prevented, still spilled
 	// 150-390 registers to scratch at 16-21 slots.  Hence the accumulator registers by hand, and an ISA audit in the build.)
+	// HBM tier, one wave per SIMD and an even number of doubles per lane (H16): a slot is stored as [EPL/2][lane][2] -- a lane's pair (e, e + 1)
+	// adjacent, lanes contiguous -- so a slot moves in EPL/2 16-byte requests per lane (1 KB contiguous per wave each) instead of EPL 8-byte
+	// ones: half the VMEM instructions and address registers of the tail's rounds.  The tier is workspace private to a launch; nothing
+	// outside slot_store / hload sees the layout.  Odd EPL (two outputs) and the two-waves-per-SIMD instances keep [EPL][lane].
+	constexpr bool PIPE = MINW == 1, H16 = PIPE && EPL % 2 == 0;
 	auto slot_store = [&](int j, const double (&v)[EPL]) {
 		if (j < NREG) {
 			static_for<0, NREG>([&](auto Jc) __attribute__((always_inline)) {
@@ -464,6 +469,10 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 		} else if (j < NREG + NLDS) {
 #pragma unroll
 			for (int e = 0; e < EPL; e++) s_hl[((size_t)(j - NREG) * 64 + lane) * EPL + e] = v[e];
+		} else if constexpr (H16) {
+			double2 *p = (double2 *)(hbm + (size_t)(j - NREG - NLDS) * EPL * 64) + lane;
+#pragma unroll
+			for (int e = 0; e < EPL / 2; e++) p[e * 64] = double2{v[2 * e], v[2 * e + 1]};
 		} else {
 #pragma unroll
 			for (int e = 0; e < EPL; e++) hbm[((size_t)(j - NREG - NLDS) * EPL + e) * 64 + lane] = v[e];
@@ -507,7 +516,6 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 	// LB, RK: the most the register allocator takes without moving into the accumulator range or spilling more scalars (ntg_amd/isa_audit.py
 	// and tests/test_wave_sweep_isa.py hold it there; the per-problem-grid instances have no register to spare for RK).  The instances with
 	// two waves per SIMD keep the plain loops: they have no spare registers, and the other wave hides the latency.
-	constexpr bool PIPE = MINW == 1;
 	constexpr int LB = 2, RK = (PIPE && NREG > 0 && !PPG) ? (4 < NREG ? 4 : NREG) : 0;
 	auto sweep = [&](int ns, const double (&v)[EPL], double (&tv)[EPL]) {
 		if (ns < 2) return;   // a chain of one vector carries no update yet
@@ -516,9 +524,14 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 		auto hload = [&](int base, double (&h)[HG][EPL]) {   // unconditional: past the end the newest vector again (masked where it is used)
 #pragma unroll
 			for (int g2 = 0; g2 < HG; g2++) {
-				const double *p = hbm + (size_t)(min(base + g2, ns - 1) - H0) * EPL * 64 + lane;
+				const double *p = hbm + (size_t)(min(base + g2, ns - 1) - H0) * EPL * 64;
+				if constexpr (H16) {
 #pragma unroll
-				for (int e = 0; e < EPL; e++) h[g2][e] = p[e * 64];
+					for (int e = 0; e < EPL / 2; e++) { const double2 t2 = ((const double2 *)p)[e * 64 + lane]; h[g2][2 * e] = t2.x; h[g2][2 * e + 1] = t2.y; }
+				} else {
+#pragma unroll
+					for (int e = 0; e < EPL; e++) h[g2][e] = p[e * 64 + lane];
+				}
 			}
 		};
 		if (ns > H0) hload(H0, hA);

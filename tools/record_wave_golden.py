@@ -1,10 +1,11 @@
-"""Record tests/golden/wave_instances.npz (tests/test_gpu_wave_golden_instances.py) or, with --restarts, tests/golden/wave_restarts.npz
-(tests/test_gpu_wave_golden_restarts.py) with the library named by NTG_AMD_LIB -- meant for the library of the commit BEFORE a change
+"""Record tests/golden/wave_instances.npz (tests/test_gpu_wave_golden_instances.py), with --restarts tests/golden/wave_restarts.npz
+(tests/test_gpu_wave_golden_restarts.py) or with --tail tests/golden/wave_tail.npz (tests/test_gpu_wave_golden_tail.py) with the library
+named by NTG_AMD_LIB -- meant for the library of the commit BEFORE a change
 that must not move a bit.
 
   python tools/record_wave_golden.py --audit LIB     where LIB was built (no GPU): audit the device assembly of its wave kernels
                                                      (ntg_amd/isa_audit.py, ntg_amd/call_audit.py) and write LIB.audited
-  NTG_AMD_LIB=LIB python tools/record_wave_golden.py [--restarts] [OUT.npz]     on the GPU: refuses a library without a matching LIB.audited
+  NTG_AMD_LIB=LIB python tools/record_wave_golden.py [--restarts | --tail] [OUT.npz]     on the GPU: refuses a library without a matching LIB.audited
 
 A library whose wave kernels failed the audit may corrupt the chain or fault on the GPU: it is never run."""
 import hashlib
@@ -59,8 +60,11 @@ def main():
     if not ok:
         sys.exit("%s has no matching .audited stamp (run --audit where it was built): not run" % lib)
     import numpy as np
-    args = [a for a in sys.argv[1:] if a != "--restarts"]
-    if "--restarts" in sys.argv[1:]:
+    args = [a for a in sys.argv[1:] if a not in ("--restarts", "--tail")]
+    if "--tail" in sys.argv[1:]:
+        import wave_golden_tail_cases as wc
+        default = "wave_tail.npz"
+    elif "--restarts" in sys.argv[1:]:
         import wave_golden_restart_cases as wc
         default = "wave_restarts.npz"
     else:
