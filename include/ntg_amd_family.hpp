@@ -132,10 +132,12 @@ struct FamilyDefaults {
 	hipError_t ntg_module_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a);                                         \
 	hipError_t ntg_module_launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a);                                            \
 	hipError_t ntg_module_launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a)
+// (their bodies: the one launcher of time_tile.hpp; a module has the widest flag's instances only)
 #define NTG_AMD_MODULE_CHECK_                                                                                                              \
-	hipError_t ntg_module_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a) { return launch_check<NTG_FAM_MODULE_SLOT, NTG_MAX_NZ>(D, T, a); } \
-	hipError_t ntg_module_launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a) { return launch_cost<NTG_FAM_MODULE_SLOT, NTG_MAX_NZ>(D, T, a); } \
-	hipError_t ntg_module_launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a) { return launch_verify<NTG_FAM_MODULE_SLOT, NTG_MAX_NZ>(D, T, a); }
+	static constexpr TileLaunchers ntg_module_tile = tile_launchers<NTG_FAM_MODULE_SLOT, NTG_MAX_NZ>();                                    \
+	hipError_t ntg_module_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a) { return ntg_module_tile.check(D, T, a); } \
+	hipError_t ntg_module_launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a) { return ntg_module_tile.cost(D, T, a); }   \
+	hipError_t ntg_module_launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a) { return ntg_module_tile.verify(D, T, a); }
 #define NTG_AMD_MODULE_MAIN_(FAMILY, NAME, NOUT_REQUIRED)                                                                                  \
 	namespace {                                                                                                                            \
 	hipError_t ntg_module_launch_eval(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a)                      \

@@ -13,7 +13,7 @@
 // scans.  Maxima with a total order on ties (the smaller key wins): no floating-point atomics, the result does not depend on the order
 // in which anything ran.
 #pragma once
-#include "solve_impl.hpp"
+#include "time_tile.hpp"   // (for the launcher only: the kernel below has the tile's steps written out)
 
 // the (violation, key) maximum of two candidates; key < 0: no violation seen
 __device__ __forceinline__ void check_take(double &bv, long long &bk, double ov, long long ok)
@@ -138,26 +138,11 @@ check_kernel(NtgDims D, NtgTables T, CheckArgs a)
 	}
 }
 
-template <int FAM, int NZMAX>
-static hipError_t launch_check_one(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
-{
-	using Fam = Family<FAM>;
-	if (D.nz > NZMAX || D.nnltc > Fam::NNLTC || !ntg_all_d(D, Fam::DM) || D.nout > NZMAX / Fam::DM) return hipErrorInvalidValue;
-	if (a.nb <= 0 || a.ntimes <= 0) return hipSuccess;
-	auto kfn = check_kernel<FAM, NZMAX>;
-	const size_t lds = ntg_check_lds(D);
-	if (lds > NTG_CHECK_LDS_MAX) return hipErrorInvalidValue;   // (ntg_batch_check refuses such a plan before it gets here)
-	if (lds > 64 * 1024) {
-		const hipError_t e = hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-		if (e != hipSuccess) return e;
-	}
-	hipLaunchKernelGGL(kfn, dim3(a.ntiles, a.ngroups), dim3(NTG_CHECK_NT), lds, a.st, D, T, a);
-	return hipGetLastError();
-}
-// the instance with the smallest flag that holds the plan's (the flag lives in registers)
-template <int FAM, int NZ0, int... NZS>
-static hipError_t launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
-{
-	if constexpr (sizeof...(NZS) > 0) { if (D.nz > NZ0) return launch_check<FAM, NZS...>(D, T, a); }
-	return launch_check_one<FAM, NZ0>(D, T, a);
-}
+// what tile_launch (time_tile.hpp) asks of a time-tile kernel
+struct CheckTile {
+	using Args = CheckArgs;
+	static constexpr size_t LDS_MAX = NTG_CHECK_LDS_MAX;
+	static const CheckArgs &tile(const CheckArgs &a) { return a; }
+	template <int FAM, int NZMAX> static auto kernel() { return check_kernel<FAM, NZMAX>; }
+	template <class Fam> static bool refuses(const NtgDims &D) { return D.nnltc > Fam::NNLTC; }
+};

@@ -62,27 +62,11 @@ cost_kernel(NtgDims D, NtgTables T, CostArgs ca)
 	}
 }
 
-template <int FAM, int NZMAX>
-static hipError_t launch_cost_one(const NtgDims &D, const NtgTables &T, const CostArgs &ca)
-{
-	using Fam = Family<FAM>;
-	const CheckArgs &a = ca.t;
-	if (D.nz > NZMAX || !ntg_all_d(D, Fam::DM) || D.nout > NZMAX / Fam::DM) return hipErrorInvalidValue;
-	if (a.nb <= 0 || a.ntimes <= 0) return hipSuccess;
-	auto kfn = cost_kernel<FAM, NZMAX>;
-	const size_t lds = ntg_check_lds(D);
-	if (lds > NTG_CHECK_LDS_MAX) return hipErrorInvalidValue;   // (ntg_batch_cost refuses such a plan before it gets here)
-	if (lds > 64 * 1024) {
-		const hipError_t e = hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-		if (e != hipSuccess) return e;
-	}
-	hipLaunchKernelGGL(kfn, dim3(a.ntiles, a.ngroups), dim3(NTG_CHECK_NT), lds, a.st, D, T, ca);
-	return hipGetLastError();
-}
-// the instance with the smallest flag that holds the plan's (the flag lives in registers)
-template <int FAM, int NZ0, int... NZS>
-static hipError_t launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a)
-{
-	if constexpr (sizeof...(NZS) > 0) { if (D.nz > NZ0) return launch_cost<FAM, NZS...>(D, T, a); }
-	return launch_cost_one<FAM, NZ0>(D, T, a);
-}
+// what tile_launch (time_tile.hpp) asks of a time-tile kernel
+struct CostTile {
+	using Args = CostArgs;
+	static constexpr size_t LDS_MAX = NTG_CHECK_LDS_MAX;
+	static const CheckArgs &tile(const CostArgs &ca) { return ca.t; }
+	template <int FAM, int NZMAX> static auto kernel() { return cost_kernel<FAM, NZMAX>; }
+	template <class Fam> static bool refuses(const NtgDims &) { return false; }
+};

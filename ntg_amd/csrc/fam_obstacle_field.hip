@@ -4,9 +4,8 @@
 
 static hipError_t fam_launch_eval(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a) { return obstacle_launch_eval<NTG_FAM_OBSTACLE_FIELD>(D, T, L, a); }
 static hipError_t fam_launch_sqp(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const SolveParams &sp, const SqpArgs &a) { return obstacle_launch_sqp<NTG_FAM_OBSTACLE_FIELD>(D, T, L, sp, a); }
-static hipError_t fam_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a) { return obstacle_launch_check<NTG_FAM_OBSTACLE_FIELD>(D, T, a); }
-static hipError_t fam_launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a) { return obstacle_launch_cost<NTG_FAM_OBSTACLE_FIELD>(D, T, a); }
-static hipError_t fam_launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a) { return obstacle_launch_verify<NTG_FAM_OBSTACLE_FIELD>(D, T, a); }
+// (in both passes: the device pass instantiates the time-tile kernels from this line)
+static constexpr TileLaunchers fam_tile = obstacle_tile<NTG_FAM_OBSTACLE_FIELD>();
 
 // the family on the host (family_module.hpp): its shape rule, and its descriptor from Family<>'s constants.  Host pass only: the device
 // pass would emit the constant object into the device code as well.
@@ -17,5 +16,5 @@ static const char *shape_rule(const ntg_spec &s)
 	           ? "obstacle-field family: 2 outputs, 1 to 8 trajectory constraints (one per obstacle), no initial or final rows" : nullptr;
 }
 static_assert(Family<NTG_FAM_OBSTACLE_FIELD>::NNLTC == 8, "the shape rule's text says 8");
-extern const NtgFamily ntg_fam_obstacle_field = ntg_builtin_family<NTG_FAM_OBSTACLE_FIELD>("obstacle_field", 2, shape_rule, fam_launch_eval, fam_launch_sqp, fam_launch_check, fam_launch_cost, fam_launch_verify, true);
+extern const NtgFamily ntg_fam_obstacle_field = ntg_builtin_family<NTG_FAM_OBSTACLE_FIELD>("obstacle_field", 2, shape_rule, fam_launch_eval, fam_launch_sqp, fam_tile, true);
 #endif

@@ -32,21 +32,9 @@ static hipError_t fam_launch_sqp(const NtgDims &D, const NtgTables &T, const Sme
 	return launch_sqp_generic<NTG_FAM_QUADROTOR>(D, T, L, sp, a);
 }
 
-// the between-breakpoints check (check.hpp): instances by flag size
-static hipError_t fam_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
-{
-	return launch_check<NTG_FAM_QUADROTOR, 20, NTG_MAX_NZ>(D, T, a);
-}
-// the running cost under a quadrature (cost.hpp): the same instances
-static hipError_t fam_launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a)
-{
-	return launch_cost<NTG_FAM_QUADROTOR, 20, NTG_MAX_NZ>(D, T, a);
-}
-// the derivative audit at the breakpoints (verify.hpp): the same instances
-static hipError_t fam_launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a)
-{
-	return launch_verify<NTG_FAM_QUADROTOR, 20, NTG_MAX_NZ>(D, T, a);
-}
+// the time-tile kernels (check.hpp, cost.hpp, verify.hpp): instances by flag size, the same for the three.  In both passes: the
+// device pass instantiates the kernels from this line.
+static constexpr TileLaunchers fam_tile = tile_launchers<NTG_FAM_QUADROTOR, 20, NTG_MAX_NZ>();
 
 // the family on the host (family_module.hpp): its shape rule, and its descriptor from Family<>'s constants.  (x, y, z) couple through thrust and
 // speed; the yaw output appears in no row: the one family whose plans have a free output (free_outputs_ok).  Host pass only: the device
@@ -56,5 +44,5 @@ static const char *shape_rule(const ntg_spec &s)
 {
 	return s.nout != 4 || s.nnlic || s.nnlfc || s.nnltc > 2 ? "quadrotor family: 4 outputs, at most two trajectory constraints" : nullptr;
 }
-extern const NtgFamily ntg_fam_quadrotor = ntg_builtin_family<NTG_FAM_QUADROTOR>("quadrotor", 4, shape_rule, fam_launch_eval, fam_launch_sqp, fam_launch_check, fam_launch_cost, fam_launch_verify, false, true);
+extern const NtgFamily ntg_fam_quadrotor = ntg_builtin_family<NTG_FAM_QUADROTOR>("quadrotor", 4, shape_rule, fam_launch_eval, fam_launch_sqp, fam_tile, false, true);
 #endif

@@ -23,21 +23,9 @@ static hipError_t fam_launch_sqp(const NtgDims &D, const NtgTables &T, const Sme
 	return launch_sqp_generic<NTG_FAM_TESTFAM>(D, T, L, sp, a);
 }
 
-// the between-breakpoints check (check.hpp): instances by flag size
-static hipError_t fam_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
-{
-	return launch_check<NTG_FAM_TESTFAM, 9, NTG_MAX_NZ>(D, T, a);
-}
-// the running cost under a quadrature (cost.hpp): the same instances
-static hipError_t fam_launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a)
-{
-	return launch_cost<NTG_FAM_TESTFAM, 9, NTG_MAX_NZ>(D, T, a);
-}
-// the derivative audit at the breakpoints (verify.hpp): the same instances
-static hipError_t fam_launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a)
-{
-	return launch_verify<NTG_FAM_TESTFAM, 9, NTG_MAX_NZ>(D, T, a);
-}
+// the time-tile kernels (check.hpp, cost.hpp, verify.hpp): instances by flag size, the same for the three.  In both passes: the
+// device pass instantiates the kernels from this line.
+static constexpr TileLaunchers fam_tile = tile_launchers<NTG_FAM_TESTFAM, 9, NTG_MAX_NZ>();
 
 // the family on the host (family_module.hpp): its shape rule, and its descriptor from Family<>'s constants.  Host pass only: the device
 // pass would emit the constant object into the device code as well.
@@ -46,5 +34,5 @@ static const char *shape_rule(const ntg_spec &s)
 {
 	return s.nnlic > 1 || s.nnltc > 2 || s.nnlfc > 1 ? "testfam has 1/2/1 nonlinear constraints" : nullptr;
 }
-extern const NtgFamily ntg_fam_testfam = ntg_builtin_family<NTG_FAM_TESTFAM>("testfam", 0, shape_rule, fam_launch_eval, fam_launch_sqp, fam_launch_check, fam_launch_cost, fam_launch_verify);
+extern const NtgFamily ntg_fam_testfam = ntg_builtin_family<NTG_FAM_TESTFAM>("testfam", 0, shape_rule, fam_launch_eval, fam_launch_sqp, fam_tile);
 #endif

@@ -445,11 +445,10 @@ template <> struct Family<NTG_FAM_OBSTACLE_FIELD> {
 // number of outputs a plan must have (0: any), its shape rule and launchers, and the two flags.
 template <int FAM>
 constexpr NtgFamily ntg_builtin_family(const char *name, int nout, const char *(*shape)(const ntg_spec &), ntg_module_eval_fn launch_eval, ntg_module_sqp_fn launch_sqp,
-                                       ntg_module_check_fn launch_check, ntg_module_cost_fn launch_cost, ntg_module_verify_fn launch_verify, bool kincar_flag = false,
-                                       bool free_outputs_ok = false)
+                                       const TileLaunchers &tile, bool kincar_flag = false, bool free_outputs_ok = false)
 {
 	using F = Family<FAM>;
 	static_assert((F::COUPLE > 0) == (F::GROUP_VARS != 0), "a family with second-order blocks names the flag entries of one coupling group");
 	return NtgFamily{name, F::DM, F::NNLIC, F::NNLTC, F::NNLFC, nout, F::COUPLE, F::CG, F::GROUP_VARS, free_outputs_ok,
-	                 FamPrmCounts<F>::n, FamPrmCounts<F>::bp, FamPrmRow<F>::value, kincar_flag, shape, launch_eval, launch_sqp, launch_check, launch_cost, launch_verify};
+	                 FamPrmCounts<F>::n, FamPrmCounts<F>::bp, FamPrmRow<F>::value, kincar_flag, shape, launch_eval, launch_sqp, tile.check, tile.cost, tile.verify};
 }

@@ -21,6 +21,8 @@ typedef hipError_t (*ntg_module_sqp_fn)(const NtgDims &, const NtgTables &, cons
 typedef hipError_t (*ntg_module_check_fn)(const NtgDims &, const NtgTables &, const CheckArgs &);
 typedef hipError_t (*ntg_module_cost_fn)(const NtgDims &, const NtgTables &, const CostArgs &);
 typedef hipError_t (*ntg_module_verify_fn)(const NtgDims &, const NtgTables &, const VerifyArgs &);
+// the launchers of a family's time-tile kernels, made from its one list of flag sizes (tile_launchers, time_tile.hpp)
+struct TileLaunchers { ntg_module_check_fn check; ntg_module_cost_fn cost; ntg_module_verify_fn verify; };
 
 struct ntg_family_module_desc {
 	unsigned long long abi;   // NTG_AMD_ABI the module was compiled with (first member in every version of the descriptor)

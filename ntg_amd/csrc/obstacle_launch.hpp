@@ -35,23 +35,6 @@ static hipError_t obstacle_launch_sqp(const NtgDims &D, const NtgTables &T, cons
 	return launch_sqp_generic<FAM>(D, T, L, sp, a);
 }
 
-// the between-breakpoints check (check.hpp): the families have two outputs, a flag of 6
+// the time-tile kernels (check.hpp, cost.hpp, verify.hpp): the families have two outputs, a flag of 6
 template <int FAM>
-static hipError_t obstacle_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a)
-{
-	return launch_check<FAM, 6>(D, T, a);
-}
-
-// the running cost under a quadrature (cost.hpp): the same instance
-template <int FAM>
-static hipError_t obstacle_launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a)
-{
-	return launch_cost<FAM, 6>(D, T, a);
-}
-
-// the derivative audit at the breakpoints (verify.hpp): the same instance
-template <int FAM>
-static hipError_t obstacle_launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a)
-{
-	return launch_verify<FAM, 6>(D, T, a);
-}
+constexpr TileLaunchers obstacle_tile() { return tile_launchers<FAM, 6>(); }

@@ -355,42 +355,39 @@ extern "C" int ntg_batch_interp_strided(const ntg_plan *p, int batch, const doub
 	if (p->grid_batch) {
 		// per-problem grids: every problem on its own knots (one basis class), at its own times (row b of d_times at b * times_stride) or,
 		// times_stride == 0, all at the same times
+		StreamScratch scratch(st);
 		double *d_tb = nullptr; int *d_to = nullptr;
 		const size_t per = (size_t)ntimes * D.cls_k[0] * D.cls_d[0];
-		hipError_t e2 = hipMallocAsync((void **)&d_tb, (size_t)batch * per * 8, st);
-		if (e2 == hipSuccess) e2 = hipMallocAsync((void **)&d_to, (size_t)batch * ntimes * 4, st);
+		hipError_t e2 = scratch.alloc(&d_tb, (size_t)batch * per);
+		if (e2 == hipSuccess) e2 = scratch.alloc(&d_to, (size_t)batch * ntimes);
 		if (e2 == hipSuccess) e2 = ntg_launch_basis(batch, D.cls_l[0], D.cls_k[0], D.cls_m[0], D.cls_d[0], ntimes, p->d_grid_knots, d_times, D.cls_l[0] + 1, times_stride, d_tb, d_to, st);
 		if (e2 == hipSuccess) e2 = ntg_launch_interp(D, batch, ntimes, d_x, d_tb, d_to, nullptr, d_z, st, 1);
-		if (d_tb) (void)hipFreeAsync(d_tb, st);
-		if (d_to) (void)hipFreeAsync(d_to, st);
 		if (e2 != hipSuccess) return fail(NTG_E_HIP, hipGetErrorString(e2));
 		return 0;
 	}
 	// basis of every class at the requested times (the same kernel that builds the collocation tables), stream ordered
+	StreamScratch scratch(st);
 	double *d_tblk = nullptr; int *d_toff = nullptr, *d_base = nullptr;
 	std::vector<int> base(D.nclass);
 	size_t tot = 0;
 	for (int c = 0; c < D.nclass; c++) { base[c] = (int)tot; tot += (size_t)ntimes * D.cls_k[c] * D.cls_d[c]; }
-	// (the three buffers are released on every path: failures fall through to the frees below)
-	hipError_t e = hipMallocAsync((void **)&d_tblk, tot * 8, st);
-	if (e == hipSuccess) e = hipMallocAsync((void **)&d_toff, (size_t)D.nclass * ntimes * 4, st);
-	if (e == hipSuccess) e = hipMallocAsync((void **)&d_base, (size_t)D.nclass * 4, st);
+	hipError_t e = scratch.alloc(&d_tblk, tot);
+	if (e == hipSuccess) e = scratch.alloc(&d_toff, (size_t)D.nclass * ntimes);
+	if (e == hipSuccess) e = scratch.alloc(&d_base, (size_t)D.nclass);
 	if (e == hipSuccess) e = hipMemcpyAsync(d_base, base.data(), (size_t)D.nclass * 4, hipMemcpyHostToDevice, st);
 	for (int c = 0; c < D.nclass && e == hipSuccess; c++)
 		e = ntg_launch_basis(1, D.cls_l[c], D.cls_k[c], D.cls_m[c], D.cls_d[c], ntimes, p->d_knots[c], d_times, 0, 0,
 		                     d_tblk + base[c], d_toff + (size_t)c * ntimes, st);
 	if (e == hipSuccess) e = ntg_launch_interp(D, batch, ntimes, d_x, d_tblk, d_toff, d_base, d_z, st);
 	const hipError_t es = hipStreamSynchronize(st);   // `base` is read by the async copy above
-	if (d_tblk) (void)hipFreeAsync(d_tblk, st);
-	if (d_toff) (void)hipFreeAsync(d_toff, st);
-	if (d_base) (void)hipFreeAsync(d_base, st);
 	HIPCHK(e);
 	HIPCHK(es);
 	return 0;
 }
 
-// ---- the kernels with times on the lanes (time_tile.hpp): ntg_batch_check here, ntg_batch_cost in plan_cost.cpp ----
-// What a call with a time vector refuses, in the order the two calls document; 0: go on.
+// ---- the kernels with times on the lanes (time_tile.hpp): ntg_batch_check here, ntg_batch_cost in plan_cost.cpp, ntg_batch_verify in
+// plan_verify.cpp ----
+// What a call with a time vector refuses, in the order the calls document; 0: go on.
 int time_args_check(const ntg_plan *p, int batch, int ntimes, long long times_stride)
 {
 	if (p->grid_batch && batch != p->grid_batch) return fail(NTG_E_BADARG, "the plan carries per-problem grids for another batch size");
@@ -402,11 +399,12 @@ int time_args_check(const ntg_plan *p, int batch, int ntimes, long long times_st
 }
 
 // The walk over the batch: fills the tile fields of `a` (the caller set x, st and its own fields), builds the basis at the times (the
-// tables ntg_batch_interp builds) in scratch, stream ordered and released on every path, and calls launch(a) for every chunk of problems.
+// tables ntg_batch_interp builds) in scratch, stream ordered and released when the walk returns, and calls launch() for every chunk of
+// problems.
 // On the shared grid the tables do not depend on the batch: one launch.  On per-problem grids they are as large as the flags would be, so
 // the batch is processed in chunks of problems whose tables stay under scratch_cap bytes (at least one problem per chunk).
 hipError_t time_tile_walk(const ntg_plan *p, int batch, int ntimes, const double *d_times, long long times_stride, long long scratch_cap,
-                          CheckArgs &a, const std::function<hipError_t(const CheckArgs &)> &launch)
+                          CheckArgs &a, const std::function<hipError_t()> &launch)
 {
 	const NtgDims &D = p->D;
 	hipStream_t st = a.st;
@@ -418,9 +416,10 @@ hipError_t time_tile_walk(const ntg_plan *p, int batch, int ntimes, const double
 	const size_t per_tab = tot * 8 + (size_t)(a.pp ? 1 : D.nclass) * ntimes * 4;   // bytes of one set
 	const int chunk = a.pp ? (int)std::max<long long>(1, std::min<long long>(batch, scratch_cap / (long long)per_tab)) : batch;
 	const int ntab = a.pp ? chunk : 1;
+	StreamScratch scratch(st);
 	double *d_tblk = nullptr; int *d_toff = nullptr;
-	hipError_t e = hipMallocAsync((void **)&d_tblk, (size_t)ntab * tot * 8, st);
-	if (e == hipSuccess) e = hipMallocAsync((void **)&d_toff, (size_t)ntab * (a.pp ? 1 : D.nclass) * ntimes * 4, st);
+	hipError_t e = scratch.alloc(&d_tblk, (size_t)ntab * tot);
+	if (e == hipSuccess) e = scratch.alloc(&d_toff, (size_t)ntab * (a.pp ? 1 : D.nclass) * ntimes);
 	a.tblk = d_tblk; a.toff = d_toff;
 	// workgroups: (time tile, group of problems); a group's problems share the staged tile on the shared grid, so no more groups than
 	// fill the device a few times over
@@ -429,7 +428,7 @@ hipError_t time_tile_walk(const ntg_plan *p, int batch, int ntimes, const double
 		for (int c = 0; c < D.nclass && e == hipSuccess; c++)
 			e = ntg_launch_basis(1, D.cls_l[c], D.cls_k[c], D.cls_m[c], D.cls_d[c], ntimes, p->d_knots[c], d_times, 0, 0, d_tblk + a.gbase[c], d_toff + (size_t)c * ntimes, st);
 		a.b0 = 0; a.nb = batch; a.ngroups = std::min(std::min(batch, want_groups), 65535);
-		if (e == hipSuccess) e = launch(a);
+		if (e == hipSuccess) e = launch();
 	} else {
 		// per-problem grids: every problem on its own knots (one basis class), at its own times or, times_stride == 0, all at the same
 		const int l = D.cls_l[0];
@@ -441,11 +440,9 @@ hipError_t time_tile_walk(const ntg_plan *p, int batch, int ntimes, const double
 				                     d_times + (size_t)(b0 + g0) * times_stride, l + 1, times_stride, d_tblk + (size_t)g0 * tot, d_toff + (size_t)g0 * ntimes, st);
 			}
 			a.b0 = b0; a.nb = nb; a.ngroups = std::min(std::min(nb, want_groups), 65535);
-			if (e == hipSuccess) e = launch(a);
+			if (e == hipSuccess) e = launch();
 		}
 	}
-	if (d_tblk) (void)hipFreeAsync(d_tblk, st);
-	if (d_toff) (void)hipFreeAsync(d_toff, st);
 	return e;
 }
 
@@ -475,18 +472,12 @@ static int batch_check(const ntg_plan *p, int batch, const double *d_x, const do
 	CheckArgs a{};
 	a.x = d_x; a.lo = want_max ? d_lower : nullptr; a.up = want_max ? d_upper : nullptr;
 	a.ltc = p->d_ltc; a.rows = d_rows; a.st = st;
-	double *d_pv = nullptr; long long *d_pk = nullptr;
+	StreamScratch scratch(st);
 	hipError_t e = hipSuccess;
-	if (want_max) e = hipMallocAsync((void **)&d_pv, (size_t)batch * ntiles * 8, st);
-	if (e == hipSuccess && want_max) e = hipMallocAsync((void **)&d_pk, (size_t)batch * ntiles * 8, st);
-	a.pviol = d_pv; a.pkey = d_pk;
-	if (e == hipSuccess) e = time_tile_walk(p, batch, ntimes, d_times, times_stride, scratch_cap, a, [&](const CheckArgs &c) { return ntg_launch_check(D, p->T, c); });
-	if (e == hipSuccess && want_max) e = ntg_launch_check_final(batch, ntiles, ntimes, d_pv, d_pk, d_viol, d_where, st);
-	if (d_pv) (void)hipFreeAsync(d_pv, st);
-	if (d_pk) (void)hipFreeAsync(d_pk, st);
-	if (e == hipErrorInvalidValue) return fail(NTG_E_UNSUPPORTED, "the plan's family has no check instance for this shape");
-	if (e != hipSuccess) return fail(NTG_E_HIP, hipGetErrorString(e));
-	return 0;
+	if (want_max) e = scratch.alloc(&a.pviol, (size_t)batch * ntiles);
+	if (e == hipSuccess && want_max) e = scratch.alloc(&a.pkey, (size_t)batch * ntiles);
+	return time_tile_run(p, "check", e, batch, ntimes, d_times, times_stride, scratch_cap, a, [&] { return ntg_launch_check(D, p->T, a); },
+	                     [&] { return want_max ? ntg_launch_check_final(batch, ntiles, ntimes, a.pviol, a.pkey, d_viol, d_where, st) : hipSuccess; });
 }
 
 extern "C" int ntg_batch_check(const ntg_plan *p, int batch, const double *d_x, const double *d_lower, const double *d_upper, int ntimes,

@@ -1,7 +1,7 @@
 // plan_cost.cpp -- ntg_batch_cost: the running cost of a batch of trajectories at arbitrary times, summed under the caller's quadrature
 // weights (cost.hpp).  The walk over the batch is ntg_batch_check's (time_tile_walk, plan.cpp): the basis at the times in stream-ordered
 // scratch, per-problem grids in chunks of problems under the scratch cap.  Scratch of its own: one partial sum per problem and tile of
-// NTG_CHECK_NT times, added in tile order by cost_final_kernel.  Everything is released on every path.
+// NTG_CHECK_NT times, added in tile order by cost_final_kernel.  Its owner (StreamScratch) releases it on every path.
 #include "plan_priv.hpp"
 #include "family_module.hpp"
 
@@ -28,17 +28,11 @@ static int batch_cost(const ntg_plan *p, int batch, const double *d_x, int ntime
 	CostArgs ca{};
 	ca.t.x = d_x; ca.t.st = st;
 	ca.weights = d_cost ? d_weights : nullptr; ca.vals = d_vals;
-	double *d_pc = nullptr;
+	StreamScratch scratch(st);
 	hipError_t e = hipSuccess;
-	if (d_cost) e = hipMallocAsync((void **)&d_pc, (size_t)batch * ntiles * 8, st);
-	ca.pcost = d_pc;
-	if (e == hipSuccess)
-		e = time_tile_walk(p, batch, ntimes, d_times, times_stride, scratch_cap, ca.t, [&](const CheckArgs &) /* ca.t, filled by the walk */ { return ntg_launch_cost(D, p->T, ca); });
-	if (e == hipSuccess && d_cost) e = ntg_launch_cost_final(batch, ntiles, d_pc, d_cost, st);
-	if (d_pc) (void)hipFreeAsync(d_pc, st);
-	if (e == hipErrorInvalidValue) return fail(NTG_E_UNSUPPORTED, "the plan's family has no cost instance for this shape");
-	if (e != hipSuccess) return fail(NTG_E_HIP, hipGetErrorString(e));
-	return 0;
+	if (d_cost) e = scratch.alloc(&ca.pcost, (size_t)batch * ntiles);
+	return time_tile_run(p, "cost", e, batch, ntimes, d_times, times_stride, scratch_cap, ca.t, [&] { return ntg_launch_cost(D, p->T, ca); },
+	                     [&] { return d_cost ? ntg_launch_cost_final(batch, ntiles, ca.pcost, d_cost, st) : hipSuccess; });
 }
 
 extern "C" int ntg_batch_cost(const ntg_plan *p, int batch, const double *d_x, int ntimes, const double *d_times, const double *d_weights,

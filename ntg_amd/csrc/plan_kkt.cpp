@@ -1,7 +1,7 @@
 // plan_kkt.cpp -- ntg_batch_kkt: first-order optimality residuals of a batch of points, whoever produced them (kkt.hpp).
 // The batch goes through in chunks of problems: per chunk the evaluation ntg_batch_eval runs for mode 2 without the dense Jacobian
 // (values, gradient, residuals, banded Jacobian rows), the expanded bounds of ntg_batch_bounds, then kkt_kernel.  Scratch, stream ordered,
-// one allocation, released on every path, per problem of a chunk:
+// one allocation (StreamScratch releases it on every path), per problem of a chunk:
 //   f [1]  g [nC]  c [ncnln]  jband [ncnln][sumk]  bl, bu [nC + nclin + ncnln]
 // (f is not used: with it the evaluation is the instance ntg_batch_eval launches for the same request).  A chunk holds as many problems
 // as stay under the scratch cap, at least one.
@@ -51,8 +51,9 @@ static int batch_kkt(const ntg_plan *p, int batch, const double *d_x, const doub
 	const int ntot = D.nC + D.nclin + D.ncnln;
 	EvalShape es;
 	if (int rc = eval_shape(p, chunk, &es)) return rc;
+	StreamScratch scratch(st);
 	double *d_s = nullptr;
-	hipError_t e = hipMallocAsync((void **)&d_s, (size_t)chunk * per, st);
+	hipError_t e = scratch.alloc(&d_s, (size_t)chunk * kkt_scratch_doubles(D));
 	if (e != hipSuccess) return fail(NTG_E_HIP, hipGetErrorString(e));
 	double *d_f = d_s, *d_g = d_f + chunk, *d_c = d_g + (size_t)chunk * D.nC, *d_jb = d_c + (size_t)chunk * D.ncnln;
 	double *d_bl = d_jb + (size_t)chunk * D.ncnln * D.sumk, *d_bu = d_bl + (size_t)chunk * ntot;
@@ -71,7 +72,6 @@ static int batch_kkt(const ntg_plan *p, int batch, const double *d_x, const doub
 		KktArgs ka{b0, nb, std::min(nb, ncu * wg_per_cu), d_x, d_clambda, d_g, d_c, d_jb, d_bl, d_bu, d_res, d_r, st};
 		if (e == hipSuccess) e = ntg_launch_kkt(D, p->T, ka);
 	}
-	(void)hipFreeAsync(d_s, st);
 	if (rc) return rc;
 	if (e != hipSuccess) return fail(NTG_E_HIP, hipGetErrorString(e));
 	return 0;

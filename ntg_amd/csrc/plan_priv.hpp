@@ -1,9 +1,11 @@
-// plan_priv.hpp -- what the host translation units behind include/ntg_amd.h share and nobody else sees: error reporting, the owner
-// of device allocations, the small algebra used by more than one of them, and the functions one unit offers the others.
+// plan_priv.hpp -- what the host translation units behind include/ntg_amd.h share and nobody else sees: error reporting, the owners
+// of device allocations and of stream-ordered scratch, the small algebra used by more than one of them, and the functions one unit offers
+// the others.
 //   plan.cpp        entry points of the batched calls, the solve setup (which kernel, which layout, which part of the workspace)
 //   plan_build.cpp  ntg_plan_create: spec validation, basis classes, channel tables, linear rows; the structured-Newton tables; the
 //                   preconditioner; plan queries
 //   plan_grids.cpp  per-problem grids (ntg_plan_set_grids) and per-problem family parameters
+//   plan_refine.cpp ntg_batch_refine: which pairs of plans it takes, the break conditions on shared grids, the launch
 //   plan_kkt.cpp    ntg_batch_kkt: first-order optimality residuals of a batch
 //   plan_cost.cpp   ntg_batch_cost: the running cost of a batch at arbitrary times under a quadrature
 //   plan_verify.cpp ntg_batch_verify: a family's analytic derivatives against central differences at the breakpoints
@@ -54,6 +56,28 @@ public:
 	}
 	void free_all() { for (void *q : ptrs_) (void)hipFree(q); ptrs_.clear(); }
 	void release_into(std::vector<void *> &dst) { dst.insert(dst.end(), ptrs_.begin(), ptrs_.end()); ptrs_.clear(); }   // in allocation order
+};
+
+// Owner of stream-ordered scratch, DevOwner's counterpart for hipMallocAsync: what it allocated is freed on its stream (hipFreeAsync,
+// in allocation order) when it goes out of scope, on every path.  The frees are ordered behind the work already on the stream; a user
+// that has to wait for that work (the host reads a result, or the work reads host memory) synchronises the stream itself.
+class StreamScratch {
+	static constexpr int CAP = 4;   // buffers of one owner (the most a user has: 3); a fixed array: no heap allocation per call
+	hipStream_t st_;
+	void *ptrs_[CAP];
+	int n_ = 0;
+public:
+	explicit StreamScratch(hipStream_t st) : st_(st) {}
+	StreamScratch(const StreamScratch &) = delete;
+	StreamScratch &operator=(const StreamScratch &) = delete;
+	~StreamScratch() { for (int i = 0; i < n_; i++) (void)hipFreeAsync(ptrs_[i], st_); }
+	// n elements; on failure *dst is null and nothing is owned
+	template <class T> hipError_t alloc(T **dst, size_t n)
+	{
+		const hipError_t e = n_ < CAP ? hipMallocAsync((void **)dst, n * sizeof(T), st_) : hipErrorOutOfMemory;
+		if (e == hipSuccess) ptrs_[n_++] = (void *)*dst; else *dst = nullptr;
+		return e;
+	}
 };
 
 // ---------------- small algebra with more than one user ----------------
@@ -119,8 +143,23 @@ int check_params(const ntg_plan *p, int batch);
 // launch shape of the evaluation of `batch` problems: workgroup size, persistent grid, LDS layout; 0 or an error code  (plan.cpp)
 struct EvalShape { int nt, grid; SmemLayout L; };
 int eval_shape(const ntg_plan *p, int batch, EvalShape *s);
-// calls with a time vector (ntg_batch_check, ntg_batch_cost; plan.cpp): what they refuse about the batch, the stride, the parameters and
-// the LDS; and the walk over the batch with the basis at the times in stream-ordered scratch, launch(a) once per chunk of problems
+// the calls on time tiles (ntg_batch_check in plan.cpp, ntg_batch_cost, ntg_batch_verify): what they refuse about the batch, the stride,
+// the parameters and the LDS; the walk over the batch with the basis at the times in stream-ordered scratch, launch() once per chunk of
+// problems (plan.cpp); and their common tail: the walk, the final kernel behind it (the walk's tables are released before it is
+// enqueued), and what the call returns.
+//   a     the tile fields of the call's arguments: the caller set x and st, the walk fills the rest before every launch
+//   what  the call's name in the refusal of a shape without an instance
+//   e     the outcome of the caller's own allocations: a failure skips the walk and is reported like one of its own
 int time_args_check(const ntg_plan *p, int batch, int ntimes, long long times_stride);
 hipError_t time_tile_walk(const ntg_plan *p, int batch, int ntimes, const double *d_times, long long times_stride, long long scratch_cap,
-                          CheckArgs &a, const std::function<hipError_t(const CheckArgs &)> &launch);
+                          CheckArgs &a, const std::function<hipError_t()> &launch);
+template <class Launch, class Finish>
+static inline int time_tile_run(const ntg_plan *p, const char *what, hipError_t e, int batch, int ntimes, const double *d_times, long long times_stride,
+                                long long scratch_cap, CheckArgs &a, Launch launch, Finish finish)
+{
+	if (e == hipSuccess) e = time_tile_walk(p, batch, ntimes, d_times, times_stride, scratch_cap, a, launch);
+	if (e == hipSuccess) e = finish();
+	if (e == hipErrorInvalidValue) return fail(NTG_E_UNSUPPORTED, std::string("the plan's family has no ") + what + " instance for this shape");
+	if (e != hipSuccess) return fail(NTG_E_HIP, hipGetErrorString(e));
+	return 0;
+}

@@ -74,13 +74,13 @@ extern "C" int ntg_batch_refine(const ntg_plan *from, const ntg_plan *to, int ba
 		return 0;
 	}
 	// per-problem grids: the kernel checks every problem's two break sequences; the call waits for its error word
-	hipError_t e = hipMallocAsync((void **)&A.err, 8, st);
+	StreamScratch scratch(st);
+	hipError_t e = scratch.alloc(&A.err, 1);
 	if (e == hipSuccess) e = hipMemsetAsync(A.err, 0xff, 8, st);
 	if (e == hipSuccess) e = ntg_launch_refine(A, 1, plan_ncu(to), st);
 	unsigned long long herr = ~0ull;
 	if (e == hipSuccess) e = hipMemcpyAsync(&herr, A.err, 8, hipMemcpyDeviceToHost, st);
 	const hipError_t es = hipStreamSynchronize(st);
-	if (A.err) (void)hipFreeAsync(A.err, st);
 	HIPCHK(e);
 	HIPCHK(es);
 	if (herr != ~0ull) {

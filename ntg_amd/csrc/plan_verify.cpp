@@ -2,7 +2,7 @@
 // (verify.hpp).  The walk over the batch is ntg_batch_check's (time_tile_walk, plan.cpp) with the breakpoints as the times -- the plan's,
 // or after ntg_plan_set_grids every problem's own: the basis at them in stream-ordered scratch, per-problem grids in chunks of problems
 // under the scratch cap.  Scratch of its own: one (value, key) pair per problem, tile of NTG_CHECK_NT breakpoints, slot and kind, which
-// verify_final_kernel scans in tile order.  Everything is released on every path.
+// verify_final_kernel scans in tile order.  Its owner (StreamScratch) releases it on every path.
 #include "plan_priv.hpp"
 #include "family_module.hpp"
 
@@ -31,16 +31,11 @@ static int batch_verify(const ntg_plan *p, int batch, const double *d_x, double 
 	const size_t npart = (size_t)batch * ntiles * 2 * NTG_VERIFY_NSLOT;
 	VerifyArgs va{};
 	va.t.x = d_x; va.t.st = st;
-	hipError_t e = hipMallocAsync((void **)&va.pval, npart * 8, st);
-	if (e == hipSuccess) e = hipMallocAsync((void **)&va.pkey, npart * 8, st);
-	if (e == hipSuccess)
-		e = time_tile_walk(p, batch, P, p->T.bps, stride, scratch_cap, va.t, [&](const CheckArgs &) /* va.t, filled by the walk */ { return ntg_launch_verify(D, p->T, va); });
-	if (e == hipSuccess) e = ntg_launch_verify_final(batch, ntiles, P, D.nz, va.pval, va.pkey, d_err, d_where, d_leak, d_leak_where, st);
-	if (va.pval) (void)hipFreeAsync(va.pval, st);
-	if (va.pkey) (void)hipFreeAsync(va.pkey, st);
-	if (e == hipErrorInvalidValue) return fail(NTG_E_UNSUPPORTED, "the plan's family has no verify instance for this shape");
-	if (e != hipSuccess) return fail(NTG_E_HIP, hipGetErrorString(e));
-	return 0;
+	StreamScratch scratch(st);
+	hipError_t e = scratch.alloc(&va.pval, npart);
+	if (e == hipSuccess) e = scratch.alloc(&va.pkey, npart);
+	return time_tile_run(p, "verify", e, batch, P, p->T.bps, stride, scratch_cap, va.t, [&] { return ntg_launch_verify(D, p->T, va); },
+	                     [&] { return ntg_launch_verify_final(batch, ntiles, P, D.nz, va.pval, va.pkey, d_err, d_where, d_leak, d_leak_where, st); });
 }
 
 extern "C" int ntg_batch_verify(const ntg_plan *p, int batch, const double *d_x, double *d_err, int *d_where, double *d_leak, int *d_leak_where,

@@ -6,6 +6,7 @@
 // check_kernel (check.hpp) has the same steps written out in its body, statement for statement: called from there, these functions
 // compile to other code for its shipped instances (the 64-entry instances go from 171 to 243 vector registers, the others move by up
 // to 4 % in instructions), so it keeps its text and its code.  A change to the staging, the offsets or the flag belongs in both places.
+// On the host every such kernel, check_kernel included, is launched by tile_launch below; a family names its instances once (tile_launchers).
 #pragma once
 #include "solve_impl.hpp"
 
@@ -89,4 +90,40 @@ __device__ __forceinline__ int tile_bp_index(const NtgDims &D, const NtgTables &
 	int ilo = 0, ihi = D.P;
 	while (ihi - ilo > 1) { const int mid = (ilo + ihi) >> 1; if (bps[mid] <= tv) ilo = mid; else ihi = mid; }
 	return ilo;
+}
+
+// ---------------- host side: the one launcher of the time-tile kernels ----------------
+// A kernel of this kind states in a struct K next to it (CheckTile, CostTile, VerifyTile) what the launcher cannot know:
+//   Args                    its argument struct, and tile(args): the tile fields in it
+//   kernel<FAM, NZMAX>()    its instance for a family and a flag size
+//   refuses<Fam>(D)         shapes it does not take, besides the ones no time-tile kernel takes
+//   LDS_MAX                 the most dynamic LDS a workgroup of it may ask for (160 KiB less its static part)
+// NZ0, NZS...: the flag sizes the family has instances for, ascending; the one launched is the smallest that holds the plan's (the
+// flag lives in registers).  hipErrorInvalidValue: no instance for this shape.
+template <class K, int FAM, int NZ0, int... NZS>
+static hipError_t tile_launch(const NtgDims &D, const NtgTables &T, const typename K::Args &ka)
+{
+	if constexpr (sizeof...(NZS) > 0) { if (D.nz > NZ0) return tile_launch<K, FAM, NZS...>(D, T, ka); }
+	using Fam = Family<FAM>;
+	const CheckArgs &a = K::tile(ka);
+	if (D.nz > NZ0 || !ntg_all_d(D, Fam::DM) || D.nout > NZ0 / Fam::DM || K::template refuses<Fam>(D)) return hipErrorInvalidValue;
+	if (a.nb <= 0 || a.ntimes <= 0) return hipSuccess;
+	auto kfn = K::template kernel<FAM, NZ0>();
+	const size_t lds = ntg_check_lds(D);
+	if (lds > K::LDS_MAX) return hipErrorInvalidValue;   // (the batch call refuses such a plan before it gets here)
+	if (lds > 64 * 1024) {
+		const hipError_t e = hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+		if (e != hipSuccess) return e;
+	}
+	hipLaunchKernelGGL(kfn, dim3(a.ntiles, a.ngroups), dim3(NTG_CHECK_NT), lds, a.st, D, T, ka);
+	return hipGetLastError();
+}
+
+// The three launchers of a family (TileLaunchers, family_module.hpp) from its one list of flag sizes.  A unit that calls this includes
+// check.hpp, cost.hpp and verify.hpp, and calls it where the device pass sees the call too: that is what instantiates the kernels.
+struct CheckTile; struct CostTile; struct VerifyTile;
+template <int FAM, int... NZS>
+constexpr TileLaunchers tile_launchers()
+{
+	return TileLaunchers{tile_launch<CheckTile, FAM, NZS...>, tile_launch<CostTile, FAM, NZS...>, tile_launch<VerifyTile, FAM, NZS...>};
 }

@@ -202,28 +202,14 @@ verify_kernel(NtgDims D, NtgTables T, VerifyArgs va)
 	}
 }
 
-template <int FAM, int NZMAX>
-static hipError_t launch_verify_one(const NtgDims &D, const NtgTables &T, const VerifyArgs &va)
-{
-	using Fam = Family<FAM>;
-	const CheckArgs &a = va.t;
-	if (D.nz > NZMAX || !ntg_all_d(D, Fam::DM) || D.nout > NZMAX / Fam::DM || D.nz != Fam::DM * D.nout) return hipErrorInvalidValue;
-	if (D.nnlic > Fam::NNLIC || D.nnltc > Fam::NNLTC || D.nnlfc > Fam::NNLFC) return hipErrorInvalidValue;
-	if (a.nb <= 0 || a.ntimes <= 0) return hipSuccess;
-	auto kfn = verify_kernel<FAM, NZMAX>;
-	const size_t lds = ntg_check_lds(D);
-	if (lds > NTG_VERIFY_LDS_MAX) return hipErrorInvalidValue;   // (ntg_batch_verify refuses such a plan before it gets here)
-	if (lds > 64 * 1024) {
-		const hipError_t e = hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-		if (e != hipSuccess) return e;
+// what tile_launch (time_tile.hpp) asks of a time-tile kernel; the callbacks get the whole flag of DM nout entries
+struct VerifyTile {
+	using Args = VerifyArgs;
+	static constexpr size_t LDS_MAX = NTG_VERIFY_LDS_MAX;
+	static const CheckArgs &tile(const VerifyArgs &va) { return va.t; }
+	template <int FAM, int NZMAX> static auto kernel() { return verify_kernel<FAM, NZMAX>; }
+	template <class Fam> static bool refuses(const NtgDims &D)
+	{
+		return D.nz != Fam::DM * D.nout || D.nnlic > Fam::NNLIC || D.nnltc > Fam::NNLTC || D.nnlfc > Fam::NNLFC;
 	}
-	hipLaunchKernelGGL(kfn, dim3(a.ntiles, a.ngroups), dim3(NTG_CHECK_NT), lds, a.st, D, T, va);
-	return hipGetLastError();
-}
-// the instance with the smallest flag that holds the plan's (the flag lives in registers)
-template <int FAM, int NZ0, int... NZS>
-static hipError_t launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a)
-{
-	if constexpr (sizeof...(NZS) > 0) { if (D.nz > NZ0) return launch_verify<FAM, NZS...>(D, T, a); }
-	return launch_verify_one<FAM, NZ0>(D, T, a);
-}
+};
