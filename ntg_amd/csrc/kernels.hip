@@ -396,12 +396,11 @@ SmemLayout ntg_make_layout(const NtgDims &D, int nthreads, int nvec, int with_x,
 		if (L.dfz_rows < 1) L.dfz_rows = 1;
 		L.tav_rows = nvec > 0 ? D.ntav : D.ntav_cost;
 		int dfz_bytes = (L.dfz_rows * (D.P + 1) + ntg_dfz_tail(D)) * 8;
-		if (D.nwt_on && nvec > 0) dfz_bytes = std::max(dfz_bytes,   // (solve layouts only: the evaluation kernels never factor anything)
-		                                   std::max(D.nwt_ngrp * ((D.nwt_tw ? 16 * (D.nwt_ja + 3) + 48 + 16 * (D.nwt_jb + 3) + 48 : 16 * ((D.nwt_ng + 15) / 16) + 48) + (D.nwt_tw ? 2 : 1) * 416 /* NWT_PANEL */) * 8 + D.nwt_nfo * (16 * ((D.nwt_ngf + 15) / 16) + 48) * 8 + (qp ? (D.nwt_ngrp * ntg_qp_doubles(ntg_qp_maxa(D.nwt_ngrp, nthreads)) + NTG_QP_RED) * 8 : 0) /* QP-based SQP step: the groups' slots, scratch of the entering-row search */, (nthreads / 64) * 216 * 8 + D.nwt_ngrp * ((D.P + 63) / 64) * 8));   // solve vectors + panels | the assembly's staging buffers + the block flags
+		if (D.nwt_on && nvec > 0) dfz_bytes = std::max(dfz_bytes, nwt_map(D, nthreads, qp, D.nwt_cg).bytes);   // (solve layouts only: the evaluation kernels never factor anything)
 		L.dfz = p; L.nwt_y = p; p = align16(p + dfz_bytes);
 	}
 	L.fvals = p; p = align16(p + D.P * 8);
-	L.red = p; p = align16(p + (32 * (nthreads / 64) + 2) * 8);   // two halves of 16 values x waves (block_sum) + the Newton mode's flag words
+	L.red = p; p = align16(p + nwt_map(D, nthreads, qp, D.nwt_cg).red_doubles * 8);   // two halves of 16 values x waves (block_sum) + the Newton mode's flag words
 	L.dfi = p; p = align16(p + (D.nz + 1) * 8);
 	L.dff = p; p = align16(p + (D.nz + 1) * 8);
 	// evaluation layouts (nvec == 0) carry no solver state: no vectors, multipliers or line-search records (config D's evaluation sits

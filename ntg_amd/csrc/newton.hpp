@@ -20,9 +20,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ntg_dev.hpp"
+#include "nwt_map.hpp"   // NWT_PANEL, NWT_STAGE and where everything of the mode lives
 
 #define NWT_PSTRIDE 17   // LDS row stride (doubles) of a 48 x 16 panel in operand order (nwt_to_operand: diagnostics, tests/tools_mfma.hip)
-#define NWT_PANEL 416    // LDS doubles a factoring wave owns (nwt_factor_wave: two buffers of four panel columns, stride 52)
 #ifndef NWT_PIVOTS
 #define NWT_PIVOTS 2     // pivots per LDS round trip of the factorisation's sweep (1, 2 or 4; 4 is no faster standalone and 15-30 % slower
                          // inside the solve kernels, whose instances compile the routine for at most 256 registers)
@@ -523,7 +523,7 @@ __device__ __forceinline__ void nwt_solve_pairs(const double *Kt, const double *
 // read-modify-write of the band needs no atomics and the sum is deterministic.  Per item there is ONE round trip to
 // HBM/L2: the interval's blocks (one coalesced load, staged in LDS) and the band entries the result is added to are
 // requested together, before the products.
-// Bz: [ngrp][P][cg*cg] of this problem, or nullptr (cost model alone: phase 0, mu == 0).  wbuf: LDS, 216 doubles per wave.
+// Bz: [ngrp][P][cg*cg] of this problem, or nullptr (cost model alone: phase 0, mu == 0).  wbuf: LDS, NWT_STAGE doubles per wave (NwtMap::act: the block-flag words behind them).
 // CG: the family's block size (Family::CG) as a compile-time constant: the loop over a block's variables unrolls, kk / CG is a multiply,
 // and what a variable is (its output, the LDS offset of its derivative channel, whether this lane's columns belong to its output) is
 // decoded once per kernel instead of once per k-step and variable.
@@ -559,8 +559,8 @@ NWT_FN void nwt_assemble(const NtgDims &D, const NtgTables &T, const double *row
 	__syncthreads();
 	if (tkx) { const unsigned long long t1 = __builtin_amdgcn_s_memtime(); tkx[0] += t1 - tx0; tx0 = t1; }
 	if (!Bz) return;
-	double *wbuf = wbuf_all + wave * 216;
-	const unsigned long long *act = (const unsigned long long *)(wbuf_all + NW * 216);   // written by the block pass (sqp_kernel, nwt_refresh)
+	double *wbuf = wbuf_all + wave * NWT_STAGE;
+	const unsigned long long *act = (const unsigned long long *)(wbuf_all + NW * NWT_STAGE);   // written by the block pass (sqp_kernel, nwt_refresh)
 	// the two local columns (block-coefficient index a = q go + o) this lane stands for in the operand tiles
 	const int a0 = li, a1 = 16 + li;
 	const int qa0 = a0 / go, oa0 = a0 - qa0 * go, qa1 = a1 / go, oa1 = a1 - qa1 * go;
@@ -621,7 +621,7 @@ NWT_FN void nwt_assemble(const NtgDims &D, const NtgTables &T, const double *row
 #pragma unroll
 			for (int e = 0; e < 12; e++) kv[e] = Kg[NWT_IDX(idx[e] >= 0 ? idx[e] : 0, (long long)total, "asm")];
 #pragma unroll
-			for (int u = 0; u < 4; u++) if (lane + 64 * u < 216) wbuf[lane + 64 * u] = bl[u];
+			for (int u = 0; u < 4; u++) if (lane + 64 * u < NWT_STAGE) wbuf[lane + 64 * u] = bl[u];
 			nwt_wave_sync();
 			nwt_d4 S00 = {0.0, 0.0, 0.0, 0.0}, S10 = {0.0, 0.0, 0.0, 0.0}, S11 = {0.0, 0.0, 0.0, 0.0};
 			for (int s = 0; s < ksteps; s++) {
@@ -638,7 +638,7 @@ NWT_FN void nwt_assemble(const NtgDims &D, const NtgTables &T, const double *row
 				const double A1 = (kvd && ua1 >= 0) ? a1v : 0.0;
 				// B[kk][b] = V[kk][b] = sum_v B_i[u][v] Mst_i[v][b]
 				double B0 = 0.0, B1 = 0.0;
-				const double *Bi = wbuf + NWT_IDX((bi * CG + u) * CG, 216, "wbuf");
+				const double *Bi = wbuf + NWT_IDX((bi * CG + u) * CG, NWT_STAGE, "wbuf");
 #pragma unroll
 				for (int v = 0; v < CG; v++) {
 					const double bb = kvd ? Bi[v] : 0.0;

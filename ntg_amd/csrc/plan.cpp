@@ -8,7 +8,7 @@
 #include <cstdlib>
 #include <mutex>
 #include "plan_priv.hpp"
-#include "qpdual.hpp"
+#include "nwt_map.hpp"
 #include "family_module.hpp"
 
 static thread_local std::string g_err;
@@ -90,14 +90,11 @@ static size_t hist_doubles(const NtgDims &D, int batch, const SolveParams &sp)
 	return (size_t)batch * sp.memcap * (2 * D.nC + 2);
 }
 static size_t al_doubles(const NtgDims &D, int batch) { return (size_t)batch * 2 * (D.ncnln + D.nI); }
-// structured Newton mode: band matrix / factor of every group + the per-breakpoint blocks, per problem
+// structured Newton mode / QP-based SQP step: the per-problem workspace of nwt_map.hpp
 static size_t nwt_doubles(const NtgDims &D, int batch, const SolveParams &sp, int nt)
 {
 	if (sp.hessian < 2 || !D.nwt_on) return 0;
-	const size_t rev = D.nwt_tw ? (size_t)D.nwt_ngrp * (16 * D.nwt_jb + 48) * (D.nwt_hb + 1) : 0;   // the reversed arrays of the two-sided factorisation
-	// QP-based SQP step: the slots' columns W J' and the QP's multipliers (sqp_kernel, qp_pp)
-	const size_t qp = sp.hessian == 3 ? (size_t)ntg_qp_maxa(D.nwt_ngrp, nt) * ((D.nC + 1) & ~1) + (size_t)((D.ncnln + 1) & ~1) * (3 + D.nwt_cg + ntg_qp_maxa(D.nwt_ngrp, nt)) : 0;
-	return (size_t)batch * ((size_t)D.nwt_ngrp * D.nwt_ng * (D.nwt_hb + 1) + rev + (size_t)D.nwt_ngrp * D.P * D.nwt_cg * D.nwt_cg + qp);
+	return (size_t)batch * nwt_map(D, nt, sp.hessian == 3, D.nwt_cg).total;
 }
 
 

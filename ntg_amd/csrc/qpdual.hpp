@@ -1,6 +1,9 @@
-// qpdual.hpp -- the dual active-set solve of the QP-based SQP step (ntg_solve_opts.hessian = 3), scalar code shared
-// by the device kernel (one lane per coupling group runs it on that group's slots in LDS) and by the host unit test
-// (tests/drivers/qpdual_drv.cpp).
+// qpdual.hpp -- the dual active-set solve of the QP-based SQP step (ntg_solve_opts.hessian = 3), twice:
+//   qp_passive_solve       scalar code, host and device: the SPECIFICATION, and the subject of the host unit test (tests/drivers/qpdual_drv.cpp);
+//   qp_passive_solve_wave  what sqp_kernel runs (solve_impl.hpp): the same matrices, ratio test and drop rule by all lanes of the group's wave on
+//                          the group's slots in LDS (tests/drivers/qpwave_unit.hip runs both on the GPU: same passive set, same multipliers).
+// Their round bounds differ: 3 NTG_QP_MAXA + 8 rounds for the scalar routine, 3 QA + 8 (QA = the plan's slots per group, ntg_qp_maxa) for the
+// wave routine; every round but the last removes a slot, so neither bound is reached with a working set of at most QA slots.
 //
 // Role in the reference: the QP subproblem NPSOL solves with the Jacobian ntg() hands it (ntg.c:217-220,250-253; constraints.c:120-162):
 //     min 1/2 p'K p + g'p   s.t.  bl - c <= J p <= bu - c      (A_E p = 0 is built into W = Z (Z'KZ)^-1 Z')
@@ -113,3 +116,87 @@ NTG_HD int qp_passive_solve(Q &s)
 	}
 	return solves;
 }
+
+#ifdef __HIPCC__
+__device__ __forceinline__ void nwt_wave_sync();   // (newton.hpp)
+// The same solve (same matrices, same ratio test, same drop rule) by ALL lanes of the group's wave:
+// lane i owns row i of the passive matrix in LDS -- right-looking Cholesky with one rank-one update per pivot, substitutions with the
+// pivot's unknown broadcast by __shfl.  The scalar routine's O(np^3) dependent LDS accesses were the tail of config D (working sets of
+// 20 - 30 rows: a millisecond per solve); this is O(np^2) per lane.
+// q: the group's slots (LDS), lane: of the wave, QA: the plan's slots per group.  Returns the number of passive-set solves.
+template <class Q>
+__device__ __forceinline__ int qp_passive_solve_wave(Q &q, int lane, int QA)
+{
+	int solves = 0;
+	// (every round that does not end the loop removes at least one slot in exact arithmetic; the count is bounded all the same -- a wave
+	// that never leaves this loop would take the GPU with it)
+	for (int round = 0; round < 3 * QA + 8; round++) {
+		const int ns = *q.ns;
+		int np = 0;
+		for (int a = 0; a < ns; a++) if (q.inP[a]) { if (lane == 0) q.pl[np] = a; np++; }   // (uniform count; lane 0 writes the list)
+		nwt_wave_sync();
+		if (np == 0) break;
+		const int mya = lane < np ? q.pl[lane] : 0;
+		const double mys = q.sgn[mya] < 0 ? -1.0 : 1.0;
+		bool ok = false;
+		for (int attempt = 0; attempt < 2 && !ok; attempt++) {
+			const double shift = attempt ? 1e4 : 1.0;
+			if (lane < np)
+				for (int l = 0; l <= lane; l++) {
+					const int b2 = q.pl[l]; const double sb = q.sgn[b2] < 0 ? -1.0 : 1.0;
+					double h = mys * sb * q.S[mya >= b2 ? NTG_QP_TR(mya, b2) : NTG_QP_TR(b2, mya)];
+					if (l == lane) h += shift * 1e-10 * q.S[NTG_QP_TR(mya, mya)];
+					q.H[NTG_QP_TR(lane, l)] = h;
+				}
+			nwt_wave_sync();
+			ok = true;
+			for (int k = 0; k < np; k++) {
+				const double dkk = q.H[NTG_QP_TR(k, k)];
+				if (!(dkk > 0.0)) { ok = false; break; }   // (uniform: every lane reads the same word)
+				const double r = sqrt(dkk);
+				double lik = 0.0;
+				if (lane > k && lane < np) { lik = q.H[NTG_QP_TR(lane, k)] / r; q.H[NTG_QP_TR(lane, k)] = lik; }
+				nwt_wave_sync();
+				if (lane == k) q.H[NTG_QP_TR(k, k)] = r;
+				if (lane > k && lane < np) for (int j = k + 1; j <= lane; j++) q.H[NTG_QP_TR(lane, j)] -= lik * q.H[NTG_QP_TR(j, k)];
+				nwt_wave_sync();
+			}
+		}
+		if (!ok) {   // not factorable even with the larger shift: the working set is given up
+			if (lane < np) { q.nu[mya] = 0.0; q.inP[mya] = 0; }
+			nwt_wave_sync();
+			break;
+		}
+		// L z = -q, L' x = z
+		double zi = lane < np ? -(mys * (q.jwg[mya] + q.rr[mya]) - 1e-10 * q.S[NTG_QP_TR(mya, mya)] * q.nu0[mya]) : 0.0;
+		for (int k = 0; k < np; k++) {
+			const double lkk = q.H[NTG_QP_TR(k, k)];
+			if (lane == k) zi /= lkk;
+			const double zk = __shfl(zi, k);
+			if (lane > k && lane < np) zi -= q.H[NTG_QP_TR(lane, k)] * zk;
+		}
+		for (int k = np - 1; k >= 0; k--) {
+			const double lkk = q.H[NTG_QP_TR(k, k)];
+			if (lane == k) zi /= lkk;
+			const double xk = __shfl(zi, k);
+			if (lane < k) zi -= q.H[NTG_QP_TR(k, lane)] * xk;
+		}
+		solves++;
+		// ratio test: back to the first sign change
+		const double nua = lane < np ? q.nu[mya] : 0.0;
+		const bool bad = lane < np && q.sgn[mya] != 0 && !(zi > 0.0);
+		double al = bad ? nua / (nua - zi) : 1.0;
+#pragma unroll
+		for (int sh = 1; sh < 64; sh <<= 1) al = fmin(al, __shfl_xor(al, sh));
+		if (__ballot(bad) == 0ull) { if (lane < np) q.nu[mya] = zi; nwt_wave_sync(); break; }
+		if (!(al >= 0.0)) al = 0.0;
+		if (lane < np) {
+			const double nn = nua + al * (zi - nua);
+			if (q.sgn[mya] != 0 && !(nn > 1e-14 * (1.0 + fabs(zi)))) { q.nu[mya] = 0.0; q.inP[mya] = 0; }
+			else q.nu[mya] = nn;
+		}
+		nwt_wave_sync();
+	}
+	return solves;
+}
+#endif

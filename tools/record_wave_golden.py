@@ -1,13 +1,15 @@
 """Record tests/golden/wave_instances.npz (tests/test_gpu_wave_golden_instances.py), with --restarts tests/golden/wave_restarts.npz
-(tests/test_gpu_wave_golden_restarts.py) or with --tail tests/golden/wave_tail.npz (tests/test_gpu_wave_golden_tail.py) with the library
-named by NTG_AMD_LIB -- meant for the library of the commit BEFORE a change
-that must not move a bit.
+(tests/test_gpu_wave_golden_restarts.py), with --tail tests/golden/wave_tail.npz (tests/test_gpu_wave_golden_tail.py) or with --sqp
+tests/golden/sqp_modes.npz (the Newton and QP modes of sqp_kernel: tests/test_gpu_sqp_golden.py) with the library named by NTG_AMD_LIB --
+meant for the library of the commit BEFORE a change that must not move a bit.
 
   python tools/record_wave_golden.py --audit LIB     where LIB was built (no GPU): audit the device assembly of its wave kernels
-                                                     (ntg_amd/isa_audit.py, ntg_amd/call_audit.py) and write LIB.audited
-  NTG_AMD_LIB=LIB python tools/record_wave_golden.py [--restarts | --tail] [OUT.npz]     on the GPU: refuses a library without a matching LIB.audited
+                                                     (ntg_amd/isa_audit.py) and the call boundaries of every unit's (ntg_amd/call_audit.py),
+                                                     and write LIB.audited
+  NTG_AMD_LIB=LIB python tools/record_wave_golden.py [--restarts | --tail | --sqp] [OUT.npz]     on the GPU: refuses a library without a matching LIB.audited
 
 A library whose wave kernels failed the audit may corrupt the chain or fault on the GPU: it is never run."""
+import glob
 import hashlib
 import os
 import sys
@@ -38,7 +40,9 @@ def audit(lib):
     asm = _assembly_of(lib)
     if asm is None:
         sys.exit("no device assembly of the wave kernels next to %s (or newer than it): nothing to audit" % lib)
-    bad = isa_audit.audit("hipcc", "", "", [], 16, asm_path=asm) + call_audit.audit(asm)
+    bad = isa_audit.audit("hipcc", "", "", [], 16, asm_path=asm)
+    for a in sorted(glob.glob(os.path.join(os.path.dirname(asm), "*-gfx950.s")) if asm.endswith("-gfx950.s") else [asm]):   # (the --sqp cases run the other units' kernels)
+        bad += call_audit.audit(a)
     if bad:
         sys.exit("audit FAILED for %s:\n  %s" % (lib, "\n  ".join(b[:200] for b in bad[:8])))
     with open(lib + ".audited", "w") as f:
@@ -60,8 +64,11 @@ def main():
     if not ok:
         sys.exit("%s has no matching .audited stamp (run --audit where it was built): not run" % lib)
     import numpy as np
-    args = [a for a in sys.argv[1:] if a not in ("--restarts", "--tail")]
-    if "--tail" in sys.argv[1:]:
+    args = [a for a in sys.argv[1:] if a not in ("--restarts", "--tail", "--sqp")]
+    if "--sqp" in sys.argv[1:]:
+        import sqp_golden_cases as wc
+        default = "sqp_modes.npz"
+    elif "--tail" in sys.argv[1:]:
         import wave_golden_tail_cases as wc
         default = "wave_tail.npz"
     elif "--restarts" in sys.argv[1:]:
@@ -76,6 +83,8 @@ def main():
     arrays = {}
     for name in wc.CASES:
         res = wc.run_case(name)
+        if isinstance(res, tuple):   # (--sqp: with the kernel the plan names for the solve)
+            res, arrays[name + "/kernel"] = res[0], np.array(res[1])
         for k in wc.KEYS:
             arrays[name + "/" + k] = res[k]
         print("%-20s iters %s nfev %s inform %s" % (name, res["iters"].tolist(), res["nfev"].tolist(), res["inform"].tolist()), flush=True)
