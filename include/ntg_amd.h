@@ -32,6 +32,8 @@
  *                        result reproduces: the refined coefficients describe the same function
  *   ntg_batch_envelope   nothing in the reference bounds a trajectory between samples; its only dense output is SplineInterp (colloc.c:449-484),
  *                        point by point, which the result encloses: bounds of every flag entry and linear trajectory row over whole pieces of time
+ *   ntg_batch_envelope_sos  nothing in the reference bounds a row between samples; constraints.c:119-160 evaluates the trajectory rows at the
+ *                        breakpoints only: bounds of the sum-of-squares rows (obstacle clearance, thrust^2, speed^2) over whole pieces of time
  *   ntg_batch_kincar_reverse  examples/kincar.c:68-92 kincar_flat_reverse (the example's flat-to-state map), for a batch
  *   ntg(), npsoloption(), linspace(), SplineInterp(), matrix helpers: see include/ntg.h
  */
@@ -421,6 +423,56 @@ int ntg_batch_envelope(const ntg_plan *p, int batch, const double *d_x, int nsub
                        double *d_lo, double *d_hi,
                        double *d_row_lo, double *d_row_hi,
                        double *d_viol, int *d_where, void *stream);
+
+/* Certify the QUADRATIC trajectory rows over time: ntg_batch_envelope's statement "for all t", for the nonlinear trajectory rows that are
+ * sums of squares of shifted flag entries -- the obstacle row of NTG_FAM_OBSTACLE, every row of NTG_FAM_OBSTACLE_FIELD, thrust^2 and speed^2
+ * of NTG_FAM_QUADROTOR.  The solvers enforce these rows at the breakpoints only, and ntg_batch_check tells what they are at the times
+ * passed in; between two breakpoints a car can clip an obstacle.  Every flag entry is a polynomial on a knot interval, so such a row is one
+ * too, and its Bezier polygon follows exactly from the polygons ntg_batch_envelope builds by a Bezier product.  No family callback runs.
+ * Declaration.  A family declares row j of its nonlinear trajectory rows, on the host, as
+ *   c_j(z) = sum_{t < nt_j} (z[v_t] - s_t)^2,   s_t = const_t + (pidx_t >= 0 ? prm_row_j[pidx_t] : 0)
+ * with nt_j <= NTG_SOS_MAXTERMS, v_t a flag entry and prm_row_j the problem's parameter block of that row (ntg_plan_set_params).  Squares
+ * only: no weights, no bilinear terms.  The built-in families declare: OBSTACLE row 0; OBSTACLE_FIELD every row; QUADROTOR rows 0 and 1;
+ * TESTFAM row 0 (its row 1 has a cosine).  MANIP, KINCAR and VANDERPOL declare nothing.  Loaded modules declare nothing: the module
+ * descriptor has no field for it yet, so every row of a module family counts as undeclared.
+ * ntg_plan_sos_rows: flags[nnltc], 1 = row j is certified by ntg_batch_envelope_sos on this plan, 0 = no statement (the row is undeclared,
+ * or it names outputs of different basis classes and has no common pieces).  No device call.
+ * Pieces.  Pieces, npc and the range of nsub are exactly as in ntg_batch_envelope.  A row's pieces are those of the basis class of the
+ * entries it names (a row with flag 0: of the first entry it names, or of output 0).  d_q_lo / d_q_hi are [batch][nnltc][npc].
+ * Per term.  The control points beta_i, i = 0 .. d, of entry v_t on the piece come from steps 1-3 of ntg_batch_envelope, with the same
+ * arithmetic.  Then p_i = beta_i - s_t.  If the entry's derivative order is >= k its polygon is the single point 0 and p_0 = -s_t.
+ * Square, degree d -> 2d.  g_m = sum_{i+j=m} W_d[i][j] p_i p_j, i ascending, with W_d[i][j] = C(d,i) C(d,j) / C(2d,m) formed on the
+ * host from exact integer binomials and rounded once.  This is the Bezier product of the polygon with itself, not interval arithmetic.
+ * Row polygon.  Every term's polygon is degree-elevated to D = max_t 2 d_t with the formula ntg_batch_envelope states, and the polygons
+ * are summed in term order.  lo / hi are the min / max of the D + 1 points; a NaN among them stays in both (the env_min / env_max rule of
+ * ntg_batch_envelope).  Pieces past the class's own are lo = +inf, hi = -inf.  A row with flag 0 gives lo = -inf, hi = +inf on the live
+ * pieces, which is no statement.
+ * Certified violation.  d_viol [batch], d_where [batch][2] = {row, piece}: the largest max(l - lo, hi - u, 0) over certified rows and pieces,
+ * the bounds read from d_lower / d_upper [batch][nbounds] at the nnltc columns, in the nlic, nltc, nlfc, nnlic, nnltc order of
+ * ntg_batch_check (|bound| >= NTG_INF_BOUND: absent).  Ties go to the smallest row * npc + piece; a NaN wins over every number, the first
+ * NaN in that order (the env_take rule of ntg_batch_envelope); {-1, -1} where the violation is 0.  d_viol == 0 certifies, up to the
+ * rounding stated next, that every such row holds at every time of the horizon.
+ * Rounding.  With S_t = max_i |c_{o,i}| (2(k-1)/h_min)^r + |s_t| for term t (o, r the output and derivative order of v_t), each factor's
+ * control point carries at most 2^-42 S_t, the statement of ntg_batch_envelope with its factor of ten to spare.  So a product control point
+ * carries at most 2 * 2^-42 S_t^2 plus a few units in the last place of S_t^2; elevation and the sum add a few more.  The row's slack is
+ * 2^-40 * sum_t S_t^2.
+ * Any output pointer may be NULL, but not all four; d_lower / d_upper are required only for d_viol / d_where.  Stream ordered.  No scratch
+ * allocation and no floating-point atomics: results are bit-identical from call to call and independent of the batch around a problem.
+ * Per-problem parameters are read for pidx >= 0; per-problem grids are honoured, with the batch rules of ntg_batch_envelope.
+ * batch <= 0 returns 0, after the null-plan and nsub checks.  NTG_E_BADARG for a null plan or null d_x, nsub out of range, all four outputs
+ * null, violation outputs without bounds, nnltc == 0, parameters needed but not set, a batch other than the grids' or the parameters'.
+ * NTG_E_UNSUPPORTED for host-callback plans, for tables above NTG_ENVELOPE_LDS_MAX (64 KiB of LDS: the extraction tables of
+ * ntg_batch_envelope plus 385 product weights and the parameter row), for more than 8 trajectory rows, for a plan no row of which is
+ * certified (the message says the family declares none), and for d_viol / d_where when some row of the plan has flag 0 (the message names
+ * the row): a partial certificate must not read as a whole one. */
+#define NTG_SOS_MAXTERMS 4
+/* flags[nnltc]: 1 = row j is certified by ntg_batch_envelope_sos on this plan,
+ * 0 = no statement (undeclared, or names outputs of different basis classes). No device call. */
+int ntg_plan_sos_rows(const ntg_plan *p, int *flags);
+
+int ntg_batch_envelope_sos(const ntg_plan *p, int batch, const double *d_x, int nsub,
+                           const double *d_lower, const double *d_upper,
+                           double *d_q_lo, double *d_q_hi, double *d_viol, int *d_where, void *stream);
 
 /* The flat-to-state map of the kinematic car for a whole ntg_batch_interp result (examples/kincar.c:68-92 kincar_flat_reverse,
  * called per sample by the example's output loop, kincar.c:392-406): d_z [batch][ntimes][nz] -> d_state [batch][ntimes][ncars][5] =

@@ -81,6 +81,8 @@ def lib():
         L.ntg_batch_cost.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_batch_verify.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_batch_envelope.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 9
+        L.ntg_batch_envelope_sos.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        L.ntg_plan_sos_rows.argtypes = [C.c_void_p, ip]
         L.ntg_batch_refine.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_plan_set_grids.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ntg_plan_clear_grids.argtypes = [C.c_void_p]
@@ -413,6 +415,42 @@ class Plan:
             out["viol"] = torch.zeros(batch, dtype=torch.float64, device=dev); out["where"] = torch.full((batch, 2), -1, dtype=torch.int32, device=dev)
         _check(lib().ntg_batch_envelope(self.h, batch, _ptr(x), int(nsub), _ptr(lower), _ptr(upper), _ptr(out.get("lo")), _ptr(out.get("hi")),
                                         _ptr(out.get("row_lo")), _ptr(out.get("row_hi")), _ptr(out.get("viol")), _ptr(out.get("where")), self._stream()))
+        return out
+
+    def sos_rows(self) -> np.ndarray:
+        """[nnltc] int32: 1 where envelope_sos certifies the nonlinear trajectory row on this plan, 0 where it makes no statement (the
+        family does not declare the row a sum of squares, or the row names outputs of different basis classes).  See ntg_plan_sos_rows."""
+        flags = np.zeros(self.spec.nnltc, dtype=np.int32)
+        _check(lib().ntg_plan_sos_rows(self.h, flags.ctypes.data_as(ip)))
+        return flags
+
+    def envelope_sos(self, x, nsub: int = 0, lower=None, upper=None):
+        """Bounds of the sum-of-squares trajectory rows (obstacle clearance, thrust^2, speed^2) that hold at EVERY time
+        (ntg_batch_envelope_sos): x [batch, nC]; pieces as in envelope.  Returns a dict: q_lo, q_hi [batch, nnltc, npc] and, with bounds
+        [batch, nbounds], viol [batch] and where [batch, 2] = (row, piece) of the largest certified violation or (-1, -1).  A row
+        sos_rows() flags 0 comes back as (-inf, +inf) on its live pieces, and viol / where are then refused.  viol == 0 certifies every
+        nonlinear trajectory row over the whole horizon."""
+        import torch
+        sp = self.spec
+        dev = x.device
+        _check_tensor(x, dev); _check_tensor(lower, dev); _check_tensor(upper, dev)
+        if x.dim() != 2 or x.shape[1] != sp.nC:
+            raise NtgError(f"x must be [batch, {sp.nC}]")
+        batch = x.shape[0]
+        if (lower is None) != (upper is None):
+            raise NtgError("pass both bounds or neither")
+        if lower is not None and (lower.shape != (batch, sp.nbounds) or upper.shape != (batch, sp.nbounds)):
+            raise NtgError(f"bounds must be [{batch}, {sp.nbounds}]")
+        if not 0 <= int(nsub) <= ENVELOPE_MAX_NSUB:
+            raise NtgError(f"nsub must lie in 0 .. {ENVELOPE_MAX_NSUB} (NTG_ENVELOPE_MAX_NSUB)")
+        npc = max(sp.kninterv) << int(nsub)
+        # (a plan without such rows gets one row of storage: the library refuses it before it writes, an empty tensor would arrive as a null pointer)
+        out = {"q_lo": torch.empty((batch, max(sp.nnltc, 1), npc), dtype=torch.float64, device=dev)}
+        out["q_hi"] = torch.empty_like(out["q_lo"])
+        if lower is not None:
+            out["viol"] = torch.zeros(batch, dtype=torch.float64, device=dev); out["where"] = torch.full((batch, 2), -1, dtype=torch.int32, device=dev)
+        _check(lib().ntg_batch_envelope_sos(self.h, batch, _ptr(x), int(nsub), _ptr(lower), _ptr(upper), _ptr(out["q_lo"]), _ptr(out["q_hi"]),
+                                            _ptr(out.get("viol")), _ptr(out.get("where")), self._stream()))
         return out
 
     def set_grids(self, knots, bps, with_precond: bool = True):

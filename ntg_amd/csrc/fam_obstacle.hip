@@ -14,5 +14,12 @@ static const char *shape_rule(const ntg_spec &s)
 {
 	return s.nout != 2 || s.nnlic || s.nnlfc || s.nnltc > 1 ? "obstacle family: 2 outputs, at most one trajectory constraint" : nullptr;
 }
-extern const NtgFamily ntg_fam_obstacle = ntg_builtin_family<NTG_FAM_OBSTACLE>("obstacle", 2, shape_rule, fam_launch_eval, fam_launch_sqp, fam_tile, true);
+// row 0 = (x - 20)^2 + (y - 0.5)^2, a sum of squares (ntg_batch_envelope_sos)
+static int sos_rows(int row, int, NtgSosTerm *t)
+{
+	if (row != 0) return 0;
+	t[0] = {0, 20.0, -1}; t[1] = {3, 0.5, -1};
+	return 2;
+}
+extern const NtgFamily ntg_fam_obstacle = ntg_family_sos(ntg_builtin_family<NTG_FAM_OBSTACLE>("obstacle", 2, shape_rule, fam_launch_eval, fam_launch_sqp, fam_tile, true), sos_rows);
 #endif

@@ -16,5 +16,13 @@ static const char *shape_rule(const ntg_spec &s)
 	           ? "obstacle-field family: 2 outputs, 1 to 8 trajectory constraints (one per obstacle), no initial or final rows" : nullptr;
 }
 static_assert(Family<NTG_FAM_OBSTACLE_FIELD>::NNLTC == 8, "the shape rule's text says 8");
-extern const NtgFamily ntg_fam_obstacle_field = ntg_builtin_family<NTG_FAM_OBSTACLE_FIELD>("obstacle_field", 2, shape_rule, fam_launch_eval, fam_launch_sqp, fam_tile, true);
+// every row j = (x - cx_j)^2 + (y - cy_j)^2, the centre from the row's parameter block: a sum of squares (ntg_batch_envelope_sos)
+static int sos_rows(int, int, NtgSosTerm *t)
+{
+	t[0] = {0, 0.0, 0}; t[1] = {3, 0.0, 1};
+	return 2;
+}
+static_assert(Family<NTG_FAM_OBSTACLE_FIELD>::NPARAM_ROW == 2, "sos_rows reads cx_j, cy_j");
+extern const NtgFamily ntg_fam_obstacle_field =
+	ntg_family_sos(ntg_builtin_family<NTG_FAM_OBSTACLE_FIELD>("obstacle_field", 2, shape_rule, fam_launch_eval, fam_launch_sqp, fam_tile, true), sos_rows);
 #endif

@@ -44,5 +44,13 @@ static const char *shape_rule(const ntg_spec &s)
 {
 	return s.nout != 4 || s.nnlic || s.nnlfc || s.nnltc > 2 ? "quadrotor family: 4 outputs, at most two trajectory constraints" : nullptr;
 }
-extern const NtgFamily ntg_fam_quadrotor = ntg_builtin_family<NTG_FAM_QUADROTOR>("quadrotor", 4, shape_rule, fam_launch_eval, fam_launch_sqp, fam_tile, false, true);
+// row 0 = x''^2 + y''^2 + (z'' + g)^2, row 1 = x'^2 + y'^2 + z'^2: sums of squares (ntg_batch_envelope_sos)
+static int sos_rows(int row, int, NtgSosTerm *t)
+{
+	if (row == 0) { t[0] = {2, 0.0, -1}; t[1] = {7, 0.0, -1}; t[2] = {12, -Family<NTG_FAM_QUADROTOR>::G, -1}; return 3; }
+	if (row == 1) { t[0] = {1, 0.0, -1}; t[1] = {6, 0.0, -1}; t[2] = {11, 0.0, -1}; return 3; }
+	return 0;
+}
+extern const NtgFamily ntg_fam_quadrotor =
+	ntg_family_sos(ntg_builtin_family<NTG_FAM_QUADROTOR>("quadrotor", 4, shape_rule, fam_launch_eval, fam_launch_sqp, fam_tile, false, true), sos_rows);
 #endif

@@ -34,5 +34,12 @@ static const char *shape_rule(const ntg_spec &s)
 {
 	return s.nnlic > 1 || s.nnltc > 2 || s.nnlfc > 1 ? "testfam has 1/2/1 nonlinear constraints" : nullptr;
 }
-extern const NtgFamily ntg_fam_testfam = ntg_builtin_family<NTG_FAM_TESTFAM>("testfam", 0, shape_rule, fam_launch_eval, fam_launch_sqp, fam_tile);
+// row 0 = z_0^2 + z_L^2 (L the last output) is a sum of squares (ntg_batch_envelope_sos); row 1 has a cosine and is not declared
+static int sos_rows(int row, int nout, NtgSosTerm *t)
+{
+	if (row != 0) return 0;
+	t[0] = {0, 0.0, -1}; t[1] = {3 * (nout - 1), 0.0, -1};
+	return 2;
+}
+extern const NtgFamily ntg_fam_testfam = ntg_family_sos(ntg_builtin_family<NTG_FAM_TESTFAM>("testfam", 0, shape_rule, fam_launch_eval, fam_launch_sqp, fam_tile), sos_rows);
 #endif

@@ -43,6 +43,13 @@ struct ntg_family_module_desc {
 };
 typedef const ntg_family_module_desc *(*ntg_family_module_entry_fn)(void);
 
+// A nonlinear trajectory row declared as a sum of squares of shifted flag entries (ntg_batch_envelope_sos):
+//   c_j(z) = sum_{t < nt_j} (z[v_t] - s_t)^2,   s_t = shift_t + (pidx_t >= 0 ? prm_row_j[pidx_t] : 0)
+// v: flag entry; prm_row_j: the problem's parameter block of row j (params + j * nparam_row).  Squares only: no weights, no bilinear terms.
+struct NtgSosTerm { int v; double shift; int pidx; };
+// the declaration of row j for a plan with nout outputs: fills t[0 .. NTG_SOS_MAXTERMS) and returns nt_j, 0: the row is not declared
+typedef int (*ntg_sos_decl_fn)(int row, int nout, NtgSosTerm *t);
+
 // One problem family as the host sees it.  A built-in family defines its descriptor in its own fam_*.hip, from Family<FAM>'s constants
 // (ntg_builtin_family, families.hpp); a loaded module's is filled from its ntg_family_module_desc at load.
 struct NtgFamily {
@@ -64,7 +71,11 @@ struct NtgFamily {
 	ntg_module_check_fn launch_check;
 	ntg_module_cost_fn launch_cost;
 	ntg_module_verify_fn launch_verify;
+	// which of the family's trajectory rows are sums of squares (nullptr: none).  A built-in family sets it next to its
+	// ntg_builtin_family(...) call (ntg_family_sos); a loaded module declares nothing: ntg_family_module_desc has no field for it
+	ntg_sos_decl_fn sos;
 };
+constexpr NtgFamily ntg_family_sos(NtgFamily f, ntg_sos_decl_fn sos) { f.sos = sos; return f; }
 
 // the registry (family_registry.cpp): ids 0 .. of the built-in families, ids >= NTG_FAM_MODULE_BASE of loaded modules; nullptr for any
 // other id (NTG_FAM_HOST included: the host-callback path is not a device family)

@@ -19,6 +19,8 @@
 //   kkt_kernel      first-order optimality residuals of a batch on the banded Jacobian (kkt.hpp)
 //   envelope_*      bounds of every flag entry and linear trajectory row over whole pieces of the
 //                   knot intervals, from the Bezier control polygons (envelope.hpp)
+//   envelope_sos_*  the same for the nonlinear trajectory rows declared as sums of squares, by the
+//                   Bezier product of those polygons (envelope_sos.hpp)
 //
 // Mapping to CDNA4: one workgroup per problem; breakpoints (then coefficients) across the
 // lanes; basis tables, knots/breakpoints and the coefficient vector staged in LDS; the only
@@ -31,6 +33,7 @@
 #include "family_module.hpp"
 #include "refine.hpp"
 #include "envelope.hpp"
+#include "envelope_sos.hpp"
 #include "kkt.hpp"
 #include "verify.hpp"
 
@@ -639,6 +642,28 @@ hipError_t ntg_launch_envelope(const EnvArgs &A, int ncu, hipStream_t st)
 	if (lds > NTG_ENVELOPE_LDS_MAX || A.kmax > NTG_MAX_ORDER) return hipErrorInvalidValue;   // (ntg_batch_envelope refuses such a plan before it gets here)
 	if (A.batch <= 0) return hipSuccess;
 	return A.kmax <= 6 ? launch_envelope<6>(A, ncu, lds, st) : launch_envelope<NTG_MAX_ORDER>(A, ncu, lds, st);
+}
+
+// ntg_batch_envelope_sos (envelope_sos.hpp): the instances and the launch shapes of ntg_launch_envelope.
+// hipErrorInvalidValue: the tables exceed the LDS.
+template <int KM>
+static hipError_t launch_envelope_sos(const SosArgs &A, int ncu, size_t lds, hipStream_t st)
+{
+	if (A.pp) {
+		const int groups = (A.batch + NTG_ENVELOPE_NT / 64 - 1) / (NTG_ENVELOPE_NT / 64);
+		hipLaunchKernelGGL((envelope_sos_pp_kernel<NTG_ENVELOPE_NT, KM>), dim3(std::min(groups, 8 * ncu)), dim3(NTG_ENVELOPE_NT), lds, st, A);
+	} else {
+		const int grid = std::max(1, std::min((A.batch + 3) / 4, 8 * ncu));
+		hipLaunchKernelGGL((envelope_sos_shared_kernel<NTG_ENVELOPE_NT, KM>), dim3(grid), dim3(NTG_ENVELOPE_NT), lds, st, A);
+	}
+	return hipGetLastError();
+}
+hipError_t ntg_launch_envelope_sos(const SosArgs &A, int ncu, hipStream_t st)
+{
+	const size_t lds = ntg_envelope_sos_lds(A);
+	if (lds > NTG_ENVELOPE_LDS_MAX || A.kmax > NTG_MAX_ORDER || A.nrow > NTG_SOS_MAXROWS) return hipErrorInvalidValue;   // (ntg_batch_envelope_sos refuses such a plan before it gets here)
+	if (A.batch <= 0) return hipSuccess;
+	return A.kmax <= 6 ? launch_envelope_sos<6>(A, ncu, lds, st) : launch_envelope_sos<NTG_MAX_ORDER>(A, ncu, lds, st);
 }
 
 // Flat flag -> state and input of the kinematic car, the map of examples/kincar.c:68-92 (kincar_flat_reverse), for every car

@@ -234,3 +234,36 @@ static inline size_t ntg_envelope_lds(const EnvArgs &A)
 {
 	return (size_t)(A.pp ? NTG_ENVELOPE_NT / 64 : 1) * (size_t)(A.ne + A.nC + A.lmax + 1) * 8;
 }
+
+// sum-of-squares row envelope (envelope_sos.hpp): certified bounds of the nonlinear trajectory rows declared as sums of squares of shifted
+// flag entries.  c, knots, ne, lmax, kmax as in EnvArgs.  row[j]: nt terms, the basis class cl of the entries it names, the degree D of its
+// polygon, flag = 1: certified (0: no statement, nothing else of the row is read).  term[j][t]: coefficient offset iC of the output, its
+// derivative order r, the shift's constant s0 and the index poff into the problem's parameter row (np doubles at prm + b pp_prm) or -1.
+// w: the product tables W_d[i][j] = C(d,i) C(d,j) / C(2d,i+j), d = 0 .. NTG_MAX_ORDER - 1, the upper triangles (i <= j) row by row, d
+// ascending; the kernels unfold them into LDS.  lower / upper [batch][nbounds], the rows' slots start at slot0.
+#define NTG_SOS_MAXROWS 8
+#define NTG_SOS_WTRI (NTG_MAX_ORDER * (NTG_MAX_ORDER + 1) * (NTG_MAX_ORDER + 2) / 6)     // doubles of the triangles
+#define NTG_SOS_WFULL (NTG_MAX_ORDER * (NTG_MAX_ORDER + 1) * (2 * NTG_MAX_ORDER + 1) / 6) // doubles of the unfolded tables
+struct SosRow { int nt, cl, D, flag; };
+struct SosTerm { int iC, r, poff, pad; double s0; };
+struct SosArgs {
+	int nC, nclass, batch, nsub, npc, nrow, nbounds, slot0, pp, ne, lmax, kmax, np, pad;
+	long long pp_prm;
+	EnvClass c[NTG_MAX_OUT];
+	const double *knots[NTG_MAX_OUT];
+	const double *x, *prm, *lower, *upper;
+	double *q_lo, *q_hi, *viol; int *where;
+	SosRow row[NTG_SOS_MAXROWS];
+	SosTerm term[NTG_SOS_MAXROWS][NTG_SOS_MAXTERMS];
+	double w[NTG_SOS_WTRI];
+};
+static_assert(sizeof(SosArgs) <= 4096, "SosArgs travels as a kernel argument");
+// table of degree d: offset of its triangle in SosArgs::w, of its unfolded [d + 1][d + 1] form in LDS
+static inline __host__ __device__ int ntg_sos_wtri(int d) { return d * (d + 1) * (d + 2) / 6; }
+static inline __host__ __device__ int ntg_sos_wfull(int d) { return d * (d + 1) * (2 * d + 1) / 6; }
+// dynamic LDS: the unfolded product tables, then the extraction tables, one coefficient row, one parameter row and one break sequence -- of
+// the workgroup (shared grids) or of each of its waves
+static inline size_t ntg_envelope_sos_lds(const SosArgs &A)
+{
+	return ((size_t)NTG_SOS_WFULL + (size_t)(A.pp ? NTG_ENVELOPE_NT / 64 : 1) * (size_t)(A.ne + A.nC + A.np + A.lmax + 1)) * 8;
+}

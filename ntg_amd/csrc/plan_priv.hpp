@@ -10,6 +10,7 @@
 //   plan_cost.cpp   ntg_batch_cost: the running cost of a batch at arbitrary times under a quadrature
 //   plan_verify.cpp ntg_batch_verify: a family's analytic derivatives against central differences at the breakpoints
 //   plan_envelope.cpp ntg_batch_envelope: certified bounds of the flag entries and linear trajectory rows over the whole horizon
+//   plan_envelope_sos.cpp ntg_batch_envelope_sos: the same for the nonlinear trajectory rows a family declares as sums of squares
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
