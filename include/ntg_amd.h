@@ -34,6 +34,8 @@
  *                        point by point, which the result encloses: bounds of every flag entry and linear trajectory row over whole pieces of time
  *   ntg_batch_envelope_sos  nothing in the reference bounds a row between samples; constraints.c:119-160 evaluates the trajectory rows at the
  *                        breakpoints only: bounds of the sum-of-squares rows (obstacle clearance, thrust^2, speed^2) over whole pieces of time
+ *   ntg_batch_extrema    nothing in the reference looks for a row's extremum between samples; constraints.c:119-160 evaluates the trajectory rows
+ *                        at the breakpoints only: the minimum and maximum of every certifiable row over the horizon, enclosed to a tolerance, with their times
  *   ntg_batch_kincar_reverse  examples/kincar.c:68-92 kincar_flat_reverse (the example's flat-to-state map), for a batch
  *   ntg(), npsoloption(), linspace(), SplineInterp(), matrix helpers: see include/ntg.h
  */
@@ -473,6 +475,82 @@ int ntg_plan_sos_rows(const ntg_plan *p, int *flags);
 int ntg_batch_envelope_sos(const ntg_plan *p, int batch, const double *d_x, int nsub,
                            const double *d_lower, const double *d_upper,
                            double *d_q_lo, double *d_q_hi, double *d_viol, int *d_where, void *stream);
+
+/* Certified row EXTREMA over time, by bisection: the global minimum and maximum of each certifiable trajectory row over the horizon, each
+ * enclosed to a tolerance and each with a witness time.  ntg_batch_envelope and ntg_batch_envelope_sos cut every knot interval into the same
+ * 2^nsub pieces; a row that sits on its bound at a breakpoint (the obstacle row of a solved problem) is then never certified, because the
+ * polygon of the piece holding that breakpoint lies below the bound by a term of order (piece width)^2.  This call bisects only the pieces
+ * that can still hold the extremum and says by how much the row is violated between breakpoints, no more than that, and WHEN.
+ * Rows.  nrow = nltc + nnltc, the linear trajectory rows first: ntg_batch_check's numbering.  ntg_plan_extrema_rows: flags[nrow], no
+ * device call.  A linear row has flag 1 when the outputs it names (non-zero ltc[i][v]) belong to one basis class; a row of zeros counts as
+ * class 0 and has flag 1.  A nonlinear row has the flag ntg_plan_sos_rows gives it.  Loaded modules declare no sum of squares yet: their
+ * linear rows are certified, their nonlinear rows are not.
+ * Outputs, any may be NULL but not all six:
+ *   d_ext     [batch][nrow][4]  {min_lo, min_hi, max_lo, max_hi}
+ *   d_when    [batch][nrow][2]  {t_min, t_max}
+ *   d_status  [batch][nrow]     NTG_EXTREMA_OK / _DEPTH / _FULL / _NAN / _NONE
+ *   d_npieces [batch][nrow]     polygons evaluated
+ *   d_viol    [batch][2]        {attained, certified}
+ *   d_where   [batch][2]        row of each of the two violations; ties to the smallest row; -1 where the figure is 0
+ * Definition, per problem and per row with flag 1.
+ * 1. Level-0 pieces.  The level-0 pieces are the l knot intervals of the row's basis class (after ntg_plan_set_grids: the problem's own
+ *    intervals).  The polygon B_0 .. B_D of the row on interval j is the row polygon of ntg_batch_envelope (linear rows) or
+ *    ntg_batch_envelope_sos (nonlinear rows) at nsub = 0, piece j, formed by the same sequence of operations.  So with max_depth = 0, min_lo
+ *    equals the minimum over j of those calls' row_lo / q_lo and max_hi equals the maximum of their row_hi / q_hi, bit for bit.  A row of zeros
+ *    has D = 0 and B_0 = 0.
+ * 2. Indexing and state.  A piece at level lambda of interval j has an index i in [0, 2^lambda); its ends lie at the local parameters
+ *    i / 2^lambda and (i + 1) / 2^lambda, and B_0 and B_D are the row's values at those ends.  plo and phi are the env_min / env_max of its
+ *    D + 1 points.  The row keeps four quantities: U, the smallest end value seen, with its time; V, the largest end value seen, with its time;
+ *    Rlo, the smallest plo of a retired piece (initially +inf); Rhi, the largest phi of a retired piece (initially -inf).  The time of an end
+ *    is kn[j] + hh[j] * ((double)i / (double)(1 << lambda)) with hh[j] = kn[j + 1] - kn[j], the product and the sum rounded separately (no
+ *    fused multiply-add); an end at local parameter 1 takes kn[j + 1].  On equal values the smaller time wins, so minimum and maximum do not
+ *    depend on the order of the pieces.  A NaN end value is never taken.
+ * 3. Level lambda.  Update U and V with both ends of every piece of the level.  Then decide each piece: a piece is open if
+ *    (sides & 1) and plo < U - tol, or (sides & 2) and phi > V + tol.  Every other piece retires into Rlo / Rhi.
+ *    No open piece: status OK, stop.  lambda == max_depth: status DEPTH, the open pieces retire, stop.  More than NTG_EXTREMA_CAP open
+ *    pieces: status FULL, they retire, stop.  Otherwise every open piece is split at the middle by de Casteljau: each new point is
+ *    0.5 * (a + b), the two end points of a polygon are carried over, not recomputed; the children form level lambda + 1.
+ * 4. Result.  min_lo = Rlo, min_hi = U, max_lo = V, max_hi = Rhi; t_min and t_max are the times of U and V; npieces is the number of
+ *    polygons evaluated over all levels (l at level 0, two per open piece afterwards).  Always min_lo <= min over t of the row <= min_hi, and
+ *    the same for the maximum, up to the rounding below.  min_hi and max_lo are attained values.  With status OK and the side asked for,
+ *    min_hi - min_lo <= tol.  A side not asked for never opens a piece, but its two numbers are kept from the pieces visited and are still valid.
+ * 5. NaN.  A NaN in any plo / phi makes all four numbers and both times NaN, with status NAN.  Such a piece is never open, the levels go on
+ *    without it, and npieces counts as usual.
+ * 6. Rows with flag 0: (-inf, +inf, -inf, +inf), times NaN, status NONE, npieces 0.
+ * 7. Violation.  Bounds d_lower / d_upper [batch][nbounds] are read as ntg_batch_check reads them (|bound| >= NTG_INF_BOUND is absent).
+ *    Both figures are maxima over the rows: attained = max(l - min_hi, max_lo - u, 0) -- at d_when the row really violates by this much;
+ *    certified = max(l - min_lo, max_hi - u, 0) -- no time violates by more.  certified == 0 certifies the plan's rows over the whole horizon.
+ *    A NaN wins over every number (the env_take rule of ntg_batch_envelope).  Both are refused (NTG_E_UNSUPPORTED, naming the row) when some
+ *    row has flag 0: the rule of ntg_batch_envelope_sos.
+ * Rounding.  The level-0 polygon carries the slack of the call it comes from.  A halving adds one rounding per new point, of at most
+ * 2^-53 max|B|; a point passes at most D <= 18 of them per level, over at most 30 levels: less than 2^-43 max|B|, and max|B| <= sum_t S_t^2
+ * for a quadratic row.  So the slack is 2^-39 * sum_t S_t^2 for a quadratic row (S_t as in ntg_batch_envelope_sos) and twice
+ * ntg_batch_envelope's row slack for a linear one.
+ * Arguments.  tol is finite and >= 0; 0 <= max_depth <= NTG_EXTREMA_MAX_DEPTH; sides is one of 1 (minimum), 2 (maximum), 3 (both).
+ * Stream ordered, without scratch in HBM and without floating-point atomics: a wavefront owns a problem and keeps the open pieces of one
+ * row in a work list in LDS.  Results are bit-identical from call to call and independent of the batch around a problem.  Per-problem
+ * parameters and per-problem grids are honoured with the batch rules of ntg_batch_envelope_sos.
+ * batch <= 0 returns 0 after the null-plan and argument checks.  NTG_E_BADARG for a null plan or null d_x, an argument outside the ranges
+ * above, all outputs null, violation outputs without bounds, nrow == 0, parameters needed but not set, a batch other than the grids' or the
+ * parameters'.  NTG_E_UNSUPPORTED for host-callback plans, for a plan without any flagged row, for nnltc > 8, and for tables and work lists
+ * above 158 KiB of LDS: 385 product weights, sum over basis classes of l (k^2 + 2) + 1, and per wavefront of four nC + the parameter row +
+ * 64 (D_max + 2) doubles with D_max = 10 (largest order <= 6) or 18 -- on per-problem grids the class tables count per wavefront too. */
+#define NTG_EXTREMA_MAX_DEPTH 30
+#define NTG_EXTREMA_CAP 64          /* open pieces of one row at one level */
+#define NTG_EXTREMA_OK 0            /* every piece closed: the tolerance is met */
+#define NTG_EXTREMA_DEPTH 1         /* stopped at max_depth with pieces still open */
+#define NTG_EXTREMA_FULL 2          /* stopped because more than NTG_EXTREMA_CAP pieces were open */
+#define NTG_EXTREMA_NAN 3
+#define NTG_EXTREMA_NONE (-1)       /* no statement for this row */
+
+/* flags[nltc + nnltc]: 1 = ntg_batch_extrema certifies the row on this plan, 0 = no statement. No device call. */
+int ntg_plan_extrema_rows(const ntg_plan *p, int *flags);
+
+int ntg_batch_extrema(const ntg_plan *p, int batch, const double *d_x,
+                      double tol, int max_depth, int sides,
+                      const double *d_lower, const double *d_upper,
+                      double *d_ext, double *d_when, int *d_status, int *d_npieces,
+                      double *d_viol, int *d_where, void *stream);
 
 /* The flat-to-state map of the kinematic car for a whole ntg_batch_interp result (examples/kincar.c:68-92 kincar_flat_reverse,
  * called per sample by the example's output loop, kincar.c:392-406): d_z [batch][ntimes][nz] -> d_state [batch][ntimes][ncars][5] =

@@ -83,6 +83,8 @@ def lib():
         L.ntg_batch_envelope.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 9
         L.ntg_batch_envelope_sos.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7
         L.ntg_plan_sos_rows.argtypes = [C.c_void_p, ip]
+        L.ntg_batch_extrema.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_int] + [C.c_void_p] * 9
+        L.ntg_plan_extrema_rows.argtypes = [C.c_void_p, ip]
         L.ntg_batch_refine.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_plan_set_grids.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ntg_plan_clear_grids.argtypes = [C.c_void_p]
@@ -453,6 +455,41 @@ class Plan:
                                             _ptr(out.get("viol")), _ptr(out.get("where")), self._stream()))
         return out
 
+    def extrema_rows(self) -> np.ndarray:
+        """[nltc + nnltc] int32: 1 where extrema certifies the trajectory row on this plan (a linear row whose outputs share a basis class,
+        a nonlinear row sos_rows() flags), 0 where it makes no statement.  See ntg_plan_extrema_rows."""
+        flags = np.zeros(self.spec.nltc + self.spec.nnltc, dtype=np.int32)
+        _check(lib().ntg_plan_extrema_rows(self.h, flags.ctypes.data_as(ip)))
+        return flags
+
+    def extrema(self, x, tol, max_depth: int = 30, sides: int = 3, lower=None, upper=None):
+        """The minimum and maximum of every certifiable trajectory row over the whole horizon, each enclosed to tol, by bisection
+        (ntg_batch_extrema): x [batch, nC]; rows are the nltc linear trajectory rows, then the nnltc nonlinear ones.  Returns a dict: ext
+        [batch, nrow, 4] = (min_lo, min_hi, max_lo, max_hi), when [batch, nrow, 2] = (t_min, t_max), the times where min_hi and max_lo are
+        attained, status [batch, nrow] (EXTREMA_OK / _DEPTH / _FULL / _NAN / _NONE), npieces [batch, nrow] and, with bounds [batch, nbounds],
+        viol [batch, 2] = (attained, certified) and where [batch, 2], the row of each or -1.  sides: 1 the minimum, 2 the maximum, 3 both.
+        viol[:, 1] == 0 certifies every trajectory row over the whole horizon; a row extrema_rows() flags 0 comes back as
+        (-inf, +inf, -inf, +inf), and viol / where are then refused."""
+        import torch
+        sp = self.spec
+        dev = x.device
+        _check_tensor(x, dev); _check_tensor(lower, dev); _check_tensor(upper, dev)
+        if x.dim() != 2 or x.shape[1] != sp.nC:
+            raise NtgError(f"x must be [batch, {sp.nC}]")
+        batch = x.shape[0]
+        if (lower is None) != (upper is None):
+            raise NtgError("pass both bounds or neither")
+        if lower is not None and (lower.shape != (batch, sp.nbounds) or upper.shape != (batch, sp.nbounds)):
+            raise NtgError(f"bounds must be [{batch}, {sp.nbounds}]")
+        nrow = max(sp.nltc + sp.nnltc, 1)   # (a plan without rows gets one row of storage: the library refuses it before it writes)
+        out = {"ext": torch.empty((batch, nrow, 4), dtype=torch.float64, device=dev), "when": torch.empty((batch, nrow, 2), dtype=torch.float64, device=dev),
+               "status": torch.empty((batch, nrow), dtype=torch.int32, device=dev), "npieces": torch.empty((batch, nrow), dtype=torch.int32, device=dev)}
+        if lower is not None:
+            out["viol"] = torch.zeros((batch, 2), dtype=torch.float64, device=dev); out["where"] = torch.full((batch, 2), -1, dtype=torch.int32, device=dev)
+        _check(lib().ntg_batch_extrema(self.h, batch, _ptr(x), float(tol), int(max_depth), int(sides), _ptr(lower), _ptr(upper), _ptr(out["ext"]), _ptr(out["when"]),
+                                       _ptr(out["status"]), _ptr(out["npieces"]), _ptr(out.get("viol")), _ptr(out.get("where")), self._stream()))
+        return out
+
     def set_grids(self, knots, bps, with_precond: bool = True):
         """Per-problem grids: knots [batch, ninterv+1], bps [batch, nbps] (device, float64).  See ntg_plan_set_grids."""
         _check_tensor(knots, knots.device); _check_tensor(bps, bps.device)
@@ -560,6 +597,8 @@ class Plan:
 
 
 ENVELOPE_MAX_NSUB = 6   # NTG_ENVELOPE_MAX_NSUB
+EXTREMA_MAX_DEPTH, EXTREMA_CAP = 30, 64   # NTG_EXTREMA_MAX_DEPTH, NTG_EXTREMA_CAP
+EXTREMA_OK, EXTREMA_DEPTH, EXTREMA_FULL, EXTREMA_NAN, EXTREMA_NONE = 0, 1, 2, 3, -1   # NTG_EXTREMA_* status codes
 
 
 def envelope_pieces(spec_or_knots, o: int = 0, nsub: int = 0) -> np.ndarray:

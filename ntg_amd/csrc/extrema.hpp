@@ -1,0 +1,428 @@
+// extrema.hpp -- ntg_batch_extrema: the global minimum and maximum over the horizon of every certifiable trajectory row, each enclosed to a
+// tolerance and each with the time of the attained value, by adaptive bisection of the row's Bezier polygons.  The fixed subdivision of
+// envelope.hpp / envelope_sos.hpp spends 2^nsub polygons on every knot interval; here only the pieces that can still hold the extremum are
+// halved, so the work follows the data: a per-row work list in LDS, compacted at every level.
+//
+// Per (problem, row), the definition of include/ntg_amd.h:
+//   level 0   the row's polygon on every knot interval j of its basis class: env_rows' sequence of operations for a linear row, sos_rows' for
+//             a sum-of-squares row, both at nsub = 0 (ext_poly_lin / ext_poly_sos restate them; the depth-0 test holds them to it bit for bit).
+//   level L   U / V = smallest / largest end value seen, with its time (smaller time on equal values): every lane folds in the ends of its
+//             pieces, the wave reduces by the butterfly.  A piece is open if its polygon reaches below U - tol (above V + tol); the others
+//             retire into Rlo / Rhi.  An open piece is split in the middle by de Casteljau (0.5 * (a + b) per new point, the ends carried over).
+//   The loop ends when no piece is open (OK), at max_depth (DEPTH) or with more than NTG_EXTREMA_CAP open pieces (FULL).
+// A wavefront owns a problem and walks its rows one after the other.  Level 0 is a strided loop over the intervals; afterwards lane p takes
+// parent p of the work list, splits it in registers and evaluates both children.  Open children go back into the list at the position the
+// ballots of the wave give them: parent order first, left child first.  The list is updated in place: every lane has its parent in
+// registers before any lane stores a child (the loads of a level precede its stores in program order, and LDS operations of one wave complete
+// in order), so there is no workgroup barrier inside the level loop and nothing waits on data: the level loop runs at most max_depth + 1 times.
+//
+//   extrema_shared_kernel  plans on their own grid: persistent workgroups of four waves; the row, term and class tables, the product tables,
+//                          the extraction weights and the breaks of every basis class are built once into LDS; every wave then streams problems
+//                          with its own x row, parameter row and work list.
+//   extrema_pp_kernel      per-problem grids: the same, with breaks and weights of the wave's own problem.
+// No scratch in HBM, no atomics, nothing depends on the batch around a problem.  Every private array is indexed by unrolled loop counters only.
+#pragma once
+#include "envelope_sos.hpp"
+
+// (value, time) minimum / maximum: on equal values the smaller time; a NaN is never taken
+__device__ __forceinline__ void ext_take_min(double &v, double &t, double ov, double ot) { if (ov < v || (ov == v && ot < t)) { v = ov; t = ot; } }
+__device__ __forceinline__ void ext_take_max(double &v, double &t, double ov, double ot) { if (ov > v || (ov == v && ot < t)) { v = ov; t = ot; } }
+template <int BIT>
+__device__ __forceinline__ void ext_xchg_step(double &u, double &tu, double &v, double &tv)
+{
+	const double ou = lane_xchg<BIT>(u), otu = lane_xchg<BIT>(tu), ov = lane_xchg<BIT>(v), otv = lane_xchg<BIT>(tv);
+	ext_take_min(u, tu, ou, otu); ext_take_max(v, tv, ov, otv);
+}
+// every lane gets the wave's (U, tU), (V, tV)
+__device__ __forceinline__ void ext_wave_ends(double &u, double &tu, double &v, double &tv)
+{
+	ext_xchg_step<1>(u, tu, v, tv); ext_xchg_step<2>(u, tu, v, tv); ext_xchg_step<4>(u, tu, v, tv);
+	ext_xchg_step<8>(u, tu, v, tv); ext_xchg_step<16>(u, tu, v, tv); ext_xchg_step<32>(u, tu, v, tv);
+}
+template <int BIT>
+__device__ __forceinline__ void ext_range_step(double &lo, double &hi)
+{
+	const double ol = lane_xchg<BIT>(lo), oh = lane_xchg<BIT>(hi);
+	if (ol < lo) lo = ol;
+	if (oh > hi) hi = oh;
+}
+__device__ __forceinline__ void ext_wave_range(double &lo, double &hi)
+{
+	ext_range_step<1>(lo, hi); ext_range_step<2>(lo, hi); ext_range_step<4>(lo, hi);
+	ext_range_step<8>(lo, hi); ext_range_step<16>(lo, hi); ext_range_step<32>(lo, hi);
+}
+
+// time of end i / 2^lam of interval j (inv = 2^-lam): product and sum rounded separately, the interval's own end at local parameter 1
+__device__ __forceinline__ double ext_time(const double *kn, const double *hh, int j, int i, int lam, double inv)
+{
+#pragma clang fp contract(off)
+	const double f = hh[j] * ((double)i * inv);
+	return i == (1 << lam) ? kn[j + 1] : kn[j] + f;
+}
+
+// point D of a polygon, by unrolled counters
+template <int KD>
+__device__ __forceinline__ double ext_last(const EnvPoly<KD> &P, int D)
+{
+	long long v = 0;   // (bits of the one point taken, zeros of the others: a chain of "if (s == D) v = P.b[s]" is compiled into an indexed load, which puts P in scratch)
+#pragma unroll
+	for (int s = 0; s < KD; s++) v |= s == D ? __double_as_longlong(P.b[s]) : 0ll;
+	return __longlong_as_double(v);
+}
+
+// polygon of linear row lr (class cl, degree D) on knot interval j: env_rows' operations at nsub = 0
+template <int KM>
+__device__ __forceinline__ void ext_poly_lin(const ExtArgs &A, const double *lr, int cl, int D, const EnvClass C, const double *tab, const double *xrow, int j,
+                                             EnvPoly<2 * KM - 1> &S)
+{
+	const double h = tab[C.hoff + j];
+	EnvPoly<KM> L;
+#pragma unroll
+	for (int s = 0; s < KM; s++) L.b[s] = 0.0;
+	for (int o = 0; o < A.nout; o++) {
+		if (A.cls[o] != cl) continue;
+		const double *lo_r = lr + A.iz[o];
+		bool any = false;
+		for (int r = 0; r < A.d[o] && r < C.k; r++) any = any || lo_r[r] != 0.0;
+		if (!any) continue;
+		EnvPoly<KM> P;
+		P.extract(tab + C.eoff + j * C.k * C.k, xrow + A.iC[o] + C.k - 1 + j * (C.k - C.m), C.k);
+		for (int r = 0; r < A.d[o] && r < C.k; r++) {
+			const int d = C.k - 1 - r;
+			if (r > 0) P.diff(d + 1, h);
+			const double w = lo_r[r];
+			if (w != 0.0) {
+				EnvPoly<KM> Q = P;
+				for (int t = d; t < D; t++) Q.elevate(t);
+#pragma unroll
+				for (int s = 0; s < KM; s++) { if (s <= D) L.b[s] += w * Q.b[s]; }
+			}
+		}
+	}
+#pragma unroll
+	for (int s = 0; s < 2 * KM - 1; s++) S.b[s] = 0.0;
+#pragma unroll
+	for (int s = 0; s < KM; s++) S.b[s] = L.b[s];
+}
+
+// polygon of sum-of-squares row `row` on knot interval j: sos_rows' operations at nsub = 0
+template <int KM>
+__device__ __forceinline__ void ext_poly_sos(const SosTables &T, int row, const SosRow R, const EnvClass C, const double *wl, const double *tab, const double *xrow,
+                                             const double *prow, int j, EnvPoly<2 * KM - 1> &S)
+{
+	constexpr int KD = 2 * KM - 1;
+	const double h = tab[C.hoff + j];
+#pragma unroll
+	for (int s = 0; s < KD; s++) S.b[s] = 0.0;
+	for (int t = 0; t < R.nt; t++) {
+		const SosTerm Q = T.term[row][t];
+		const double sh = Q.s0 + (Q.poff >= 0 ? prow[Q.poff] : 0.0);
+		EnvPoly<KM> P;
+		int d = C.k - 1 - Q.r;
+		if (d >= 0) {
+			P.extract(tab + C.eoff + j * C.k * C.k, xrow + Q.iC + C.k - 1 + j * (C.k - C.m), C.k);
+			for (int r = 1; r <= Q.r; r++) P.diff(C.k - r, h);
+		} else {   // a derivative of order >= k: the zero polynomial
+			d = 0;
+			P.b[0] = 0.0;
+		}
+#pragma unroll
+		for (int s = 0; s < KM; s++) P.b[s] = s <= d ? P.b[s] - sh : 0.0;
+		const double *W = wl + ntg_sos_wfull(d);
+		if (2 * d == R.D) sos_square_into<KM>(S, P, W, d, true);
+		else {   // a term of lower degree than the row: its polygon whole, elevated, then added
+			EnvPoly<KD> G;
+			sos_square_into<KM>(G, P, W, d, false);
+			for (int u = 2 * d; u < R.D; u++) G.elevate(u);
+#pragma unroll
+			for (int s = 0; s < KD; s++) { if (s <= R.D) S.b[s] += G.b[s]; }
+		}
+	}
+}
+
+// what a wave works with: the workgroup's (or its own) tables and its own rows and work list, all in LDS
+struct ExtLds {
+	const double *wl, *tab, *kns, *xrow, *prow;
+	double *list;        // [NTG_EXTREMA_CAP][2 KM - 1]
+	long long *keys;     // [NTG_EXTREMA_CAP]: interval << 32 | index of the piece at its level
+};
+
+// one row of problem b.  res = {min_lo, min_hi, max_lo, max_hi}, tw = {t_min, t_max}; every lane returns the same figures
+template <int KM>
+__device__ __forceinline__ void ext_row(const ExtArgs &A, const SosTables &T, const ExtLds &M, int row, int lane, double (&res)[4], double (&tw)[2], int &status, int &npieces)
+{
+	constexpr int KD = 2 * KM - 1;
+	const bool lin = row < A.nltc;
+	const double *lr = A.ltc + (size_t)(lin ? row : 0) * A.nz;
+	const SosRow R = T.row[lin ? 0 : row - A.nltc];   // (a linear row reads none of it)
+	int cl = -1, D = -1, flag = 1;
+	if (lin) {   // the row's basis class and degree as env_rows finds them; flag 0: it names outputs of different classes
+		int first = -1;
+		for (int o = 0; o < A.nout; o++) {
+			const int k = T.c[A.cls[o]].k;
+			for (int r = 0; r < A.d[o]; r++) {
+				if (lr[A.iz[o] + r] == 0.0) continue;
+				if (first < 0) first = o;
+				else if (A.cls[o] != A.cls[first]) flag = 0;
+				if (r < k) { if (cl < 0) cl = A.cls[o]; D = max(D, k - 1 - r); }
+			}
+		}
+		if (cl < 0) cl = A.cls[0];
+		if (D < 0) D = 0;   // a row of zeros: the zero polynomial, one point
+	} else {
+		cl = R.cl; D = R.D; flag = R.flag;
+	}
+	if (!flag) {
+		res[0] = -INFINITY; res[1] = INFINITY; res[2] = -INFINITY; res[3] = INFINITY;
+		tw[0] = tw[1] = NAN; status = NTG_EXTREMA_NONE; npieces = 0;
+		return;
+	}
+	const EnvClass C = T.c[cl];
+	const double *kn = M.kns + A.koff[cl], *hh = M.tab + C.hoff;
+	const double tol = A.tol;
+	const bool s_lo = A.sides & 1, s_hi = A.sides & 2;
+	const unsigned long long below = (1ull << lane) - 1ull;
+	double U = INFINITY, tU = INFINITY, V = -INFINITY, tV = INFINITY;   // the same in every lane after a level's butterfly
+	double Rlo = INFINITY, Rhi = -INFINITY;   // retired pieces, this lane's
+	double Olo = INFINITY, Ohi = -INFINITY;   // open pieces of the current level, this lane's: they retire when the loop stops on them
+	bool nan = false;
+	int nopen = 0;
+
+	// level 0: lane + 64 t takes interval j.  Two rounds over the intervals: the ends first, then the decisions, which need U and V of the whole
+	// level.  One polygon per lane (l <= 64) stays in registers between the rounds; otherwise the second round forms it again, the same way.
+	const int npass = (C.l + 63) >> 6;
+	EnvPoly<KD> P;
+#pragma unroll
+	for (int s = 0; s < KD; s++) P.b[s] = 0.0;
+	for (int it = 0; it < 2 * npass; it++) {
+		const bool second = it >= npass;
+		const int j = lane + 64 * (second ? it - npass : it);
+		const bool on = j < C.l;
+		if (on && (!second || npass > 1)) {
+			if (lin) ext_poly_lin<KM>(A, lr, cl, D, C, M.tab, M.xrow, j, P);
+			else ext_poly_sos<KM>(T, row - A.nltc, R, C, M.wl, M.tab, M.xrow, M.prow, j, P);
+		}
+		if (!second) {
+			if (on) {
+				const double e0 = P.b[0], e1 = ext_last<KD>(P, D);
+				ext_take_min(U, tU, e0, kn[j]); ext_take_min(U, tU, e1, kn[j + 1]);
+				ext_take_max(V, tV, e0, kn[j]); ext_take_max(V, tV, e1, kn[j + 1]);
+			}
+			if (it == npass - 1) ext_wave_ends(U, tU, V, tV);
+		} else {
+			double plo = 0.0, phi = 0.0;
+			bool open = false;
+			if (on) {
+				P.range(D, plo, phi);
+				nan = nan || plo != plo || phi != phi;
+				open = (s_lo && plo < U - tol) || (s_hi && phi > V + tol);
+			}
+			const unsigned long long m = __ballot(open);
+			const int pos = nopen + __popcll(m & below);
+			if (open) {
+				if (plo < Olo) Olo = plo;
+				if (phi > Ohi) Ohi = phi;
+				if (pos < NTG_EXTREMA_CAP) {
+#pragma unroll
+					for (int s = 0; s < KD; s++) { if (s <= D) M.list[pos * KD + s] = P.b[s]; }
+					M.keys[pos] = (long long)j << 32;
+				}
+			} else if (on) {
+				if (plo < Rlo) Rlo = plo;
+				if (phi > Rhi) Rhi = phi;
+			}
+			nopen += __popcll(m);
+		}
+	}
+	npieces = C.l;
+
+	// levels: the open pieces of level lam are in the list; their children form level lam + 1
+	status = NTG_EXTREMA_OK;
+	for (int lam = 0; lam <= A.max_depth; lam++) {
+		if (nopen == 0) break;
+		if (lam == A.max_depth || nopen > NTG_EXTREMA_CAP) {
+			status = lam == A.max_depth ? NTG_EXTREMA_DEPTH : NTG_EXTREMA_FULL;
+			if (Olo < Rlo) Rlo = Olo;
+			if (Ohi > Rhi) Rhi = Ohi;
+			break;
+		}
+		Olo = INFINITY; Ohi = -INFINITY;
+		const bool on = lane < nopen;
+		int Dl = D;
+		asm volatile("" : "+s"(Dl));   // the degree's masks are formed where they are used, level by level: hoisted out of the loop they fill the scalar registers
+		const double inv = 1.0 / (double)(1 << (lam + 1));
+		EnvPoly<KD> Lp, Rp;
+		long long key = 0;
+		__builtin_amdgcn_wave_barrier();   // the list of level lam is whole
+		if (on) {
+#pragma unroll
+			for (int s = 0; s < KD; s++) Rp.b[s] = s <= Dl ? M.list[lane * KD + s] : 0.0;
+			key = M.keys[lane];
+		} else {
+#pragma unroll
+			for (int s = 0; s < KD; s++) Rp.b[s] = 0.0;
+		}
+		__builtin_amdgcn_wave_barrier();   // every parent is in registers before a child is stored
+		const int j = (int)(key >> 32), i = (int)(key & 0xffffffffll);
+		// split in the middle: Rp becomes the right child, Lp the left one
+#pragma unroll
+		for (int s = 0; s < KD; s++) Lp.b[s] = 0.0;
+		Lp.b[0] = Rp.b[0];
+#pragma unroll
+		for (int r = 1; r < KD; r++) {
+			if (r <= Dl) {
+#pragma unroll
+				for (int s = 0; s < KD - r; s++) { if (s <= Dl - r) Rp.b[s] = 0.5 * (Rp.b[s] + Rp.b[s + 1]); }
+				Lp.b[r] = Rp.b[0];
+			}
+		}
+		double llo = 0.0, lhi = 0.0, rlo = 0.0, rhi = 0.0;
+		if (on) {
+			const double e0 = Lp.b[0], em = Rp.b[0], e1 = ext_last<KD>(Rp, Dl);
+			const double t0 = ext_time(kn, hh, j, 2 * i, lam + 1, inv), tm = ext_time(kn, hh, j, 2 * i + 1, lam + 1, inv), t1 = ext_time(kn, hh, j, 2 * i + 2, lam + 1, inv);
+			ext_take_min(U, tU, e0, t0); ext_take_min(U, tU, em, tm); ext_take_min(U, tU, e1, t1);
+			ext_take_max(V, tV, e0, t0); ext_take_max(V, tV, em, tm); ext_take_max(V, tV, e1, t1);
+			Lp.range(Dl, llo, lhi); Rp.range(Dl, rlo, rhi);
+			nan = nan || llo != llo || lhi != lhi || rlo != rlo || rhi != rhi;
+		}
+		ext_wave_ends(U, tU, V, tV);
+		const bool openL = on && ((s_lo && llo < U - tol) || (s_hi && lhi > V + tol));
+		const bool openR = on && ((s_lo && rlo < U - tol) || (s_hi && rhi > V + tol));
+		const unsigned long long mL = __ballot(openL), mR = __ballot(openR);
+		const int posL = __popcll(mL & below) + __popcll(mR & below), posR = posL + (openL ? 1 : 0);
+		if (openL) {
+			if (llo < Olo) Olo = llo;
+			if (lhi > Ohi) Ohi = lhi;
+			if (posL < NTG_EXTREMA_CAP) {
+#pragma unroll
+				for (int s = 0; s < KD; s++) { if (s <= Dl) M.list[posL * KD + s] = Lp.b[s]; }
+				M.keys[posL] = ((long long)j << 32) | (long long)(2 * i);
+			}
+		} else if (on) {
+			if (llo < Rlo) Rlo = llo;
+			if (lhi > Rhi) Rhi = lhi;
+		}
+		if (openR) {
+			if (rlo < Olo) Olo = rlo;
+			if (rhi > Ohi) Ohi = rhi;
+			if (posR < NTG_EXTREMA_CAP) {
+#pragma unroll
+				for (int s = 0; s < KD; s++) { if (s <= Dl) M.list[posR * KD + s] = Rp.b[s]; }
+				M.keys[posR] = ((long long)j << 32) | (long long)(2 * i + 1);
+			}
+		} else if (on) {
+			if (rlo < Rlo) Rlo = rlo;
+			if (rhi > Rhi) Rhi = rhi;
+		}
+		npieces += 2 * nopen;
+		nopen = __popcll(mL) + __popcll(mR);
+	}
+	__builtin_amdgcn_wave_barrier();   // the next row's list starts behind this row's loads
+	ext_wave_range(Rlo, Rhi);
+	if (__ballot(nan) != 0ull) {
+		res[0] = res[1] = res[2] = res[3] = NAN; tw[0] = tw[1] = NAN; status = NTG_EXTREMA_NAN;
+	} else {
+		res[0] = Rlo; res[1] = U; res[2] = V; res[3] = Rhi; tw[0] = tU; tw[1] = tV;
+	}
+}
+
+// every row of problem b, by one wave whose x row and parameter row are in M
+template <int KM>
+__device__ __forceinline__ void ext_problem(const ExtArgs &A, const SosTables &T, const ExtLds &M, int b, int lane)
+{
+	const int nrow = A.nltc + A.s.nrow;
+	const bool want_v = A.viol || A.where;
+	double av = 0.0, cv = 0.0; long long ak = -1, ck = -1;
+	for (int row = 0; row < nrow; row++) {
+		double res[4], tw[2];
+		int status, npieces;
+		ext_row<KM>(A, T, M, row, lane, res, tw, status, npieces);
+		const size_t at = (size_t)b * nrow + row;
+		if (lane == 0) {
+			if (A.ext) { A.ext[4 * at] = res[0]; A.ext[4 * at + 1] = res[1]; A.ext[4 * at + 2] = res[2]; A.ext[4 * at + 3] = res[3]; }
+			if (A.when) { A.when[2 * at] = tw[0]; A.when[2 * at + 1] = tw[1]; }
+			if (A.status) A.status[at] = status;
+			if (A.npieces) A.npieces[at] = npieces;
+		}
+		if (want_v) {   // (every row has flag 1: the host has refused the others)
+			const int slot = row < A.nltc ? A.slot_lin + row : A.s.slot0 + row - A.nltc;
+			const double l = A.s.lower[(size_t)b * A.s.nbounds + slot], u = A.s.upper[(size_t)b * A.s.nbounds + slot];
+			double a = 0.0, c = 0.0;
+			if (fabs(l) < NTG_INF_BOUND) { a = env_max(a, l - res[1]); c = env_max(c, l - res[0]); }
+			if (fabs(u) < NTG_INF_BOUND) { a = env_max(a, res[2] - u); c = env_max(c, res[3] - u); }
+			env_take(av, ak, a, (a > 0.0 || a != a) ? (long long)row : -1ll);
+			env_take(cv, ck, c, (c > 0.0 || c != c) ? (long long)row : -1ll);
+		}
+	}
+	if (want_v && lane == 0) {
+		if (A.viol) { A.viol[2 * (size_t)b] = ak < 0 ? 0.0 : av; A.viol[2 * (size_t)b + 1] = ck < 0 ? 0.0 : cv; }
+		if (A.where) { A.where[2 * (size_t)b] = (int)ak; A.where[2 * (size_t)b + 1] = (int)ck; }
+	}
+}
+
+template <int NT, int KM>
+__global__ void __launch_bounds__(NT)
+extrema_shared_kernel(ExtArgs A)
+{
+	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+	constexpr int NW = NT / 64, KD = 2 * KM - 1;
+	__shared__ SosTables T;
+	const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+	double *wl = reinterpret_cast<double *>(smem_raw);    // the product tables, unfolded
+	double *tab = wl + NTG_SOS_WFULL;                     // weights and interval lengths of every basis class
+	double *kns = tab + A.s.ne;                           // breaks of every basis class
+	double *mine = kns + A.nk + (size_t)wave * (A.s.nC + A.s.np + NTG_EXTREMA_CAP * (KD + 1));
+	double *xrow = mine, *prow = xrow + A.s.nC, *list = prow + A.s.np;
+	const ExtLds M{wl, tab, kns, xrow, prow, list, reinterpret_cast<long long *>(list + NTG_EXTREMA_CAP * KD)};
+	sos_stage(A.s, T, tid);
+	sos_unfold(A.s, wl, tid, NT);
+	for (int c = 0; c < A.s.nclass; c++)
+		for (int i = tid; i <= A.s.c[c].l; i += NT) kns[A.koff[c] + i] = A.s.knots[c][i];
+	__syncthreads();
+	for (int c = 0; c < A.s.nclass; c++) env_build(kns + A.koff[c], A.s.c[c], tab + A.s.c[c].eoff, tab + A.s.c[c].hoff, tid, NT);
+	__syncthreads();
+	for (int b0 = blockIdx.x * NW; b0 < A.s.batch; b0 += gridDim.x * NW) {
+		const int b = b0 + wave;
+		if (b >= A.s.batch) continue;
+		__builtin_amdgcn_wave_barrier();   // the problem before is done with the rows
+		const double *src = A.s.x + (size_t)b * A.s.nC;
+		for (int i = lane; i < A.s.nC; i += 64) xrow[i] = src[i];
+		for (int i = lane; i < A.s.np; i += 64) prow[i] = A.s.prm[(size_t)b * A.s.pp_prm + i];
+		__builtin_amdgcn_wave_barrier();
+		ext_problem<KM>(A, T, M, b, lane);
+	}
+}
+
+// per-problem grids: one basis class; every wave builds the weights of its own problem
+template <int NT, int KM>
+__global__ void __launch_bounds__(NT)
+extrema_pp_kernel(ExtArgs A)
+{
+	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+	constexpr int NW = NT / 64, KD = 2 * KM - 1;
+	__shared__ SosTables T;
+	const EnvClass C = A.s.c[0];
+	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	double *wl = reinterpret_cast<double *>(smem_raw);
+	double *tab = wl + NTG_SOS_WFULL + (size_t)wave * (A.s.ne + A.nk + A.s.nC + A.s.np + NTG_EXTREMA_CAP * (KD + 1));
+	double *kns = tab + A.s.ne, *xrow = kns + A.nk, *prow = xrow + A.s.nC, *list = prow + A.s.np;
+	const ExtLds M{wl, tab, kns, xrow, prow, list, reinterpret_cast<long long *>(list + NTG_EXTREMA_CAP * KD)};
+	sos_stage(A.s, T, threadIdx.x);
+	sos_unfold(A.s, wl, threadIdx.x, NT);
+	const int per_pass = gridDim.x * NW;
+	for (int b0 = 0; b0 < A.s.batch; b0 += per_pass) {   // (the same trip count for every wave of the grid: the barriers below are uniform)
+		const int b = b0 + blockIdx.x * NW + wave;
+		const bool on = b < A.s.batch;
+		__syncthreads();
+		if (on) {
+			const double *kt = A.s.knots[0] + (size_t)b * (C.l + 1), *src = A.s.x + (size_t)b * A.s.nC;
+			for (int i = lane; i <= C.l; i += 64) kns[i] = kt[i];
+			for (int i = lane; i < A.s.nC; i += 64) xrow[i] = src[i];
+			for (int i = lane; i < A.s.np; i += 64) prow[i] = A.s.prm[(size_t)b * A.s.pp_prm + i];
+		}
+		__syncthreads();
+		if (on) env_build(kns, C, tab + C.eoff, tab + C.hoff, lane, 64);
+		__syncthreads();
+		if (on) ext_problem<KM>(A, T, M, b, lane);
+	}
+}

@@ -21,6 +21,8 @@
 //                   knot intervals, from the Bezier control polygons (envelope.hpp)
 //   envelope_sos_*  the same for the nonlinear trajectory rows declared as sums of squares, by the
 //                   Bezier product of those polygons (envelope_sos.hpp)
+//   extrema_*       minimum and maximum of those rows over the horizon, enclosed to a tolerance, by
+//                   bisection of the same polygons from a work list in LDS (extrema.hpp)
 //
 // Mapping to CDNA4: one workgroup per problem; breakpoints (then coefficients) across the
 // lanes; basis tables, knots/breakpoints and the coefficient vector staged in LDS; the only
@@ -34,6 +36,7 @@
 #include "refine.hpp"
 #include "envelope.hpp"
 #include "envelope_sos.hpp"
+#include "extrema.hpp"
 #include "kkt.hpp"
 #include "verify.hpp"
 
@@ -664,6 +667,31 @@ hipError_t ntg_launch_envelope_sos(const SosArgs &A, int ncu, hipStream_t st)
 	if (lds > NTG_ENVELOPE_LDS_MAX || A.kmax > NTG_MAX_ORDER || A.nrow > NTG_SOS_MAXROWS) return hipErrorInvalidValue;   // (ntg_batch_envelope_sos refuses such a plan before it gets here)
 	if (A.batch <= 0) return hipSuccess;
 	return A.kmax <= 6 ? launch_envelope_sos<6>(A, ncu, lds, st) : launch_envelope_sos<NTG_MAX_ORDER>(A, ncu, lds, st);
+}
+
+// ntg_batch_extrema (extrema.hpp): the instances of ntg_launch_envelope_sos; four problems per workgroup pass, one per wave.
+// hipErrorInvalidValue: the tables and work lists exceed the LDS.
+template <int KM>
+static hipError_t launch_extrema(const ExtArgs &A, int ncu, size_t lds, hipStream_t st)
+{
+	constexpr int NW = NTG_EXTREMA_NT / 64;
+	const int groups = (A.s.batch + NW - 1) / NW;
+	auto kfn = A.s.pp ? extrema_pp_kernel<NTG_EXTREMA_NT, KM> : extrema_shared_kernel<NTG_EXTREMA_NT, KM>;
+	if (lds > 64 * 1024) {
+		const hipError_t e = hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+		if (e != hipSuccess) return e;
+	}
+	// shared grids: persistent workgroups, each builds its weights once, so each should stream several problems; no more than fill the device
+	const int grid = A.s.pp ? std::min(groups, 8 * ncu) : std::max(1, std::min((groups + 3) / 4, 8 * ncu));
+	hipLaunchKernelGGL(kfn, dim3(grid), dim3(NTG_EXTREMA_NT), lds, st, A);
+	return hipGetLastError();
+}
+hipError_t ntg_launch_extrema(const ExtArgs &A, int ncu, hipStream_t st)
+{
+	const size_t lds = ntg_extrema_lds(A);
+	if (lds > NTG_EXTREMA_LDS_MAX || A.s.kmax > NTG_MAX_ORDER || A.s.nrow > NTG_SOS_MAXROWS) return hipErrorInvalidValue;   // (ntg_batch_extrema refuses such a plan before it gets here)
+	if (A.s.batch <= 0) return hipSuccess;
+	return A.s.kmax <= 6 ? launch_extrema<6>(A, ncu, lds, st) : launch_extrema<NTG_MAX_ORDER>(A, ncu, lds, st);
 }
 
 // Flat flag -> state and input of the kinematic car, the map of examples/kincar.c:68-92 (kincar_flat_reverse), for every car

@@ -267,3 +267,32 @@ static inline size_t ntg_envelope_sos_lds(const SosArgs &A)
 {
 	return ((size_t)NTG_SOS_WFULL + (size_t)(A.pp ? NTG_ENVELOPE_NT / 64 : 1) * (size_t)(A.ne + A.nC + A.np + A.lmax + 1)) * 8;
 }
+
+// row extrema by bisection (extrema.hpp): the global minimum and maximum of every certifiable trajectory row over the horizon, each enclosed
+// to tol, with the time where the attained value sits.  Rows: the nltc linear trajectory rows (ltc [nltc][nz], read as envelope.hpp reads
+// them through cls / d / iC / iz), then the s.nrow nonlinear ones (s.row / s.term / s.w, as envelope_sos.hpp reads them).  s carries what the
+// two envelope calls share: c, knots, ne, lmax, kmax, nC, nclass, batch, pp, np, prm, pp_prm, x, lower, upper, nbounds; s.slot0 is the first
+// nonlinear row's bound slot, slot_lin the first linear row's; s.nsub, s.npc and s's outputs are not used.  koff[cl]: the breaks of class cl
+// in the LDS table of nk doubles (the times of the piece ends need them after the weights are built).
+// Outputs as documented at ntg_batch_extrema, any may be null.
+#define NTG_EXTREMA_NT 256
+struct ExtArgs {
+	SosArgs s;
+	int nout, nz, nltc, slot_lin, max_depth, sides, nk, pad;
+	double tol;
+	int cls[NTG_MAX_OUT], d[NTG_MAX_OUT], iC[NTG_MAX_OUT], iz[NTG_MAX_OUT], koff[NTG_MAX_OUT];
+	const double *ltc;
+	double *ext, *when, *viol; int *status, *npieces, *where;
+};
+static_assert(sizeof(ExtArgs) <= 4096, "ExtArgs travels as a kernel argument");
+// doubles of a work-list element: the row polygon's points; the instance (KM = 6 or NTG_MAX_ORDER) follows from the plan's largest order
+static inline int ntg_extrema_kd(const ExtArgs &A) { return A.s.kmax <= 6 ? 11 : 2 * NTG_MAX_ORDER - 1; }
+// dynamic LDS: the unfolded product tables; the extraction tables and the breaks of every class; per wave one coefficient row, one parameter
+// row, the work list (NTG_EXTREMA_CAP polygons) and its keys.  Per-problem grids: every wave has extraction tables and breaks of its own.
+static inline size_t ntg_extrema_lds(const ExtArgs &A)
+{
+	const size_t wave = (size_t)A.s.nC + A.s.np + (size_t)NTG_EXTREMA_CAP * (ntg_extrema_kd(A) + 1), tabs = (size_t)A.s.ne + A.nk;
+	return ((size_t)NTG_SOS_WFULL + (A.s.pp ? 0 : tabs) + (size_t)(NTG_EXTREMA_NT / 64) * (wave + (A.s.pp ? tabs : 0))) * 8;
+}
+// ... and what a workgroup may ask for: 160 KiB less the static part (the row, term and class tables)
+#define NTG_EXTREMA_LDS_MAX (160 * 1024 - 2048)

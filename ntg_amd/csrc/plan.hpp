@@ -69,6 +69,8 @@ hipError_t ntg_launch_refine(const RefineArgs &A, int pp, int ncu, hipStream_t s
 hipError_t ntg_launch_envelope(const EnvArgs &A, int ncu, hipStream_t st);
 // bounds of the nonlinear trajectory rows declared as sums of squares over the same pieces (envelope_sos.hpp)
 hipError_t ntg_launch_envelope_sos(const SosArgs &A, int ncu, hipStream_t st);
+// minimum and maximum of the certifiable trajectory rows over the horizon, by bisection (extrema.hpp)
+hipError_t ntg_launch_extrema(const ExtArgs &A, int ncu, hipStream_t st);
 // trajectory rows at arbitrary times (check.hpp): the family's check_kernel instance, then the maximum over a problem's time tiles
 hipError_t ntg_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a);
 hipError_t ntg_launch_check_final(int batch, int ntiles, int ntimes, const double *pviol, const long long *pkey, double *viol, int *where, hipStream_t st);

@@ -5,11 +5,7 @@
 #include "plan_priv.hpp"
 #include "family_module.hpp"
 
-namespace {
-// row j of the plan: its terms in the kernels' form.  flag 0: no statement -- the family does not declare the row (or names a flag entry the
-// plan does not have), or the entries it names belong to different basis classes; cl is then the class of the first entry named, or of output 0
-struct SosPlanRow { SosRow row; SosTerm term[NTG_SOS_MAXTERMS]; bool need_prm; };
-
+// row j of the plan: its terms in the kernels' form (SosPlanRow, plan_priv.hpp)
 SosPlanRow sos_plan_row(const ntg_plan *p, const NtgFamily *f, int j)
 {
 	const NtgDims &D = p->D;
@@ -36,13 +32,21 @@ SosPlanRow sos_plan_row(const ntg_plan *p, const NtgFamily *f, int j)
 }
 
 // C(n, r), exact: n <= 2 (NTG_MAX_ORDER - 1)
-unsigned long long binom(int n, int r)
+static unsigned long long binom(int n, int r)
 {
 	unsigned long long c = 1;
 	for (int i = 1; i <= r; i++) c = c * (unsigned long long)(n - r + i) / (unsigned long long)i;
 	return c;
 }
-}   // namespace
+
+void sos_product_tables(double *w)
+{
+	for (int d = 0; d < NTG_MAX_ORDER; d++) {   // W_d[i][j] = C(d,i) C(d,j) / C(2d,i+j), i <= j: two exact integers, one rounding
+		double *q = w + ntg_sos_wtri(d);
+		for (int i = 0; i <= d; i++)
+			for (int j = i; j <= d; j++) *q++ = (double)(binom(d, i) * binom(d, j)) / (double)binom(2 * d, i + j);
+	}
+}
 
 extern "C" int ntg_plan_sos_rows(const ntg_plan *p, int *flags)
 {
@@ -103,11 +107,7 @@ extern "C" int ntg_batch_envelope_sos(const ntg_plan *p, int batch, const double
 	A.np = need_prm ? p->prm_n : 0;
 	A.prm = need_prm ? p->T.prm : nullptr; A.pp_prm = need_prm ? p->T.pp_prm : 0;
 	if (ntg_envelope_sos_lds(A) > NTG_ENVELOPE_LDS_MAX) return fail(NTG_E_UNSUPPORTED, "the extraction and product tables of this plan exceed 64 KiB of LDS");
-	for (int d = 0; d < NTG_MAX_ORDER; d++) {   // W_d[i][j] = C(d,i) C(d,j) / C(2d,i+j), i <= j: two exact integers, one rounding
-		double *w = A.w + ntg_sos_wtri(d);
-		for (int i = 0; i <= d; i++)
-			for (int j = i; j <= d; j++) *w++ = (double)(binom(d, i) * binom(d, j)) / (double)binom(2 * d, i + j);
-	}
+	sos_product_tables(A.w);
 	A.x = d_x; A.lower = d_lower; A.upper = d_upper;
 	A.q_lo = d_q_lo; A.q_hi = d_q_hi; A.viol = d_viol; A.where = d_where;
 	HIPCHK(hipSetDevice(p->device));
