@@ -743,7 +743,7 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 #pragma unroll
 		for (int e = 0; e < EPL; e++) { d[e] = 0.0; gp[e] = 0.0; gpt[e] = 0.0; g[e] = 0.0; }
 		enum { ST_INIT = 0, ST_LS = 1, ST_FORCE = 2, ST_FINAL = 3 };
-		int inform = 4, iter = 0, nfev = 0, nupd = 0, ns = 0, state = ST_INIT;
+		int inform = 4, iter = 0, nfev = 0, nupd = 0, ns = 0, state = ST_INIT, rcn = 1;   // (rcn: what the line search said of the last trial, carried out of the trials' loop)
 		bool headpair = false;   // the quasi-Newton memory was restarted at an accepted step: its first pair is not in the span of the chain
 		// phase clock: variant builds only (-DNTGW_STAMPS, tools/mkvariant.sh + tests/tools_wave_stamps.py).  Compiled in, its eight 64-bit
 		// accumulators and the time base were 18 scalar registers live across the whole kernel -- the shipped FAT instance carried ~930
@@ -809,29 +809,80 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 			double ls_a = 0.0;
 			double tstep = 0.0;            // the point to evaluate is x + tstep (-d): a line-search trial, or x itself (first and final evaluation)
 			double r4[4] = {0, 0, 0, 0};   // gp.d, d.d, x.x, gp.gp of the current iterate
-			for (;;) {
-				// ================= the one evaluation site =================
-				double part[3] = {0.0, 0.0, 0.0};
-				{
-					// the trial point is formed here and dies inside the evaluation (it is not kept across the line-search step: an accepted
-					// step recomputes x + alpha (-d), the same operation on the same operands)
-					double xt[EPL];
-#pragma unroll
-					for (int e = 0; e < EPL; e++) xt[e] = x[e] + tstep * (-d[e]);
-					evaluate(xt, g, part[0], part[1]);
-				}
-				NTGW_STAMPV(1, g[0] + part[0] + part[1]);
-				if (state != ST_FINAL) {
-					project(g, gpt);
-#pragma unroll
-					for (int e = 0; e < EPL; e++) part[2] += gpt[e] * (-d[e]);
-					NTGW_STAMPV(2, part[2]);
-				}
-#ifdef NTGW_DBL_RED3
-				{ double q_[3] = {part[0], part[1], part[2]}; asm volatile("" : "+v"(q_[0]), "+v"(q_[1]), "+v"(q_[2])); wave_sums<3, MINW == 1>(q_, lane); asm volatile("" ::"s"(q_[0]), "s"(q_[1]), "s"(q_[2])); }
+			// One step of the line search on the values of the trial just evaluated, into rc_: 1 accept, 0 / 2 another trial at ls_a (2: the last
+			// one, taken whatever it gives), anything else failed.  A macro, so that its two places of use (one per form of the loop below, never
+			// both in one instance) compile as the text written there: as a lambda the step is optimised on its own before it is inlined, and
+			// the two-waves-per-SIMD instances, whose loop is otherwise the text it was, came out with 2 to 67 more spilled scalars.
+#ifdef NTGW_DBL_LS
+#define NTGW_LS_DBL(Fn_, slope_) \
+			{ LineSearch l2_ = ls; double fq_ = (Fn_), sq_ = (slope_); asm volatile("" : "+v"(fq_), "+v"(sq_)); fq_ = LineSearch::uni_(fq_); sq_ = LineSearch::uni_(sq_); \
+			  int rq_ = __builtin_amdgcn_readfirstlane(l2_.step(fq_, sq_)); l2_.make_uniform(); asm volatile("" ::"s"(rq_), "s"(l2_.a), "s"(l2_.a_lo), "s"(l2_.a_hi), "s"(l2_.phi_lo), "s"(l2_.phi_hi), "s"(l2_.a_prev)); }
+#else
+#define NTGW_LS_DBL(Fn_, slope_)
 #endif
-				wave_sums<3, MINW == 1>(part, lane);
-				NTGW_STAMPV(6, part[0] + part[1] + part[2]);
+#define NTGW_LS_STEP(rc_, Fn_, slope_) { \
+				NTGW_LS_DBL(Fn_, slope_) \
+				if constexpr (LSREG) { \
+					{   /* the line search's constants from the argument segment (LineSearch::init stored the same values) */ \
+						const WaveKernArgsPtr ka = kernargs(); \
+						ls.mu = ka->sp.ls_mu; ls.eta = ka->sp.ls_eta; ls.maxfev = ka->sp.ls_maxfev; \
+					} \
+					rc_ = __builtin_amdgcn_readfirstlane(ls.step((Fn_), (slope_))); \
+					ls.make_uniform(); \
+					ls_a = ls.a; \
+				} else { \
+					LineSearch lsr = *lsm; \
+					rc_ = lsr.step((Fn_), (slope_)); \
+					ls_a = lsr.a; \
+					nwt_wave_sync();   /* every lane has read the state before lane 0 rewrites it */ \
+					if (lane == 0) *lsm = lsr; \
+					nwt_wave_sync(); \
+				} \
+				NTGW_STAMPV(7, ls_a); \
+			}
+			// The line search's trials repeat in a loop of their own around the evaluation site (NEST: the one-wave-per-SIMD instances).  x, gp
+			// and d do not change from trial to trial; as a `continue` of the major loop the trial's back edge shared its header with the
+			// accepted step's, where they do, and every trip copied the whole iterate between two sets of registers.  The two-waves-per-SIMD
+			// instances keep the single loop: nested, they spill more scalars.  (An enumerator, not a constexpr local: a local is an object of the
+			// function, and one more of those, dead or not, renames registers all through the instances that are meant to stay as they were.)
+			enum { NEST = (MINW == 1) };
+			for (;;) {
+				double part[3];
+				for (;;) {
+					// ================= the one evaluation site =================
+					part[0] = 0.0; part[1] = 0.0; part[2] = 0.0;
+					{
+						// the trial point is formed here and dies inside the evaluation (it is not kept across the line-search step: an accepted
+						// step recomputes x + alpha (-d), the same operation on the same operands)
+						double xt[EPL];
+#pragma unroll
+						for (int e = 0; e < EPL; e++) xt[e] = x[e] + tstep * (-d[e]);
+						evaluate(xt, g, part[0], part[1]);
+					}
+					NTGW_STAMPV(1, g[0] + part[0] + part[1]);
+					if (state != ST_FINAL) {
+						project(g, gpt);
+#pragma unroll
+						for (int e = 0; e < EPL; e++) part[2] += gpt[e] * (-d[e]);
+						NTGW_STAMPV(2, part[2]);
+					}
+#ifdef NTGW_DBL_RED3
+					{ double q_[3] = {part[0], part[1], part[2]}; asm volatile("" : "+v"(q_[0]), "+v"(q_[1]), "+v"(q_[2])); wave_sums<3, MINW == 1>(q_, lane); asm volatile("" ::"s"(q_[0]), "s"(q_[1]), "s"(q_[2])); }
+#endif
+					wave_sums<3, MINW == 1>(part, lane);
+					NTGW_STAMPV(6, part[0] + part[1] + part[2]);
+					if constexpr (!NEST) break;
+					else {
+						rcn = 1;
+						if (state != ST_LS) break;   // the first, a forced and the final evaluation pass through once
+						NTGW_LS_STEP(rcn, part[0], part[2]);
+						if (!(rcn == 0 || rcn == 2)) break;
+						nfev++;
+						if (rcn == 2) state = ST_FORCE;
+						tstep = ls_a;
+						NTGW_STAMP(5);
+					}
+				}
 				const double Fn = part[0], gn2n = part[1];
 #ifdef NTGW_DEBUG
 				if (lane == 0 && nfev < 40) printf("b %d state %d iter %d nfev %d ns %d F %.10g g2 %.6g slope %.6g a %.6g\n", b, state, iter, nfev, ns, Fn, gn2n, part[2], ls_a);
@@ -871,35 +922,15 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 					NTGW_STAMP(4);
 					new_major = true;
 				} else {
-					int rc = 1;
-					if (state == ST_LS) {
-#ifdef NTGW_DBL_LS
-						{ LineSearch l2_ = ls; double fq_ = Fn, sq_ = part[2]; asm volatile("" : "+v"(fq_), "+v"(sq_)); fq_ = LineSearch::uni_(fq_); sq_ = LineSearch::uni_(sq_);
-						  int rq_ = __builtin_amdgcn_readfirstlane(l2_.step(fq_, sq_)); l2_.make_uniform(); asm volatile("" ::"s"(rq_), "s"(l2_.a), "s"(l2_.a_lo), "s"(l2_.a_hi), "s"(l2_.phi_lo), "s"(l2_.phi_hi), "s"(l2_.a_prev)); }
-#endif
-						if constexpr (LSREG) {
-							{   // the line search's constants from the argument segment (LineSearch::init stored the same values)
-								const WaveKernArgsPtr ka = kernargs();
-								ls.mu = ka->sp.ls_mu; ls.eta = ka->sp.ls_eta; ls.maxfev = ka->sp.ls_maxfev;
-							}
-							rc = __builtin_amdgcn_readfirstlane(ls.step(Fn, part[2]));
-							ls.make_uniform();
-							ls_a = ls.a;
-						} else {
-							LineSearch lsr = *lsm;
-							rc = lsr.step(Fn, part[2]);
-							ls_a = lsr.a;
-							nwt_wave_sync();   // every lane has read the state before lane 0 rewrites it
-							if (lane == 0) *lsm = lsr;
-							nwt_wave_sync();
+					int rc = NEST ? rcn : 1;
+					if constexpr (!NEST) {
+						if (state == ST_LS) NTGW_LS_STEP(rc, Fn, part[2]);
+						if (rc == 0 || rc == 2) {
+							if (rc == 2) state = ST_FORCE;
+							tstep = ls_a;
+							NTGW_STAMP(5);
+							continue;
 						}
-						NTGW_STAMPV(7, ls_a);
-					}
-					if (rc == 0 || rc == 2) {
-						if (rc == 2) state = ST_FORCE;
-						tstep = ls_a;
-						NTGW_STAMP(5);
-						continue;
 					}
 					if (rc != 1) {
 						const double tolg = kernargs()->sp.sr * (1.0 + fmax(1.0 + fabs(F), sqrt(gn2)));
@@ -1082,6 +1113,8 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 #endif
 			nwt_wave_sync();
 		}
+#undef NTGW_LS_STEP
+#undef NTGW_LS_DBL
 #undef NTGW_STAMP
 #undef NTGW_STAMPV
 		if (lane == 0) {
