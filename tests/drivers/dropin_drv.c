@@ -12,7 +12,9 @@
  * as NPSOL's do.  "kincarR": kincar, then the returned factor R (row-major, n x n).
  * A second argument "files" also writes the solution with PrintVector ("coef1") and the initial-constraint matrix with PrintMatrix
  * ("lic"), and frees the DoubleMatrix storage, as the examples do: the remaining helpers of include/ntg.h are called here too.
- * Usage: dropin_drv vanderpol|kincar|obstacle|ineq|sequence|kincarR [files]   -> prints "RESULT inform objective c0 c1 ..."
+ * Every further argument is handed to npsoloption() verbatim, after the options above and before the call of ntg()
+ * (e.g. "step limit 0.05", "major iteration limit = 6").
+ * Usage: dropin_drv vanderpol|kincar|obstacle|ineq|sequence|kincarR [files] [option string]...   -> prints "RESULT inform objective c0 c1 ..."
  */
 #include <math.h>
 #include "ntg.h"
@@ -37,7 +39,8 @@ static void obs_con(int *mode, int *nstate, int *i, double *c, double **dc, doub
 	if (*mode == 0 || *mode == 2) c[0] = dx * dx + dy * dy;
 	if (*mode == 1 || *mode == 2) { for (v = 0; v < 6; v++) dc[0][v] = 0; dc[0][0] = 2 * dx; dc[0][3] = 2 * dy; }
 }
-static int g_obstacle = 0, g_printR = 0, g_files = 0;
+static int g_obstacle = 0, g_printR = 0, g_files = 0, g_nopt = 0;
+static char **g_opt = NULL;
 
 static int run(int nout, int order_, int mult_, int ninterv_, int nbps, int nlic, double **lic, int nlfc, double **lfc,
                double *lowerb, double *upperb, void (*ucf)(int *, int *, int *, double *, double *, double **),
@@ -56,6 +59,7 @@ static int run(int nout, int order_, int mult_, int ninterv_, int nbps, int nlic
 	npsoloption("nolist");
 	npsoloption("summary file = 0");
 	if (g_obstacle) npsoloption("print level 0");
+	for (i = 0; i < g_nopt; i++) npsoloption(g_opt[i]);
 	ntg(nout, bps, nbps, nint, knots, order, mult, md, coef,
 	    nlic, lic, 0, NULL, nlfc, lfc, 0, NULL, g_obstacle ? 1 : 0, g_obstacle ? obs_con : NULL, 0, NULL,
 	    0, NULL, g_obstacle ? 2 : 0, g_obstacle ? ctav : NULL, 0, NULL,
@@ -87,6 +91,7 @@ static int one(int argc, char **argv);
 int main(int argc, char **argv)
 {
 	if (argc > 2 && !strcmp(argv[2], "files")) g_files = 1;
+	if (argc > 2 + g_files) { g_opt = argv + 2 + g_files; g_nopt = argc - 2 - g_files; }
 	if (argc > 1 && !strcmp(argv[1], "sequence")) {
 		char *a1[2] = {argv[0], "vanderpol"}, *a2[2] = {argv[0], "kincar"};
 		int rc = one(2, a1);

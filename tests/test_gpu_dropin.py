@@ -6,6 +6,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import solve_option_cases as soc
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -163,3 +165,49 @@ def test_linear_inequality_rows_dropin(drv):
     assert obj < 2.457581141950512
     assert istate == list(ref["istate"][spec.nC:spec.nC + 12])
     assert abs(interp[3] - 40.0) <= 1e-7                            # x(T) is still an equality row
+
+
+def run_with_counts(exe, which, *options):
+    """the driver with `options` handed to npsoloption() before it calls ntg(); the result as the oracle's dict, majors and evaluations
+    from the exit line ntg() prints at its default print level"""
+    import re
+    out = subprocess.run([str(exe), which, *options], capture_output=True, text=True, timeout=300)
+    m = re.search(r"Exit NTG/MI355X SQP - inform (-?\d+), majors (\d+), nfev (\d+),", out.stdout)
+    lines = [l for l in out.stdout.splitlines() if l.startswith("RESULT")]
+    assert m and len(lines) == 1, out.stderr + out.stdout
+    res = np.array(lines[0].split()[1:], dtype=float)
+    assert int(m.group(1)) == int(res[0]) == out.returncode, out.stderr + out.stdout      # the driver's exit status is inform
+    return dict(inform=int(res[0]), objective=res[1], x=res[2:], iters=int(m.group(2)), nfev=int(m.group(3)))
+
+
+@pytest.mark.parametrize("case", list(soc.DROPIN))
+def test_option_strings_with_values_reach_the_solver(drv, case):
+    """npsoloption() strings that carry a value ("line search tolerance = 0.1", "step limit 0.05" -- the form without '=' --, "major
+    iteration limit = 6", "optimality tolerance = 1e-3"): the solve under the string equals the oracle's under the same option value, alone
+    and next to the case's companion option, and next to the companion it DIFFERS from the run without the string (inform, or the objective
+    by more than 1e-6 relative): an ignored string does not pass.  tests/solve_option_cases.py says why the companions; tests/
+    test_solve_option_cases.py shows that the paired runs do not hang on rounding, so their majors and evaluations are compared exactly."""
+    import orc
+    problem, string, kw, companion, ckw = soc.DROPIN[case]
+    mk, bounds = soc.DROPIN_PROBLEMS[problem]
+    spec = mk()
+    lo, up = bounds()
+
+    def oracle(opts):
+        return orc.solve_one(spec, lo, up, np.ones(spec.nC), orc.default_opts(**opts))
+
+    def same(got, ref):
+        print(case, "driver inform/majors/nfev/F", got["inform"], got["iters"], got["nfev"], repr(got["objective"]),
+              "| oracle", ref["inform"], ref["iters"], ref["nfev"], repr(ref["objective"]))
+        assert got["inform"] == ref["inform"]
+        assert abs(got["objective"] - ref["objective"]) <= 1e-7 * max(1.0, abs(ref["objective"]))
+        assert np.abs(got["x"] - ref["x"]).max() <= 1e-5 * np.abs(ref["x"]).max()
+
+    alone = run_with_counts(drv, problem, string)
+    same(alone, oracle(kw))
+    base = run_with_counts(drv, problem, *([companion] if companion else []))
+    both = run_with_counts(drv, problem, companion, string) if companion else alone
+    for got, ref in ((base, oracle(ckw)), (both, oracle(dict(ckw, **kw)))):
+        same(got, ref)
+        assert (got["iters"], got["nfev"]) == (ref["iters"], ref["nfev"])
+    assert soc.differs(both, base)
