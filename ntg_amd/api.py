@@ -386,13 +386,8 @@ class Plan:
         _check(lib().ntg_batch_refine(self.h, to.h, batch, _ptr(x), _ptr(out), self._stream()))
         return out
 
-    def envelope(self, x, nsub: int = 0, lower=None, upper=None, want_entries: bool = True, want_rows: bool = False):
-        """Bounds of a batch of trajectories that hold at EVERY time (ntg_batch_envelope): x [batch, nC]; every knot interval is cut into
-        2^nsub pieces, npc = max(kninterv) << nsub (envelope_pieces gives their ends).  Returns a dict: lo, hi [batch, nz, npc] (the flag
-        entries, want_entries), row_lo, row_hi [batch, nltc, npc] (the linear trajectory rows, want_rows), and with bounds [batch, nbounds]
-        viol [batch] and where [batch, 2] = (row, piece) of the largest certified violation or (-1, -1).  Pieces past an output's own are
-        the empty set (lo = +inf, hi = -inf).  viol == 0 certifies every linear trajectory row over the whole horizon."""
-        import torch
+    def _cert_inputs(self, x, lower, upper, nsub=0):
+        """what envelope, envelope_sos and extrema ask of x [batch, nC], the optional bounds [batch, nbounds] and nsub; -> (spec, device, batch)"""
         sp = self.spec
         dev = x.device
         _check_tensor(x, dev); _check_tensor(lower, dev); _check_tensor(upper, dev)
@@ -405,6 +400,16 @@ class Plan:
             raise NtgError(f"bounds must be [{batch}, {sp.nbounds}]")
         if not 0 <= int(nsub) <= ENVELOPE_MAX_NSUB:
             raise NtgError(f"nsub must lie in 0 .. {ENVELOPE_MAX_NSUB} (NTG_ENVELOPE_MAX_NSUB)")
+        return sp, dev, batch
+
+    def envelope(self, x, nsub: int = 0, lower=None, upper=None, want_entries: bool = True, want_rows: bool = False):
+        """Bounds of a batch of trajectories that hold at EVERY time (ntg_batch_envelope): x [batch, nC]; every knot interval is cut into
+        2^nsub pieces, npc = max(kninterv) << nsub (envelope_pieces gives their ends).  Returns a dict: lo, hi [batch, nz, npc] (the flag
+        entries, want_entries), row_lo, row_hi [batch, nltc, npc] (the linear trajectory rows, want_rows), and with bounds [batch, nbounds]
+        viol [batch] and where [batch, 2] = (row, piece) of the largest certified violation or (-1, -1).  Pieces past an output's own are
+        the empty set (lo = +inf, hi = -inf).  viol == 0 certifies every linear trajectory row over the whole horizon."""
+        import torch
+        sp, dev, batch = self._cert_inputs(x, lower, upper, nsub)
         if (want_rows or lower is not None) and sp.nltc == 0:   # (empty row tensors would reach the library as null pointers)
             raise NtgError("the plan has no linear trajectory rows (nltc == 0): there is no row envelope and no violation to ask for")
         npc = max(sp.kninterv) << int(nsub)
@@ -433,18 +438,7 @@ class Plan:
         sos_rows() flags 0 comes back as (-inf, +inf) on its live pieces, and viol / where are then refused.  viol == 0 certifies every
         nonlinear trajectory row over the whole horizon."""
         import torch
-        sp = self.spec
-        dev = x.device
-        _check_tensor(x, dev); _check_tensor(lower, dev); _check_tensor(upper, dev)
-        if x.dim() != 2 or x.shape[1] != sp.nC:
-            raise NtgError(f"x must be [batch, {sp.nC}]")
-        batch = x.shape[0]
-        if (lower is None) != (upper is None):
-            raise NtgError("pass both bounds or neither")
-        if lower is not None and (lower.shape != (batch, sp.nbounds) or upper.shape != (batch, sp.nbounds)):
-            raise NtgError(f"bounds must be [{batch}, {sp.nbounds}]")
-        if not 0 <= int(nsub) <= ENVELOPE_MAX_NSUB:
-            raise NtgError(f"nsub must lie in 0 .. {ENVELOPE_MAX_NSUB} (NTG_ENVELOPE_MAX_NSUB)")
+        sp, dev, batch = self._cert_inputs(x, lower, upper, nsub)
         npc = max(sp.kninterv) << int(nsub)
         # (a plan without such rows gets one row of storage: the library refuses it before it writes, an empty tensor would arrive as a null pointer)
         out = {"q_lo": torch.empty((batch, max(sp.nnltc, 1), npc), dtype=torch.float64, device=dev)}
@@ -471,16 +465,7 @@ class Plan:
         viol[:, 1] == 0 certifies every trajectory row over the whole horizon; a row extrema_rows() flags 0 comes back as
         (-inf, +inf, -inf, +inf), and viol / where are then refused."""
         import torch
-        sp = self.spec
-        dev = x.device
-        _check_tensor(x, dev); _check_tensor(lower, dev); _check_tensor(upper, dev)
-        if x.dim() != 2 or x.shape[1] != sp.nC:
-            raise NtgError(f"x must be [batch, {sp.nC}]")
-        batch = x.shape[0]
-        if (lower is None) != (upper is None):
-            raise NtgError("pass both bounds or neither")
-        if lower is not None and (lower.shape != (batch, sp.nbounds) or upper.shape != (batch, sp.nbounds)):
-            raise NtgError(f"bounds must be [{batch}, {sp.nbounds}]")
+        sp, dev, batch = self._cert_inputs(x, lower, upper)
         nrow = max(sp.nltc + sp.nnltc, 1)   # (a plan without rows gets one row of storage: the library refuses it before it writes)
         out = {"ext": torch.empty((batch, nrow, 4), dtype=torch.float64, device=dev), "when": torch.empty((batch, nrow, 2), dtype=torch.float64, device=dev),
                "status": torch.empty((batch, nrow), dtype=torch.int32, device=dev), "npieces": torch.empty((batch, nrow), dtype=torch.int32, device=dev)}

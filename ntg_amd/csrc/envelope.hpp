@@ -154,11 +154,12 @@ struct EnvPoly {
 template <int KM>
 __device__ __forceinline__ void env_entries(const EnvArgs &A, const double *tab, const double *xrow, int b, int tid, int nthr)
 {
+	const CertLin &L = A.lin;
 	const int npc = A.npc, nsub = A.nsub, msk = (1 << nsub) - 1;
-	for (int e = tid; e < A.nout * npc; e += nthr) {
-		const int o = e / npc, q = e - o * npc, dm = A.d[o];
-		const EnvClass C = A.c[A.cls[o]];
-		const size_t base = ((size_t)b * A.nz + A.iz[o]) * npc + q;
+	for (int e = tid; e < L.nout * npc; e += nthr) {
+		const int o = e / npc, q = e - o * npc, dm = L.d[o];
+		const EnvClass C = A.g.c[L.cls[o]];
+		const size_t base = ((size_t)b * L.nz + L.iz[o]) * npc + q;
 		if (q >= (C.l << nsub)) {   // past the output's own pieces: the empty set
 			for (int r = 0; r < dm; r++) {
 				if (A.lo) A.lo[base + (size_t)r * npc] = INFINITY;
@@ -168,7 +169,7 @@ __device__ __forceinline__ void env_entries(const EnvArgs &A, const double *tab,
 		}
 		const int j = q >> nsub, i = q & msk;
 		EnvPoly<KM> P;
-		P.extract(tab + C.eoff + j * C.k * C.k, xrow + A.iC[o] + C.k - 1 + j * (C.k - C.m), C.k);
+		P.extract(tab + C.eoff + j * C.k * C.k, xrow + L.iC[o] + C.k - 1 + j * (C.k - C.m), C.k);
 		const double h = tab[C.hoff + j];
 		for (int r = 0; r < dm; r++) {
 			const int d = C.k - 1 - r;
@@ -185,63 +186,92 @@ __device__ __forceinline__ void env_entries(const EnvArgs &A, const double *tab,
 	}
 }
 
+// Shape of linear row lr: the basis class cl of the first entry it names (class of output 0 for a row of zeros), the largest degree D among
+// the entries it names (0 for a row of zeros: the zero polynomial, one point), and flag = 1 when every entry named belongs to one class.
+// c: the class table (a kernel's argument or its copy in LDS)
+struct EnvRowShape { int cl, D, flag; };
+__device__ __forceinline__ EnvRowShape env_row_shape(const CertLin &L, const EnvClass *c, const double *lr)
+{
+	EnvRowShape R{-1, 0, 1};
+	int first = -1;
+	for (int o = 0; o < L.nout; o++) {
+		const int k = c[L.cls[o]].k;
+		for (int r = 0; r < L.d[o]; r++) {
+			if (lr[L.iz[o] + r] == 0.0) continue;
+			if (first < 0) first = o;
+			else if (L.cls[o] != L.cls[first]) R.flag = 0;
+			if (r < k) { if (R.cl < 0) R.cl = L.cls[o]; R.D = max(R.D, k - 1 - r); }
+		}
+	}
+	if (R.cl < 0) R.cl = L.cls[0];
+	return R;
+}
+
+// Polygon (degree D) of linear row lr of class cl = C on piece [i, i + 1] / (msk + 1) of knot interval j: every named entry's polygon
+// elevated to D, the polygons summed with the row's coefficients, v ascending
+template <int KM>
+__device__ __forceinline__ EnvPoly<KM> env_poly_lin(const CertLin &L, const double *lr, int cl, int D, const EnvClass C, const double *tab, const double *xrow, int j, int i, int msk)
+{
+	const double h = tab[C.hoff + j];
+	EnvPoly<KM> S;
+#pragma unroll
+	for (int s = 0; s < KM; s++) S.b[s] = 0.0;
+	for (int o = 0; o < L.nout; o++) {
+		if (L.cls[o] != cl) continue;   // (a row that names another class has flag 0: the host refuses it, or no statement is made)
+		const double *lo_r = lr + L.iz[o];
+		bool any = false;
+		for (int r = 0; r < L.d[o] && r < C.k; r++) any = any || lo_r[r] != 0.0;
+		if (!any) continue;
+		EnvPoly<KM> P;
+		P.extract(tab + C.eoff + j * C.k * C.k, xrow + L.iC[o] + C.k - 1 + j * (C.k - C.m), C.k);
+		for (int r = 0; r < L.d[o] && r < C.k; r++) {
+			const int d = C.k - 1 - r;
+			if (r > 0) P.diff(d + 1, h);
+			const double w = lo_r[r];
+			if (w != 0.0) {
+				EnvPoly<KM> Q = P;
+				Q.piece(d, i, msk);
+				for (int t = d; t < D; t++) Q.elevate(t);
+#pragma unroll
+				for (int s = 0; s < KM; s++) { if (s <= D) S.b[s] += w * Q.b[s]; }
+			}
+		}
+	}
+	return S;
+}
+
+// violation of the bounds [l, u] by a row enclosed in [lo, hi]: max(l - lo, hi - u, 0), an infinite bound is none
+__device__ __forceinline__ double env_viol(double l, double u, double lo, double hi)
+{
+	double v = 0.0;
+	if (fabs(l) < NTG_INF_BOUND) v = env_max(v, l - lo);
+	if (fabs(u) < NTG_INF_BOUND) v = env_max(v, hi - u);
+	return v;
+}
+
 // row envelope of problem b and its largest certified violation (bv, bk): one thread per (row, piece), pieces fastest
 template <int KM>
 __device__ __forceinline__ void env_rows(const EnvArgs &A, const double *tab, const double *xrow, int b, int tid, int nthr, double &bv, long long &bk)
 {
+	const CertLin &L = A.lin;
 	const int npc = A.npc, nsub = A.nsub, msk = (1 << nsub) - 1;
 	const bool want_v = A.viol || A.where;
-	for (int e = tid; e < A.nltc * npc; e += nthr) {
+	for (int e = tid; e < L.nltc * npc; e += nthr) {
 		const int row = e / npc, q = e - row * npc;
-		const double *lr = A.ltc + (size_t)row * A.nz;
-		// the row's basis class (that of the first entry it names) and the largest degree among the entries it names
-		int cl = -1, D = -1;
-		for (int o = 0; o < A.nout; o++) {
-			const int k = A.c[A.cls[o]].k;
-			for (int r = 0; r < A.d[o] && r < k; r++)
-				if (lr[A.iz[o] + r] != 0.0) { if (cl < 0) cl = A.cls[o]; D = max(D, k - 1 - r); }
-		}
-		if (cl < 0) cl = A.cls[0];   // a row of zeros: the zero polynomial on the pieces of output 0
-		const EnvClass C = A.c[cl];
+		const double *lr = L.ltc + (size_t)row * L.nz;
+		const EnvRowShape R = env_row_shape(L, A.g.c, lr);
+		const EnvClass C = A.g.c[R.cl];
 		const bool live = q < (C.l << nsub);
 		double lo = INFINITY, hi = -INFINITY;
 		if (live) {
-			const int j = q >> nsub, i = q & msk;
-			const double h = tab[C.hoff + j];
-			EnvPoly<KM> S;
-#pragma unroll
-			for (int s = 0; s < KM; s++) S.b[s] = 0.0;
-			for (int o = 0; o < A.nout; o++) {
-				if (A.cls[o] != cl) continue;   // (the host has refused rows that name another class)
-				const double *lo_r = lr + A.iz[o];
-				bool any = false;
-				for (int r = 0; r < A.d[o] && r < C.k; r++) any = any || lo_r[r] != 0.0;
-				if (!any) continue;
-				EnvPoly<KM> P;
-				P.extract(tab + C.eoff + j * C.k * C.k, xrow + A.iC[o] + C.k - 1 + j * (C.k - C.m), C.k);
-				for (int r = 0; r < A.d[o] && r < C.k; r++) {
-					const int d = C.k - 1 - r;
-					if (r > 0) P.diff(d + 1, h);
-					const double w = lo_r[r];
-					if (w != 0.0) {
-						EnvPoly<KM> Q = P;
-						Q.piece(d, i, msk);
-						for (int t = d; t < D; t++) Q.elevate(t);
-#pragma unroll
-						for (int s = 0; s < KM; s++) { if (s <= D) S.b[s] += w * Q.b[s]; }
-					}
-				}
-			}
-			S.range(D, lo, hi);
+			const EnvPoly<KM> S = env_poly_lin<KM>(L, lr, R.cl, R.D, C, tab, xrow, q >> nsub, q & msk, msk);
+			S.range(R.D, lo, hi);
 		}
-		const size_t at = ((size_t)b * A.nltc + row) * npc + q;
+		const size_t at = ((size_t)b * L.nltc + row) * npc + q;
 		if (A.row_lo) A.row_lo[at] = lo;
 		if (A.row_hi) A.row_hi[at] = hi;
 		if (want_v && live) {
-			const double l = A.lower[(size_t)b * A.nbounds + A.slot0 + row], u = A.upper[(size_t)b * A.nbounds + A.slot0 + row];
-			double v = 0.0;
-			if (fabs(l) < NTG_INF_BOUND) v = env_max(v, l - lo);
-			if (fabs(u) < NTG_INF_BOUND) v = env_max(v, hi - u);
+			const double v = env_viol(A.g.lower[(size_t)b * A.g.nbounds + L.slot0 + row], A.g.upper[(size_t)b * A.g.nbounds + L.slot0 + row], lo, hi);
 			env_take(bv, bk, v, (v > 0.0 || v != v) ? (long long)e : -1ll);
 		}
 	}
@@ -252,10 +282,50 @@ __device__ __forceinline__ void env_wave_max(double &bv, long long &bk)
 	env_xchg_step<1>(bv, bk); env_xchg_step<2>(bv, bk); env_xchg_step<4>(bv, bk);
 	env_xchg_step<8>(bv, bk); env_xchg_step<16>(bv, bk); env_xchg_step<32>(bv, bk);
 }
-__device__ __forceinline__ void env_store_max(const EnvArgs &A, int b, double bv, long long bk)
+// the workgroup's maximum, into thread 0: the wave butterfly, then the waves' slots r_v / r_k [NT / 64] in index order
+template <int NT>
+__device__ __forceinline__ void env_group_max(double &bv, long long &bk, double *r_v, long long *r_k, int tid)
 {
-	if (A.viol) A.viol[b] = bk < 0 ? 0.0 : bv;
-	if (A.where) { A.where[2 * (size_t)b] = bk < 0 ? -1 : (int)(bk / A.npc); A.where[2 * (size_t)b + 1] = bk < 0 ? -1 : (int)(bk % A.npc); }
+	env_wave_max(bv, bk);
+	if ((tid & 63) == 0) { r_v[tid >> 6] = bv; r_k[tid >> 6] = bk; }
+	__syncthreads();
+	if (tid == 0) { for (int w = 1; w < NT / 64; w++) env_take(bv, bk, r_v[w], r_k[w]); }
+}
+// problem b's violation and its key as (row, piece)
+__device__ __forceinline__ void env_store_max(double *viol, int *where, int npc, int b, double bv, long long bk)
+{
+	if (viol) viol[b] = bk < 0 ? 0.0 : bv;
+	if (where) { where[2 * (size_t)b] = bk < 0 ? -1 : (int)(bk / npc); where[2 * (size_t)b + 1] = bk < 0 ? -1 : (int)(bk % npc); }
+}
+
+// Shared grids, once per workgroup: weights and interval lengths of every basis class into tab.  kns: room for the breaks -- of every class
+// at koff[c], where they are needed afterwards, or (koff null) of one class at a time
+__device__ __forceinline__ void env_build_classes(const CertBase &G, double *tab, double *kns, const int *koff, int tid, int nthr)
+{
+	for (int c = 0; c < G.nclass; c++) {
+		const EnvClass C = G.c[c];
+		double *kn = kns + (koff ? koff[c] : 0);
+		__syncthreads();   // the class before is done with kn
+		for (int i = tid; i <= C.l; i += nthr) kn[i] = G.knots[c][i];
+		__syncthreads();
+		env_build(kn, C, tab + C.eoff, tab + C.hoff, tid, nthr);
+	}
+	__syncthreads();
+}
+// the x row of problem b and, for sum-of-squares rows that read one (S and S->np non-zero), its parameter row into LDS
+__device__ __forceinline__ void env_stage_rows(const CertBase &G, const CertSos *S, int b, double *xrow, double *prow, int tid, int nthr)
+{
+	const double *src = G.x + (size_t)b * G.nC;
+	for (int i = tid; i < G.nC; i += nthr) xrow[i] = src[i];
+	if (S) { for (int i = tid; i < S->np; i += nthr) prow[i] = S->prm[(size_t)b * S->pp_prm + i]; }
+}
+// per-problem grids, by the wave that owns problem b: its breaks (one class), then its rows
+__device__ __forceinline__ void env_stage_pp(const CertBase &G, const CertSos *S, int b, double *kn, double *xrow, double *prow, int lane)
+{
+	const int l = G.c[0].l;
+	const double *kt = G.knots[0] + (size_t)b * (l + 1);
+	for (int i = lane; i <= l; i += 64) kn[i] = kt[i];
+	env_stage_rows(G, S, b, xrow, prow, lane, 64);
 }
 
 template <int NT, int KM>
@@ -266,34 +336,21 @@ envelope_shared_kernel(EnvArgs A)
 	__shared__ double r_v[NT / 64];
 	__shared__ long long r_k[NT / 64];
 	double *tab = reinterpret_cast<double *>(smem_raw);   // weights and interval lengths of every basis class
-	double *xrow = tab + A.ne;                            // [nC]
-	double *kn = xrow + A.nC;                             // breaks of the class being set up
+	double *xrow = tab + A.g.ne;                          // [nC]
+	double *kn = xrow + A.g.nC;                           // breaks of the class being set up
 	const int tid = threadIdx.x;
-	for (int c = 0; c < A.nclass; c++) {
-		const EnvClass C = A.c[c];
-		__syncthreads();   // the class before is done with kn
-		for (int i = tid; i <= C.l; i += NT) kn[i] = A.knots[c][i];
-		__syncthreads();
-		env_build(kn, C, tab + C.eoff, tab + C.hoff, tid, NT);
-	}
-	__syncthreads();
+	env_build_classes(A.g, tab, kn, nullptr, tid, NT);
 	const bool want_e = A.lo || A.hi, want_v = A.viol || A.where, want_r = A.row_lo || A.row_hi || want_v;
-	for (int b = blockIdx.x; b < A.batch; b += gridDim.x) {
-		const double *src = A.x + (size_t)b * A.nC;
-		for (int i = tid; i < A.nC; i += NT) xrow[i] = src[i];
+	for (int b = blockIdx.x; b < A.g.batch; b += gridDim.x) {
+		env_stage_rows(A.g, nullptr, b, xrow, nullptr, tid, NT);
 		__syncthreads();
 		if (want_e) env_entries<KM>(A, tab, xrow, b, tid, NT);
 		if (want_r) {
 			double bv = 0.0; long long bk = -1;
 			env_rows<KM>(A, tab, xrow, b, tid, NT, bv, bk);
 			if (want_v) {
-				env_wave_max(bv, bk);
-				if ((tid & 63) == 0) { r_v[tid >> 6] = bv; r_k[tid >> 6] = bk; }
-				__syncthreads();
-				if (tid == 0) {
-					for (int w = 1; w < NT / 64; w++) env_take(bv, bk, r_v[w], r_k[w]);
-					env_store_max(A, b, bv, bk);
-				}
+				env_group_max<NT>(bv, bk, r_v, r_k, tid);
+				if (tid == 0) env_store_max(A.viol, A.where, A.npc, b, bv, bk);
 			}
 		}
 		__syncthreads();   // xrow and the waves' slots are free again
@@ -307,21 +364,17 @@ envelope_pp_kernel(EnvArgs A)
 {
 	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
 	constexpr int NW = NT / 64;
-	const EnvClass C = A.c[0];
+	const EnvClass C = A.g.c[0];
 	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-	double *tab = reinterpret_cast<double *>(smem_raw) + (size_t)wave * (A.ne + A.nC + C.l + 1);
-	double *xrow = tab + A.ne, *kn = xrow + A.nC;
+	double *tab = reinterpret_cast<double *>(smem_raw) + (size_t)wave * (A.g.ne + A.g.nC + C.l + 1);
+	double *xrow = tab + A.g.ne, *kn = xrow + A.g.nC;
 	const bool want_e = A.lo || A.hi, want_v = A.viol || A.where, want_r = A.row_lo || A.row_hi || want_v;
 	const int per_pass = gridDim.x * NW;
-	for (int b0 = 0; b0 < A.batch; b0 += per_pass) {   // (the same trip count for every wave of the grid: the barriers below are uniform)
+	for (int b0 = 0; b0 < A.g.batch; b0 += per_pass) {   // (the same trip count for every wave of the grid: the barriers below are uniform)
 		const int b = b0 + blockIdx.x * NW + wave;
-		const bool on = b < A.batch;
+		const bool on = b < A.g.batch;
 		__syncthreads();
-		if (on) {
-			const double *kt = A.knots[0] + (size_t)b * (C.l + 1), *src = A.x + (size_t)b * A.nC;
-			for (int i = lane; i <= C.l; i += 64) kn[i] = kt[i];
-			for (int i = lane; i < A.nC; i += 64) xrow[i] = src[i];
-		}
+		if (on) env_stage_pp(A.g, nullptr, b, kn, xrow, nullptr, lane);
 		__syncthreads();
 		if (on) env_build(kn, C, tab + C.eoff, tab + C.hoff, lane, 64);
 		__syncthreads();
@@ -332,7 +385,7 @@ envelope_pp_kernel(EnvArgs A)
 				env_rows<KM>(A, tab, xrow, b, lane, 64, bv, bk);
 				if (want_v) {
 					env_wave_max(bv, bk);
-					if (lane == 0) env_store_max(A, b, bv, bk);
+					if (lane == 0) env_store_max(A.viol, A.where, A.npc, b, bv, bk);
 				}
 			}
 		}

@@ -46,7 +46,7 @@ __device__ __forceinline__ void sos_square_into(EnvPoly<2 * KM - 1> &S, const En
 }
 
 // the product tables of every degree, unfolded from the triangles of the kernel argument: one thread per weight
-__device__ __forceinline__ void sos_unfold(const SosArgs &A, double *wl, int tid, int nthr)
+__device__ __forceinline__ void sos_unfold(const CertSos &A, double *wl, int tid, int nthr)
 {
 	for (int e = tid; e < NTG_SOS_WFULL; e += nthr) {
 		int d = 0;
@@ -58,13 +58,52 @@ __device__ __forceinline__ void sos_unfold(const SosArgs &A, double *wl, int tid
 
 // the row, term and class tables a thread looks up by its own row: copied from the kernel argument into LDS, every copy at a uniform index
 struct SosTables { SosRow row[NTG_SOS_MAXROWS]; SosTerm term[NTG_SOS_MAXROWS][NTG_SOS_MAXTERMS]; EnvClass c[NTG_MAX_OUT]; };
-__device__ __forceinline__ void sos_stage(const SosArgs &A, SosTables &T, int tid)
+__device__ __forceinline__ void sos_stage(const CertSos &A, const CertBase &G, SosTables &T, int tid)
 {
 	for (int j = 0; j < A.nrow; j++) {
 		if (tid == 0) T.row[j] = A.row[j];
 		for (int t = 0; t < NTG_SOS_MAXTERMS; t++) { if (tid == 0) T.term[j][t] = A.term[j][t]; }
 	}
-	for (int c = 0; c < A.nclass; c++) { if (tid == 0) T.c[c] = A.c[c]; }
+	for (int c = 0; c < G.nclass; c++) { if (tid == 0) T.c[c] = G.c[c]; }
+}
+
+// Polygon (degree R.D) of sum-of-squares row `row` = R of class C on piece [i, i + 1] / (msk + 1) of knot interval j: the squares of its
+// terms' shifted polygons, elevated to R.D where they are lower, summed in term order
+template <int KM>
+__device__ __forceinline__ EnvPoly<2 * KM - 1> sos_poly(const SosTables &T, int row, const SosRow R, const EnvClass C, const double *wl, const double *tab, const double *xrow,
+                                                        const double *prow, int j, int i, int msk)
+{
+	constexpr int KD = 2 * KM - 1;
+	const double h = tab[C.hoff + j];
+	EnvPoly<KD> S;
+#pragma unroll
+	for (int s = 0; s < KD; s++) S.b[s] = 0.0;
+	for (int t = 0; t < R.nt; t++) {
+		const SosTerm Q = T.term[row][t];
+		const double sh = Q.s0 + (Q.poff >= 0 ? prow[Q.poff] : 0.0);
+		EnvPoly<KM> P;
+		int d = C.k - 1 - Q.r;
+		if (d >= 0) {
+			P.extract(tab + C.eoff + j * C.k * C.k, xrow + Q.iC + C.k - 1 + j * (C.k - C.m), C.k);
+			for (int r = 1; r <= Q.r; r++) P.diff(C.k - r, h);
+			P.piece(d, i, msk);
+		} else {   // a derivative of order >= k: the zero polynomial
+			d = 0;
+			P.b[0] = 0.0;
+		}
+#pragma unroll
+		for (int s = 0; s < KM; s++) P.b[s] = s <= d ? P.b[s] - sh : 0.0;
+		const double *W = wl + ntg_sos_wfull(d);
+		if (2 * d == R.D) sos_square_into<KM>(S, P, W, d, true);
+		else {   // a term of lower degree than the row: its polygon whole, elevated, then added
+			EnvPoly<KD> G;
+			sos_square_into<KM>(G, P, W, d, false);
+			for (int u = 2 * d; u < R.D; u++) G.elevate(u);
+#pragma unroll
+			for (int s = 0; s < KD; s++) { if (s <= R.D) S.b[s] += G.b[s]; }
+		}
+	}
+	return S;
 }
 
 // row envelope of problem b and its largest certified violation (bv, bk): one thread per (row, piece), pieces fastest
@@ -72,10 +111,9 @@ template <int KM>
 __device__ __forceinline__ void sos_rows(const SosArgs &A, const SosTables &T, const double *wl, const double *tab, const double *xrow, const double *prow, int b, int tid, int nthr,
                                          double &bv, long long &bk)
 {
-	constexpr int KD = 2 * KM - 1;
-	const int npc = A.npc, nsub = A.nsub, msk = (1 << nsub) - 1;
+	const int nrow = A.sos.nrow, npc = A.npc, nsub = A.nsub, msk = (1 << nsub) - 1;
 	const bool want_v = A.viol || A.where;
-	for (int e = tid; e < A.nrow * npc; e += nthr) {
+	for (int e = tid; e < nrow * npc; e += nthr) {
 		const int row = e / npc, q = e - row * npc;
 		const SosRow R = T.row[row];
 		const EnvClass C = T.c[R.cl];
@@ -83,55 +121,17 @@ __device__ __forceinline__ void sos_rows(const SosArgs &A, const SosTables &T, c
 		double lo = INFINITY, hi = -INFINITY;   // past the class's own pieces: the empty set
 		if (live && !R.flag) { lo = -INFINITY; hi = INFINITY; }   // no statement
 		else if (live) {
-			const int j = q >> nsub, i = q & msk;
-			const double h = tab[C.hoff + j];
-			EnvPoly<KD> S;
-#pragma unroll
-			for (int s = 0; s < KD; s++) S.b[s] = 0.0;
-			for (int t = 0; t < R.nt; t++) {
-				const SosTerm Q = T.term[row][t];
-				const double sh = Q.s0 + (Q.poff >= 0 ? prow[Q.poff] : 0.0);
-				EnvPoly<KM> P;
-				int d = C.k - 1 - Q.r;
-				if (d >= 0) {
-					P.extract(tab + C.eoff + j * C.k * C.k, xrow + Q.iC + C.k - 1 + j * (C.k - C.m), C.k);
-					for (int r = 1; r <= Q.r; r++) P.diff(C.k - r, h);
-					P.piece(d, i, msk);
-				} else {   // a derivative of order >= k: the zero polynomial
-					d = 0;
-					P.b[0] = 0.0;
-				}
-#pragma unroll
-				for (int s = 0; s < KM; s++) P.b[s] = s <= d ? P.b[s] - sh : 0.0;
-				const double *W = wl + ntg_sos_wfull(d);
-				if (2 * d == R.D) sos_square_into<KM>(S, P, W, d, true);
-				else {   // a term of lower degree than the row: its polygon whole, elevated, then added
-					EnvPoly<KD> G;
-					sos_square_into<KM>(G, P, W, d, false);
-					for (int u = 2 * d; u < R.D; u++) G.elevate(u);
-#pragma unroll
-					for (int s = 0; s < KD; s++) { if (s <= R.D) S.b[s] += G.b[s]; }
-				}
-			}
+			const EnvPoly<2 * KM - 1> S = sos_poly<KM>(T, row, R, C, wl, tab, xrow, prow, q >> nsub, q & msk, msk);
 			S.range(R.D, lo, hi);
 		}
-		const size_t at = ((size_t)b * A.nrow + row) * npc + q;
+		const size_t at = ((size_t)b * nrow + row) * npc + q;
 		if (A.q_lo) A.q_lo[at] = lo;
 		if (A.q_hi) A.q_hi[at] = hi;
 		if (want_v && live && R.flag) {
-			const double l = A.lower[(size_t)b * A.nbounds + A.slot0 + row], u = A.upper[(size_t)b * A.nbounds + A.slot0 + row];
-			double v = 0.0;
-			if (fabs(l) < NTG_INF_BOUND) v = env_max(v, l - lo);
-			if (fabs(u) < NTG_INF_BOUND) v = env_max(v, hi - u);
+			const double v = env_viol(A.g.lower[(size_t)b * A.g.nbounds + A.sos.slot0 + row], A.g.upper[(size_t)b * A.g.nbounds + A.sos.slot0 + row], lo, hi);
 			env_take(bv, bk, v, (v > 0.0 || v != v) ? (long long)e : -1ll);
 		}
 	}
-}
-
-__device__ __forceinline__ void sos_store_max(const SosArgs &A, int b, double bv, long long bk)
-{
-	if (A.viol) A.viol[b] = bk < 0 ? 0.0 : bv;
-	if (A.where) { A.where[2 * (size_t)b] = bk < 0 ? -1 : (int)(bk / A.npc); A.where[2 * (size_t)b + 1] = bk < 0 ? -1 : (int)(bk % A.npc); }
 }
 
 template <int NT, int KM>
@@ -144,36 +144,22 @@ envelope_sos_shared_kernel(SosArgs A)
 	__shared__ SosTables T;
 	double *wl = reinterpret_cast<double *>(smem_raw);    // the product tables, unfolded
 	double *tab = wl + NTG_SOS_WFULL;                     // weights and interval lengths of every basis class
-	double *xrow = tab + A.ne;                            // [nC]
-	double *prow = xrow + A.nC;                           // [np]
-	double *kn = prow + A.np;                             // breaks of the class being set up
+	double *xrow = tab + A.g.ne;                          // [nC]
+	double *prow = xrow + A.g.nC;                         // [np]
+	double *kn = prow + A.sos.np;                         // breaks of the class being set up
 	const int tid = threadIdx.x;
-	sos_stage(A, T, tid);
-	sos_unfold(A, wl, tid, NT);
-	for (int c = 0; c < A.nclass; c++) {
-		const EnvClass C = A.c[c];
-		__syncthreads();   // the class before is done with kn
-		for (int i = tid; i <= C.l; i += NT) kn[i] = A.knots[c][i];
-		__syncthreads();
-		env_build(kn, C, tab + C.eoff, tab + C.hoff, tid, NT);
-	}
-	__syncthreads();
+	sos_stage(A.sos, A.g, T, tid);
+	sos_unfold(A.sos, wl, tid, NT);
+	env_build_classes(A.g, tab, kn, nullptr, tid, NT);
 	const bool want_v = A.viol || A.where;
-	for (int b = blockIdx.x; b < A.batch; b += gridDim.x) {
-		const double *src = A.x + (size_t)b * A.nC;
-		for (int i = tid; i < A.nC; i += NT) xrow[i] = src[i];
-		for (int i = tid; i < A.np; i += NT) prow[i] = A.prm[(size_t)b * A.pp_prm + i];
+	for (int b = blockIdx.x; b < A.g.batch; b += gridDim.x) {
+		env_stage_rows(A.g, &A.sos, b, xrow, prow, tid, NT);
 		__syncthreads();
 		double bv = 0.0; long long bk = -1;
 		sos_rows<KM>(A, T, wl, tab, xrow, prow, b, tid, NT, bv, bk);
 		if (want_v) {
-			env_wave_max(bv, bk);
-			if ((tid & 63) == 0) { r_v[tid >> 6] = bv; r_k[tid >> 6] = bk; }
-			__syncthreads();
-			if (tid == 0) {
-				for (int w = 1; w < NT / 64; w++) env_take(bv, bk, r_v[w], r_k[w]);
-				sos_store_max(A, b, bv, bk);
-			}
+			env_group_max<NT>(bv, bk, r_v, r_k, tid);
+			if (tid == 0) env_store_max(A.viol, A.where, A.npc, b, bv, bk);
 		}
 		__syncthreads();   // xrow, prow and the waves' slots are free again
 	}
@@ -187,25 +173,20 @@ envelope_sos_pp_kernel(SosArgs A)
 	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
 	constexpr int NW = NT / 64;
 	__shared__ SosTables T;
-	const EnvClass C = A.c[0];
+	const EnvClass C = A.g.c[0];
 	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 	double *wl = reinterpret_cast<double *>(smem_raw);
-	double *tab = wl + NTG_SOS_WFULL + (size_t)wave * (A.ne + A.nC + A.np + C.l + 1);
-	double *xrow = tab + A.ne, *prow = xrow + A.nC, *kn = prow + A.np;
+	double *tab = wl + NTG_SOS_WFULL + (size_t)wave * (A.g.ne + A.g.nC + A.sos.np + C.l + 1);
+	double *xrow = tab + A.g.ne, *prow = xrow + A.g.nC, *kn = prow + A.sos.np;
 	const bool want_v = A.viol || A.where;
-	sos_stage(A, T, threadIdx.x);
-	sos_unfold(A, wl, threadIdx.x, NT);
+	sos_stage(A.sos, A.g, T, threadIdx.x);
+	sos_unfold(A.sos, wl, threadIdx.x, NT);
 	const int per_pass = gridDim.x * NW;
-	for (int b0 = 0; b0 < A.batch; b0 += per_pass) {   // (the same trip count for every wave of the grid: the barriers below are uniform)
+	for (int b0 = 0; b0 < A.g.batch; b0 += per_pass) {   // (the same trip count for every wave of the grid: the barriers below are uniform)
 		const int b = b0 + blockIdx.x * NW + wave;
-		const bool on = b < A.batch;
+		const bool on = b < A.g.batch;
 		__syncthreads();
-		if (on) {
-			const double *kt = A.knots[0] + (size_t)b * (C.l + 1), *src = A.x + (size_t)b * A.nC;
-			for (int i = lane; i <= C.l; i += 64) kn[i] = kt[i];
-			for (int i = lane; i < A.nC; i += 64) xrow[i] = src[i];
-			for (int i = lane; i < A.np; i += 64) prow[i] = A.prm[(size_t)b * A.pp_prm + i];
-		}
+		if (on) env_stage_pp(A.g, &A.sos, b, kn, xrow, prow, lane);
 		__syncthreads();
 		if (on) env_build(kn, C, tab + C.eoff, tab + C.hoff, lane, 64);
 		__syncthreads();
@@ -214,7 +195,7 @@ envelope_sos_pp_kernel(SosArgs A)
 			sos_rows<KM>(A, T, wl, tab, xrow, prow, b, lane, 64, bv, bk);
 			if (want_v) {
 				env_wave_max(bv, bk);
-				if (lane == 0) sos_store_max(A, b, bv, bk);
+				if (lane == 0) env_store_max(A.viol, A.where, A.npc, b, bv, bk);
 			}
 		}
 	}

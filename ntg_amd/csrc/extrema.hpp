@@ -5,7 +5,7 @@
 //
 // Per (problem, row), the definition of include/ntg_amd.h:
 //   level 0   the row's polygon on every knot interval j of its basis class: env_rows' sequence of operations for a linear row, sos_rows' for
-//             a sum-of-squares row, both at nsub = 0 (ext_poly_lin / ext_poly_sos restate them; the depth-0 test holds them to it bit for bit).
+//             a sum-of-squares row, both at nsub = 0: the same builders (env_poly_lin, sos_poly) on piece 0 of 1.
 //   level L   U / V = smallest / largest end value seen, with its time (smaller time on equal values): every lane folds in the ends of its
 //             pieces, the wave reduces by the butterfly.  A piece is open if its polygon reaches below U - tol (above V + tol); the others
 //             retire into Rlo / Rhi.  An open piece is split in the middle by de Casteljau (0.5 * (a + b) per new point, the ends carried over).
@@ -70,76 +70,6 @@ __device__ __forceinline__ double ext_last(const EnvPoly<KD> &P, int D)
 	return __longlong_as_double(v);
 }
 
-// polygon of linear row lr (class cl, degree D) on knot interval j: env_rows' operations at nsub = 0
-template <int KM>
-__device__ __forceinline__ void ext_poly_lin(const ExtArgs &A, const double *lr, int cl, int D, const EnvClass C, const double *tab, const double *xrow, int j,
-                                             EnvPoly<2 * KM - 1> &S)
-{
-	const double h = tab[C.hoff + j];
-	EnvPoly<KM> L;
-#pragma unroll
-	for (int s = 0; s < KM; s++) L.b[s] = 0.0;
-	for (int o = 0; o < A.nout; o++) {
-		if (A.cls[o] != cl) continue;
-		const double *lo_r = lr + A.iz[o];
-		bool any = false;
-		for (int r = 0; r < A.d[o] && r < C.k; r++) any = any || lo_r[r] != 0.0;
-		if (!any) continue;
-		EnvPoly<KM> P;
-		P.extract(tab + C.eoff + j * C.k * C.k, xrow + A.iC[o] + C.k - 1 + j * (C.k - C.m), C.k);
-		for (int r = 0; r < A.d[o] && r < C.k; r++) {
-			const int d = C.k - 1 - r;
-			if (r > 0) P.diff(d + 1, h);
-			const double w = lo_r[r];
-			if (w != 0.0) {
-				EnvPoly<KM> Q = P;
-				for (int t = d; t < D; t++) Q.elevate(t);
-#pragma unroll
-				for (int s = 0; s < KM; s++) { if (s <= D) L.b[s] += w * Q.b[s]; }
-			}
-		}
-	}
-#pragma unroll
-	for (int s = 0; s < 2 * KM - 1; s++) S.b[s] = 0.0;
-#pragma unroll
-	for (int s = 0; s < KM; s++) S.b[s] = L.b[s];
-}
-
-// polygon of sum-of-squares row `row` on knot interval j: sos_rows' operations at nsub = 0
-template <int KM>
-__device__ __forceinline__ void ext_poly_sos(const SosTables &T, int row, const SosRow R, const EnvClass C, const double *wl, const double *tab, const double *xrow,
-                                             const double *prow, int j, EnvPoly<2 * KM - 1> &S)
-{
-	constexpr int KD = 2 * KM - 1;
-	const double h = tab[C.hoff + j];
-#pragma unroll
-	for (int s = 0; s < KD; s++) S.b[s] = 0.0;
-	for (int t = 0; t < R.nt; t++) {
-		const SosTerm Q = T.term[row][t];
-		const double sh = Q.s0 + (Q.poff >= 0 ? prow[Q.poff] : 0.0);
-		EnvPoly<KM> P;
-		int d = C.k - 1 - Q.r;
-		if (d >= 0) {
-			P.extract(tab + C.eoff + j * C.k * C.k, xrow + Q.iC + C.k - 1 + j * (C.k - C.m), C.k);
-			for (int r = 1; r <= Q.r; r++) P.diff(C.k - r, h);
-		} else {   // a derivative of order >= k: the zero polynomial
-			d = 0;
-			P.b[0] = 0.0;
-		}
-#pragma unroll
-		for (int s = 0; s < KM; s++) P.b[s] = s <= d ? P.b[s] - sh : 0.0;
-		const double *W = wl + ntg_sos_wfull(d);
-		if (2 * d == R.D) sos_square_into<KM>(S, P, W, d, true);
-		else {   // a term of lower degree than the row: its polygon whole, elevated, then added
-			EnvPoly<KD> G;
-			sos_square_into<KM>(G, P, W, d, false);
-			for (int u = 2 * d; u < R.D; u++) G.elevate(u);
-#pragma unroll
-			for (int s = 0; s < KD; s++) { if (s <= R.D) S.b[s] += G.b[s]; }
-		}
-	}
-}
-
 // what a wave works with: the workgroup's (or its own) tables and its own rows and work list, all in LDS
 struct ExtLds {
 	const double *wl, *tab, *kns, *xrow, *prow;
@@ -152,26 +82,11 @@ template <int KM>
 __device__ __forceinline__ void ext_row(const ExtArgs &A, const SosTables &T, const ExtLds &M, int row, int lane, double (&res)[4], double (&tw)[2], int &status, int &npieces)
 {
 	constexpr int KD = 2 * KM - 1;
-	const bool lin = row < A.nltc;
-	const double *lr = A.ltc + (size_t)(lin ? row : 0) * A.nz;
-	const SosRow R = T.row[lin ? 0 : row - A.nltc];   // (a linear row reads none of it)
-	int cl = -1, D = -1, flag = 1;
-	if (lin) {   // the row's basis class and degree as env_rows finds them; flag 0: it names outputs of different classes
-		int first = -1;
-		for (int o = 0; o < A.nout; o++) {
-			const int k = T.c[A.cls[o]].k;
-			for (int r = 0; r < A.d[o]; r++) {
-				if (lr[A.iz[o] + r] == 0.0) continue;
-				if (first < 0) first = o;
-				else if (A.cls[o] != A.cls[first]) flag = 0;
-				if (r < k) { if (cl < 0) cl = A.cls[o]; D = max(D, k - 1 - r); }
-			}
-		}
-		if (cl < 0) cl = A.cls[0];
-		if (D < 0) D = 0;   // a row of zeros: the zero polynomial, one point
-	} else {
-		cl = R.cl; D = R.D; flag = R.flag;
-	}
+	const bool lin = row < A.lin.nltc;
+	const double *lr = A.lin.ltc + (size_t)(lin ? row : 0) * A.lin.nz;
+	const SosRow R = T.row[lin ? 0 : row - A.lin.nltc];   // (a linear row reads none of it)
+	int cl = R.cl, D = R.D, flag = R.flag;
+	if (lin) { const EnvRowShape sh = env_row_shape(A.lin, T.c, lr); cl = sh.cl; D = sh.D; flag = sh.flag; }
 	if (!flag) {
 		res[0] = -INFINITY; res[1] = INFINITY; res[2] = -INFINITY; res[3] = INFINITY;
 		tw[0] = tw[1] = NAN; status = NTG_EXTREMA_NONE; npieces = 0;
@@ -199,8 +114,13 @@ __device__ __forceinline__ void ext_row(const ExtArgs &A, const SosTables &T, co
 		const int j = lane + 64 * (second ? it - npass : it);
 		const bool on = j < C.l;
 		if (on && (!second || npass > 1)) {
-			if (lin) ext_poly_lin<KM>(A, lr, cl, D, C, M.tab, M.xrow, j, P);
-			else ext_poly_sos<KM>(T, row - A.nltc, R, C, M.wl, M.tab, M.xrow, M.prow, j, P);
+			if (lin) {   // the whole interval: piece 0 of 1
+				const EnvPoly<KM> L = env_poly_lin<KM>(A.lin, lr, cl, D, C, M.tab, M.xrow, j, 0, 0);
+#pragma unroll
+				for (int s = 0; s < KD; s++) P.b[s] = 0.0;
+#pragma unroll
+				for (int s = 0; s < KM; s++) P.b[s] = L.b[s];
+			} else P = sos_poly<KM>(T, row - A.lin.nltc, R, C, M.wl, M.tab, M.xrow, M.prow, j, 0, 0);
 		}
 		if (!second) {
 			if (on) {
@@ -330,7 +250,7 @@ __device__ __forceinline__ void ext_row(const ExtArgs &A, const SosTables &T, co
 template <int KM>
 __device__ __forceinline__ void ext_problem(const ExtArgs &A, const SosTables &T, const ExtLds &M, int b, int lane)
 {
-	const int nrow = A.nltc + A.s.nrow;
+	const int nltc = A.lin.nltc, nrow = nltc + A.sos.nrow;
 	const bool want_v = A.viol || A.where;
 	double av = 0.0, cv = 0.0; long long ak = -1, ck = -1;
 	for (int row = 0; row < nrow; row++) {
@@ -345,11 +265,9 @@ __device__ __forceinline__ void ext_problem(const ExtArgs &A, const SosTables &T
 			if (A.npieces) A.npieces[at] = npieces;
 		}
 		if (want_v) {   // (every row has flag 1: the host has refused the others)
-			const int slot = row < A.nltc ? A.slot_lin + row : A.s.slot0 + row - A.nltc;
-			const double l = A.s.lower[(size_t)b * A.s.nbounds + slot], u = A.s.upper[(size_t)b * A.s.nbounds + slot];
-			double a = 0.0, c = 0.0;
-			if (fabs(l) < NTG_INF_BOUND) { a = env_max(a, l - res[1]); c = env_max(c, l - res[0]); }
-			if (fabs(u) < NTG_INF_BOUND) { a = env_max(a, res[2] - u); c = env_max(c, res[3] - u); }
+			const int slot = row < nltc ? A.lin.slot0 + row : A.sos.slot0 + row - nltc;
+			const double l = A.g.lower[(size_t)b * A.g.nbounds + slot], u = A.g.upper[(size_t)b * A.g.nbounds + slot];
+			const double a = env_viol(l, u, res[1], res[2]), c = env_viol(l, u, res[0], res[3]);   // of the attained values, of the certified ones
 			env_take(av, ak, a, (a > 0.0 || a != a) ? (long long)row : -1ll);
 			env_take(cv, ck, c, (c > 0.0 || c != c) ? (long long)row : -1ll);
 		}
@@ -370,24 +288,18 @@ extrema_shared_kernel(ExtArgs A)
 	const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
 	double *wl = reinterpret_cast<double *>(smem_raw);    // the product tables, unfolded
 	double *tab = wl + NTG_SOS_WFULL;                     // weights and interval lengths of every basis class
-	double *kns = tab + A.s.ne;                           // breaks of every basis class
-	double *mine = kns + A.nk + (size_t)wave * (A.s.nC + A.s.np + NTG_EXTREMA_CAP * (KD + 1));
-	double *xrow = mine, *prow = xrow + A.s.nC, *list = prow + A.s.np;
+	double *kns = tab + A.g.ne;                           // breaks of every basis class
+	double *mine = kns + A.nk + (size_t)wave * (A.g.nC + A.sos.np + NTG_EXTREMA_CAP * (KD + 1));
+	double *xrow = mine, *prow = xrow + A.g.nC, *list = prow + A.sos.np;
 	const ExtLds M{wl, tab, kns, xrow, prow, list, reinterpret_cast<long long *>(list + NTG_EXTREMA_CAP * KD)};
-	sos_stage(A.s, T, tid);
-	sos_unfold(A.s, wl, tid, NT);
-	for (int c = 0; c < A.s.nclass; c++)
-		for (int i = tid; i <= A.s.c[c].l; i += NT) kns[A.koff[c] + i] = A.s.knots[c][i];
-	__syncthreads();
-	for (int c = 0; c < A.s.nclass; c++) env_build(kns + A.koff[c], A.s.c[c], tab + A.s.c[c].eoff, tab + A.s.c[c].hoff, tid, NT);
-	__syncthreads();
-	for (int b0 = blockIdx.x * NW; b0 < A.s.batch; b0 += gridDim.x * NW) {
+	sos_stage(A.sos, A.g, T, tid);
+	sos_unfold(A.sos, wl, tid, NT);
+	env_build_classes(A.g, tab, kns, A.koff, tid, NT);
+	for (int b0 = blockIdx.x * NW; b0 < A.g.batch; b0 += gridDim.x * NW) {
 		const int b = b0 + wave;
-		if (b >= A.s.batch) continue;
+		if (b >= A.g.batch) continue;
 		__builtin_amdgcn_wave_barrier();   // the problem before is done with the rows
-		const double *src = A.s.x + (size_t)b * A.s.nC;
-		for (int i = lane; i < A.s.nC; i += 64) xrow[i] = src[i];
-		for (int i = lane; i < A.s.np; i += 64) prow[i] = A.s.prm[(size_t)b * A.s.pp_prm + i];
+		env_stage_rows(A.g, &A.sos, b, xrow, prow, lane, 64);
 		__builtin_amdgcn_wave_barrier();
 		ext_problem<KM>(A, T, M, b, lane);
 	}
@@ -401,25 +313,20 @@ extrema_pp_kernel(ExtArgs A)
 	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
 	constexpr int NW = NT / 64, KD = 2 * KM - 1;
 	__shared__ SosTables T;
-	const EnvClass C = A.s.c[0];
+	const EnvClass C = A.g.c[0];
 	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 	double *wl = reinterpret_cast<double *>(smem_raw);
-	double *tab = wl + NTG_SOS_WFULL + (size_t)wave * (A.s.ne + A.nk + A.s.nC + A.s.np + NTG_EXTREMA_CAP * (KD + 1));
-	double *kns = tab + A.s.ne, *xrow = kns + A.nk, *prow = xrow + A.s.nC, *list = prow + A.s.np;
+	double *tab = wl + NTG_SOS_WFULL + (size_t)wave * (A.g.ne + A.nk + A.g.nC + A.sos.np + NTG_EXTREMA_CAP * (KD + 1));
+	double *kns = tab + A.g.ne, *xrow = kns + A.nk, *prow = xrow + A.g.nC, *list = prow + A.sos.np;
 	const ExtLds M{wl, tab, kns, xrow, prow, list, reinterpret_cast<long long *>(list + NTG_EXTREMA_CAP * KD)};
-	sos_stage(A.s, T, threadIdx.x);
-	sos_unfold(A.s, wl, threadIdx.x, NT);
+	sos_stage(A.sos, A.g, T, threadIdx.x);
+	sos_unfold(A.sos, wl, threadIdx.x, NT);
 	const int per_pass = gridDim.x * NW;
-	for (int b0 = 0; b0 < A.s.batch; b0 += per_pass) {   // (the same trip count for every wave of the grid: the barriers below are uniform)
+	for (int b0 = 0; b0 < A.g.batch; b0 += per_pass) {   // (the same trip count for every wave of the grid: the barriers below are uniform)
 		const int b = b0 + blockIdx.x * NW + wave;
-		const bool on = b < A.s.batch;
+		const bool on = b < A.g.batch;
 		__syncthreads();
-		if (on) {
-			const double *kt = A.s.knots[0] + (size_t)b * (C.l + 1), *src = A.s.x + (size_t)b * A.s.nC;
-			for (int i = lane; i <= C.l; i += 64) kns[i] = kt[i];
-			for (int i = lane; i < A.s.nC; i += 64) xrow[i] = src[i];
-			for (int i = lane; i < A.s.np; i += 64) prow[i] = A.s.prm[(size_t)b * A.s.pp_prm + i];
-		}
+		if (on) env_stage_pp(A.g, &A.sos, b, kns, xrow, prow, lane);
 		__syncthreads();
 		if (on) env_build(kns, C, tab + C.eoff, tab + C.hoff, lane, 64);
 		__syncthreads();

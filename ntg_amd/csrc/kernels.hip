@@ -624,75 +624,52 @@ hipError_t ntg_launch_refine(const RefineArgs &A, int pp, int ncu, hipStream_t s
 	return hipGetLastError();
 }
 
-// ntg_batch_envelope (envelope.hpp): the instance with the smallest private polygons that hold the plan's largest order.
-// hipErrorInvalidValue: the tables exceed the LDS.
-template <int KM>
-static hipError_t launch_envelope(const EnvArgs &A, int ncu, size_t lds, hipStream_t st)
+// The time certificates (envelope.hpp, envelope_sos.hpp, extrema.hpp).  Each has a kernel for per-problem grids (kpp: one problem per wave,
+// a workgroup per nt / 64 problems) and one for shared grids (ksh: persistent workgroups; each builds its weights once, so each should
+// stream several of the `units` of work: a workgroup for every four of them, no more than fill the device), both in the instance with the
+// smallest private polygons that hold the plan's largest order (KM = 6 or NTG_MAX_ORDER).
+template <class Args>
+static hipError_t launch_cert(void (*kpp)(Args), void (*ksh)(Args), const Args &A, int nt, int units, int ncu, size_t lds, hipStream_t st)
 {
-	if (A.pp) {
-		const int groups = (A.batch + NTG_ENVELOPE_NT / 64 - 1) / (NTG_ENVELOPE_NT / 64);
-		hipLaunchKernelGGL((envelope_pp_kernel<NTG_ENVELOPE_NT, KM>), dim3(std::min(groups, 8 * ncu)), dim3(NTG_ENVELOPE_NT), lds, st, A);
-	} else {
-		// persistent workgroups: each builds its weights once, so each should stream several problems; no more than fill the device
-		const int grid = std::max(1, std::min((A.batch + 3) / 4, 8 * ncu));
-		hipLaunchKernelGGL((envelope_shared_kernel<NTG_ENVELOPE_NT, KM>), dim3(grid), dim3(NTG_ENVELOPE_NT), lds, st, A);
-	}
-	return hipGetLastError();
-}
-hipError_t ntg_launch_envelope(const EnvArgs &A, int ncu, hipStream_t st)
-{
-	const size_t lds = ntg_envelope_lds(A);
-	if (lds > NTG_ENVELOPE_LDS_MAX || A.kmax > NTG_MAX_ORDER) return hipErrorInvalidValue;   // (ntg_batch_envelope refuses such a plan before it gets here)
-	if (A.batch <= 0) return hipSuccess;
-	return A.kmax <= 6 ? launch_envelope<6>(A, ncu, lds, st) : launch_envelope<NTG_MAX_ORDER>(A, ncu, lds, st);
-}
-
-// ntg_batch_envelope_sos (envelope_sos.hpp): the instances and the launch shapes of ntg_launch_envelope.
-// hipErrorInvalidValue: the tables exceed the LDS.
-template <int KM>
-static hipError_t launch_envelope_sos(const SosArgs &A, int ncu, size_t lds, hipStream_t st)
-{
-	if (A.pp) {
-		const int groups = (A.batch + NTG_ENVELOPE_NT / 64 - 1) / (NTG_ENVELOPE_NT / 64);
-		hipLaunchKernelGGL((envelope_sos_pp_kernel<NTG_ENVELOPE_NT, KM>), dim3(std::min(groups, 8 * ncu)), dim3(NTG_ENVELOPE_NT), lds, st, A);
-	} else {
-		const int grid = std::max(1, std::min((A.batch + 3) / 4, 8 * ncu));
-		hipLaunchKernelGGL((envelope_sos_shared_kernel<NTG_ENVELOPE_NT, KM>), dim3(grid), dim3(NTG_ENVELOPE_NT), lds, st, A);
-	}
-	return hipGetLastError();
-}
-hipError_t ntg_launch_envelope_sos(const SosArgs &A, int ncu, hipStream_t st)
-{
-	const size_t lds = ntg_envelope_sos_lds(A);
-	if (lds > NTG_ENVELOPE_LDS_MAX || A.kmax > NTG_MAX_ORDER || A.nrow > NTG_SOS_MAXROWS) return hipErrorInvalidValue;   // (ntg_batch_envelope_sos refuses such a plan before it gets here)
-	if (A.batch <= 0) return hipSuccess;
-	return A.kmax <= 6 ? launch_envelope_sos<6>(A, ncu, lds, st) : launch_envelope_sos<NTG_MAX_ORDER>(A, ncu, lds, st);
-}
-
-// ntg_batch_extrema (extrema.hpp): the instances of ntg_launch_envelope_sos; four problems per workgroup pass, one per wave.
-// hipErrorInvalidValue: the tables and work lists exceed the LDS.
-template <int KM>
-static hipError_t launch_extrema(const ExtArgs &A, int ncu, size_t lds, hipStream_t st)
-{
-	constexpr int NW = NTG_EXTREMA_NT / 64;
-	const int groups = (A.s.batch + NW - 1) / NW;
-	auto kfn = A.s.pp ? extrema_pp_kernel<NTG_EXTREMA_NT, KM> : extrema_shared_kernel<NTG_EXTREMA_NT, KM>;
+	const int groups = (A.g.batch + nt / 64 - 1) / (nt / 64);
+	auto kfn = A.g.pp ? kpp : ksh;
 	if (lds > 64 * 1024) {
 		const hipError_t e = hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 		if (e != hipSuccess) return e;
 	}
-	// shared grids: persistent workgroups, each builds its weights once, so each should stream several problems; no more than fill the device
-	const int grid = A.s.pp ? std::min(groups, 8 * ncu) : std::max(1, std::min((groups + 3) / 4, 8 * ncu));
-	hipLaunchKernelGGL(kfn, dim3(grid), dim3(NTG_EXTREMA_NT), lds, st, A);
+	const int grid = A.g.pp ? std::min(groups, 8 * ncu) : std::max(1, std::min((units + 3) / 4, 8 * ncu));
+	hipLaunchKernelGGL(kfn, dim3(grid), dim3(nt), lds, st, A);
 	return hipGetLastError();
 }
+#define NTG_CERT_LAUNCH(name, NT, units)                                                                                    \
+	(A.g.kmax <= 6 ? launch_cert(name##_pp_kernel<NT, 6>, name##_shared_kernel<NT, 6>, A, NT, units, ncu, lds, st) \
+	               : launch_cert(name##_pp_kernel<NT, NTG_MAX_ORDER>, name##_shared_kernel<NT, NTG_MAX_ORDER>, A, NT, units, ncu, lds, st))
+
+// hipErrorInvalidValue: the tables exceed the LDS (the entry points refuse such a plan before it gets here).  On shared grids a workgroup of
+// the two envelope calls takes one problem at a time ...
+hipError_t ntg_launch_envelope(const EnvArgs &A, int ncu, hipStream_t st)
+{
+	const size_t lds = ntg_envelope_lds(A);
+	if (lds > NTG_ENVELOPE_LDS_MAX || A.g.kmax > NTG_MAX_ORDER) return hipErrorInvalidValue;
+	if (A.g.batch <= 0) return hipSuccess;
+	return NTG_CERT_LAUNCH(envelope, NTG_ENVELOPE_NT, A.g.batch);
+}
+hipError_t ntg_launch_envelope_sos(const SosArgs &A, int ncu, hipStream_t st)
+{
+	const size_t lds = ntg_envelope_sos_lds(A);
+	if (lds > NTG_ENVELOPE_LDS_MAX || A.g.kmax > NTG_MAX_ORDER || A.sos.nrow > NTG_SOS_MAXROWS) return hipErrorInvalidValue;
+	if (A.g.batch <= 0) return hipSuccess;
+	return NTG_CERT_LAUNCH(envelope_sos, NTG_ENVELOPE_NT, A.g.batch);
+}
+// ... and one of ntg_batch_extrema a pass of four problems, one per wave
 hipError_t ntg_launch_extrema(const ExtArgs &A, int ncu, hipStream_t st)
 {
 	const size_t lds = ntg_extrema_lds(A);
-	if (lds > NTG_EXTREMA_LDS_MAX || A.s.kmax > NTG_MAX_ORDER || A.s.nrow > NTG_SOS_MAXROWS) return hipErrorInvalidValue;   // (ntg_batch_extrema refuses such a plan before it gets here)
-	if (A.s.batch <= 0) return hipSuccess;
-	return A.s.kmax <= 6 ? launch_extrema<6>(A, ncu, lds, st) : launch_extrema<NTG_MAX_ORDER>(A, ncu, lds, st);
+	if (lds > NTG_EXTREMA_LDS_MAX || A.g.kmax > NTG_MAX_ORDER || A.sos.nrow > NTG_SOS_MAXROWS) return hipErrorInvalidValue;
+	if (A.g.batch <= 0) return hipSuccess;
+	return NTG_CERT_LAUNCH(extrema, NTG_EXTREMA_NT, (A.g.batch + NTG_EXTREMA_NT / 64 - 1) / (NTG_EXTREMA_NT / 64));
 }
+#undef NTG_CERT_LAUNCH
 
 // Flat flag -> state and input of the kinematic car, the map of examples/kincar.c:68-92 (kincar_flat_reverse), for every car
 // of every problem at every time of an ntg_batch_interp result: z [n][nz] with the flag of car c at entries 6 c .. 6 c + 5

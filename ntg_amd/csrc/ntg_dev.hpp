@@ -214,85 +214,102 @@ struct KktArgs {
 static inline size_t ntg_kkt_lds(const NtgDims &D) { return (size_t)2 * ((D.nC + 1) & ~1) * 8 + (size_t)D.nclass * D.P * 4; }
 #define NTG_KKT_LDS_MAX (160 * 1024 - 256)
 
-// envelope kernels (envelope.hpp): certified bounds of every flag entry and every linear trajectory row on the pieces of the knot intervals.
-// c[cl]: a basis class, its extraction weights [l][k][k] at eoff and interval lengths [l] at hoff in the LDS table of ne doubles.  knots[cl]:
-// the class's break sequence (shared grids); knots[0] = [batch][l + 1] on per-problem grids (pp = 1, one class).  Outputs as documented at
-// ntg_batch_envelope, any may be null; ltc [nltc][nz]; lower / upper [batch][nbounds], the linear trajectory rows' slots start at slot0.
+// The time certificates (envelope.hpp, envelope_sos.hpp, extrema.hpp) enclose trajectory rows by their Bezier polygons on the knot intervals.
+// Their kernel arguments are composed of three parts:
+//   CertBase  the batch and its basis classes.  c[cl]: a class, its extraction weights [l][k][k] at eoff and interval lengths [l] at hoff in
+//             the LDS table of ne doubles.  knots[cl]: the class's break sequence (shared grids); knots[0] = [batch][l + 1] on per-problem
+//             grids (pp = 1, one class).  lower / upper [batch][nbounds] (null unless a violation is asked for).
+//   CertLin   the linear trajectory rows: ltc [nltc][nz], read through the outputs' cls / d / iC / iz; their bound slots start at slot0.
+//   CertSos   the nonlinear trajectory rows declared as sums of squares of shifted flag entries; their bound slots start at slot0.  row[j]: nt
+//             terms, the basis class cl of the entries it names, the degree D of its polygon, flag = 1: certified (0: no statement, nothing
+//             else of the row is read).  term[j][t]: coefficient offset iC of the output, its derivative order r, the shift's constant s0 and
+//             the index poff into the problem's parameter row (np doubles at prm + b pp_prm) or -1.  w: the product tables W_d[i][j] =
+//             C(d,i) C(d,j) / C(2d,i+j), d = 0 .. NTG_MAX_ORDER - 1, the upper triangles (i <= j) row by row, d ascending; the kernels
+//             unfold them into LDS.
 #define NTG_ENVELOPE_NT 256
 #define NTG_ENVELOPE_LDS_MAX (64 * 1024)
-struct EnvClass { int k, m, l, eoff, hoff; };
-struct EnvArgs {
-	int nout, nz, nC, nclass, batch, nsub, npc, nltc, nbounds, slot0, pp, ne, lmax, kmax;
-	int cls[NTG_MAX_OUT], d[NTG_MAX_OUT], iC[NTG_MAX_OUT], iz[NTG_MAX_OUT];
-	EnvClass c[NTG_MAX_OUT];
-	const double *knots[NTG_MAX_OUT];
-	const double *x, *ltc, *lower, *upper;
-	double *lo, *hi, *row_lo, *row_hi, *viol; int *where;
-};
-// dynamic LDS: the tables, one coefficient row and one break sequence -- of the workgroup (shared grids) or of each of its waves
-static inline size_t ntg_envelope_lds(const EnvArgs &A)
-{
-	return (size_t)(A.pp ? NTG_ENVELOPE_NT / 64 : 1) * (size_t)(A.ne + A.nC + A.lmax + 1) * 8;
-}
-
-// sum-of-squares row envelope (envelope_sos.hpp): certified bounds of the nonlinear trajectory rows declared as sums of squares of shifted
-// flag entries.  c, knots, ne, lmax, kmax as in EnvArgs.  row[j]: nt terms, the basis class cl of the entries it names, the degree D of its
-// polygon, flag = 1: certified (0: no statement, nothing else of the row is read).  term[j][t]: coefficient offset iC of the output, its
-// derivative order r, the shift's constant s0 and the index poff into the problem's parameter row (np doubles at prm + b pp_prm) or -1.
-// w: the product tables W_d[i][j] = C(d,i) C(d,j) / C(2d,i+j), d = 0 .. NTG_MAX_ORDER - 1, the upper triangles (i <= j) row by row, d
-// ascending; the kernels unfold them into LDS.  lower / upper [batch][nbounds], the rows' slots start at slot0.
 #define NTG_SOS_MAXROWS 8
 #define NTG_SOS_WTRI (NTG_MAX_ORDER * (NTG_MAX_ORDER + 1) * (NTG_MAX_ORDER + 2) / 6)     // doubles of the triangles
 #define NTG_SOS_WFULL (NTG_MAX_ORDER * (NTG_MAX_ORDER + 1) * (2 * NTG_MAX_ORDER + 1) / 6) // doubles of the unfolded tables
-struct SosRow { int nt, cl, D, flag; };
-struct SosTerm { int iC, r, poff, pad; double s0; };
-struct SosArgs {
-	int nC, nclass, batch, nsub, npc, nrow, nbounds, slot0, pp, ne, lmax, kmax, np, pad;
-	long long pp_prm;
+struct EnvClass { int k, m, l, eoff, hoff; };
+struct CertBase {
+	int nC, nclass, batch, pp, ne, lmax, kmax, nbounds;
 	EnvClass c[NTG_MAX_OUT];
 	const double *knots[NTG_MAX_OUT];
-	const double *x, *prm, *lower, *upper;
-	double *q_lo, *q_hi, *viol; int *where;
+	const double *x, *lower, *upper;
+};
+struct CertLin {
+	int nout, nz, nltc, slot0;
+	int cls[NTG_MAX_OUT], d[NTG_MAX_OUT], iC[NTG_MAX_OUT], iz[NTG_MAX_OUT];
+	const double *ltc;
+};
+struct SosRow { int nt, cl, D, flag; };
+struct SosTerm { int iC, r, poff, pad; double s0; };
+struct CertSos {
+	int nrow, slot0, np, pad;
+	long long pp_prm;
+	const double *prm;
 	SosRow row[NTG_SOS_MAXROWS];
 	SosTerm term[NTG_SOS_MAXROWS][NTG_SOS_MAXTERMS];
 	double w[NTG_SOS_WTRI];
 };
-static_assert(sizeof(SosArgs) <= 4096, "SosArgs travels as a kernel argument");
-// table of degree d: offset of its triangle in SosArgs::w, of its unfolded [d + 1][d + 1] form in LDS
+// table of degree d: offset of its triangle in CertSos::w, of its unfolded [d + 1][d + 1] form in LDS
 static inline __host__ __device__ int ntg_sos_wtri(int d) { return d * (d + 1) * (d + 2) / 6; }
 static inline __host__ __device__ int ntg_sos_wfull(int d) { return d * (d + 1) * (2 * d + 1) / 6; }
+
+// ntg_batch_envelope (envelope.hpp): every flag entry and every linear trajectory row on the npc = lmax << nsub pieces of the knot intervals.
+// Outputs as documented at ntg_batch_envelope, any may be null.
+struct EnvArgs {
+	CertBase g;
+	CertLin lin;
+	int nsub, npc;
+	double *lo, *hi, *row_lo, *row_hi, *viol; int *where;
+};
+static_assert(sizeof(EnvArgs) <= 4096, "EnvArgs travels as a kernel argument");
+// dynamic LDS: the tables, one coefficient row and one break sequence -- of the workgroup (shared grids) or of each of its waves
+static inline size_t ntg_envelope_lds(const EnvArgs &A)
+{
+	return (size_t)(A.g.pp ? NTG_ENVELOPE_NT / 64 : 1) * (size_t)(A.g.ne + A.g.nC + A.g.lmax + 1) * 8;
+}
+
+// ntg_batch_envelope_sos (envelope_sos.hpp): the sum-of-squares rows on the same pieces.  Outputs as documented there, any may be null.
+struct SosArgs {
+	CertBase g;
+	CertSos sos;
+	int nsub, npc;
+	double *q_lo, *q_hi, *viol; int *where;
+};
+static_assert(sizeof(SosArgs) <= 4096, "SosArgs travels as a kernel argument");
 // dynamic LDS: the unfolded product tables, then the extraction tables, one coefficient row, one parameter row and one break sequence -- of
 // the workgroup (shared grids) or of each of its waves
 static inline size_t ntg_envelope_sos_lds(const SosArgs &A)
 {
-	return ((size_t)NTG_SOS_WFULL + (size_t)(A.pp ? NTG_ENVELOPE_NT / 64 : 1) * (size_t)(A.ne + A.nC + A.np + A.lmax + 1)) * 8;
+	return ((size_t)NTG_SOS_WFULL + (size_t)(A.g.pp ? NTG_ENVELOPE_NT / 64 : 1) * (size_t)(A.g.ne + A.g.nC + A.sos.np + A.g.lmax + 1)) * 8;
 }
 
-// row extrema by bisection (extrema.hpp): the global minimum and maximum of every certifiable trajectory row over the horizon, each enclosed
-// to tol, with the time where the attained value sits.  Rows: the nltc linear trajectory rows (ltc [nltc][nz], read as envelope.hpp reads
-// them through cls / d / iC / iz), then the s.nrow nonlinear ones (s.row / s.term / s.w, as envelope_sos.hpp reads them).  s carries what the
-// two envelope calls share: c, knots, ne, lmax, kmax, nC, nclass, batch, pp, np, prm, pp_prm, x, lower, upper, nbounds; s.slot0 is the first
-// nonlinear row's bound slot, slot_lin the first linear row's; s.nsub, s.npc and s's outputs are not used.  koff[cl]: the breaks of class cl
-// in the LDS table of nk doubles (the times of the piece ends need them after the weights are built).
+// ntg_batch_extrema (extrema.hpp): the global minimum and maximum of every certifiable trajectory row over the horizon, each enclosed to tol,
+// with the time where the attained value sits.  Rows: the lin.nltc linear trajectory rows, then the sos.nrow nonlinear ones.  koff[cl]: the
+// breaks of class cl in the LDS table of nk doubles (the times of the piece ends need them after the weights are built).
 // Outputs as documented at ntg_batch_extrema, any may be null.
 #define NTG_EXTREMA_NT 256
 struct ExtArgs {
-	SosArgs s;
-	int nout, nz, nltc, slot_lin, max_depth, sides, nk, pad;
+	CertBase g;
+	CertLin lin;
+	CertSos sos;
+	int max_depth, sides, nk, pad;
 	double tol;
-	int cls[NTG_MAX_OUT], d[NTG_MAX_OUT], iC[NTG_MAX_OUT], iz[NTG_MAX_OUT], koff[NTG_MAX_OUT];
-	const double *ltc;
+	int koff[NTG_MAX_OUT];
 	double *ext, *when, *viol; int *status, *npieces, *where;
 };
 static_assert(sizeof(ExtArgs) <= 4096, "ExtArgs travels as a kernel argument");
 // doubles of a work-list element: the row polygon's points; the instance (KM = 6 or NTG_MAX_ORDER) follows from the plan's largest order
-static inline int ntg_extrema_kd(const ExtArgs &A) { return A.s.kmax <= 6 ? 11 : 2 * NTG_MAX_ORDER - 1; }
+static inline int ntg_extrema_kd(const ExtArgs &A) { return A.g.kmax <= 6 ? 11 : 2 * NTG_MAX_ORDER - 1; }
 // dynamic LDS: the unfolded product tables; the extraction tables and the breaks of every class; per wave one coefficient row, one parameter
 // row, the work list (NTG_EXTREMA_CAP polygons) and its keys.  Per-problem grids: every wave has extraction tables and breaks of its own.
 static inline size_t ntg_extrema_lds(const ExtArgs &A)
 {
-	const size_t wave = (size_t)A.s.nC + A.s.np + (size_t)NTG_EXTREMA_CAP * (ntg_extrema_kd(A) + 1), tabs = (size_t)A.s.ne + A.nk;
-	return ((size_t)NTG_SOS_WFULL + (A.s.pp ? 0 : tabs) + (size_t)(NTG_EXTREMA_NT / 64) * (wave + (A.s.pp ? tabs : 0))) * 8;
+	const size_t wave = (size_t)A.g.nC + A.sos.np + (size_t)NTG_EXTREMA_CAP * (ntg_extrema_kd(A) + 1), tabs = (size_t)A.g.ne + A.nk;
+	return ((size_t)NTG_SOS_WFULL + (A.g.pp ? 0 : tabs) + (size_t)(NTG_EXTREMA_NT / 64) * (wave + (A.g.pp ? tabs : 0))) * 8;
 }
 // ... and what a workgroup may ask for: 160 KiB less the static part (the row, term and class tables)
 #define NTG_EXTREMA_LDS_MAX (160 * 1024 - 2048)

@@ -1,0 +1,273 @@
+// plan_cert.cpp -- the time certificates behind include/ntg_amd.h: ntg_batch_envelope, ntg_batch_envelope_sos, ntg_batch_extrema and the
+// queries ntg_plan_sos_rows and ntg_plan_extrema_rows.  What they share comes first: the refusals (each call tests them between its own
+// argument checks, in its own order), which rows of a plan are certified -- a linear trajectory row whose outputs share a basis class, from
+// the host mirror of ltc; a nonlinear row by the family's sum-of-squares declaration, NtgFamily::sos, against the plan's iz / cls -- and the
+// three parts of the kernels' arguments (CertBase, CertLin, CertSos: ntg_dev.hpp).  An entry point then reads: its own argument checks,
+// the setup, its own fields, the launch.  The arithmetic is in envelope.hpp, envelope_sos.hpp and extrema.hpp.  No family callback runs, so
+// the calls serve every built-in family and every loaded module.  They allocate nothing.
+#include "plan_priv.hpp"
+#include "family_module.hpp"
+
+namespace {
+// ---------------- refusals ----------------
+// an empty batch (1: the call returns 0) and the coefficients
+int cert_batch(int batch, const double *d_x)
+{
+	if (batch <= 0) return 1;
+	return d_x ? 0 : fail(NTG_E_BADARG, "null argument");
+}
+int cert_bounds(bool want_v, const double *d_lower, const double *d_upper)
+{
+	return want_v && (!d_lower || !d_upper) ? fail(NTG_E_BADARG, "d_viol / d_where need the bounds d_lower and d_upper") : 0;
+}
+int cert_host(const ntg_plan *p)
+{
+	return p->D.family == NTG_FAM_HOST ? fail(NTG_E_UNSUPPORTED, "host-callback plans are not taken by the batch calls") : 0;
+}
+// per-problem grids and (with_prm) per-problem parameters made for another batch size
+int cert_batch_size(const ntg_plan *p, int batch, bool with_prm)
+{
+	if (p->grid_batch && batch != p->grid_batch) return fail(NTG_E_BADARG, "the plan carries per-problem grids for another batch size");
+	if (with_prm && p->prm_batch && batch != p->prm_batch)
+		return fail(NTG_E_BADARG, "the plan carries per-problem parameters for " + std::to_string(p->prm_batch) + " problems, not " + std::to_string(batch));
+	return 0;
+}
+int cert_nsub(int nsub)
+{
+	return nsub < 0 || nsub > NTG_ENVELOPE_MAX_NSUB ? fail(NTG_E_BADARG, "nsub must lie in 0 .. " + std::to_string(NTG_ENVELOPE_MAX_NSUB)) : 0;
+}
+
+// ---------------- rows ----------------
+// linear trajectory row i: flag 1 when the outputs it names belong to one basis class (a row of zeros: class 0); otherwise the first output
+// named and the first one of another class
+struct LinRowFlag { int flag, first, other; };
+LinRowFlag lin_row_flag(const ntg_plan *p, int i)
+{
+	const NtgDims &D = p->D;
+	const double *row = p->h_linrows.data() + (size_t)(D.nlic + i) * D.nz;
+	int first = -1;
+	for (int o = 0; o < D.nout; o++)
+		for (int r = 0; r < D.d[o]; r++) {
+			if (row[D.iz[o] + r] == 0.0) continue;
+			if (first < 0) first = o;
+			else if (D.cls[o] != D.cls[first]) return {0, first, o};
+		}
+	return {1, first, -1};
+}
+
+// Row j of the plan's nonlinear trajectory rows in the kernels' form.  flag 0: no statement -- the family does not declare the row (or names
+// a flag entry the plan does not have), or the entries it names belong to different basis classes; cl is then the class of the first entry
+// named, or of output 0.  f: the plan's family (null: declares nothing)
+struct SosPlanRow { SosRow row; SosTerm term[NTG_SOS_MAXTERMS]; bool need_prm; };
+SosPlanRow sos_plan_row(const ntg_plan *p, const NtgFamily *f, int j)
+{
+	const NtgDims &D = p->D;
+	SosPlanRow R{};
+	R.row.cl = D.cls[0];
+	NtgSosTerm decl[NTG_SOS_MAXTERMS] = {};
+	const int nt = f && f->sos ? f->sos(j, D.nout, decl) : 0;
+	if (nt <= 0 || nt > NTG_SOS_MAXTERMS) return R;
+	bool ok = true;
+	for (int t = 0; t < nt; t++) {
+		int o = -1;
+		for (int q = 0; q < D.nout; q++) if (decl[t].v >= D.iz[q] && decl[t].v < D.iz[q] + D.d[q]) o = q;
+		if (o < 0 || decl[t].pidx >= f->nparam_row) return SosPlanRow{{0, D.cls[0], 0, 0}, {}, false};
+		const int r = decl[t].v - D.iz[o], k = D.order[o];
+		if (t == 0) R.row.cl = D.cls[o];
+		else if (D.cls[o] != R.row.cl) ok = false;
+		R.row.D = std::max(R.row.D, 2 * std::max(k - 1 - r, 0));
+		R.term[t] = SosTerm{D.iC[o], r, decl[t].pidx >= 0 ? j * f->nparam_row + decl[t].pidx : -1, 0, decl[t].shift};
+		R.need_prm = R.need_prm || decl[t].pidx >= 0;
+	}
+	if (!ok) { R.row.nt = 0; R.row.D = 0; R.need_prm = false; return R; }
+	R.row.nt = nt; R.row.flag = 1;
+	return R;
+}
+
+// C(n, r), exact: n <= 2 (NTG_MAX_ORDER - 1)
+unsigned long long binom(int n, int r)
+{
+	unsigned long long c = 1;
+	for (int i = 1; i <= r; i++) c = c * (unsigned long long)(n - r + i) / (unsigned long long)i;
+	return c;
+}
+
+// ---------------- the parts of the kernels' arguments ----------------
+// the batch and the class tables; koff / nk (extrema): where every class's breaks go
+void cert_base(const ntg_plan *p, int batch, const double *d_x, const double *d_lower, const double *d_upper, CertBase &G, int *koff = nullptr, int *nk = nullptr)
+{
+	const NtgDims &D = p->D;
+	G.nC = D.nC; G.nclass = D.nclass; G.batch = batch; G.nbounds = D.nbounds;
+	G.pp = p->grid_batch ? 1 : 0;
+	for (int c = 0; c < D.nclass; c++) {
+		EnvClass &C = G.c[c];
+		C.k = D.cls_k[c]; C.m = D.cls_m[c]; C.l = D.cls_l[c];
+		C.eoff = G.ne; G.ne += C.l * C.k * C.k;
+		C.hoff = G.ne; G.ne += C.l;
+		if (koff) { koff[c] = *nk; *nk += C.l + 1; }
+		G.lmax = std::max(G.lmax, C.l); G.kmax = std::max(G.kmax, C.k);
+		G.knots[c] = G.pp ? p->d_grid_knots : p->d_knots[c];
+	}
+	G.x = d_x; G.lower = d_lower; G.upper = d_upper;
+}
+void cert_lin(const ntg_plan *p, CertLin &L)
+{
+	const NtgDims &D = p->D;
+	L.nout = D.nout; L.nz = D.nz; L.nltc = D.nltc; L.slot0 = D.nlic; L.ltc = p->d_ltc;
+	for (int o = 0; o < D.nout; o++) { L.cls[o] = D.cls[o]; L.d[o] = D.d[o]; L.iC[o] = D.iC[o]; L.iz[o] = D.iz[o]; }
+}
+// the rows, terms and product tables; how many rows are certified, the first that is not (or -1), and the parameter row where a term reads it
+struct SosCount { int ncert, first0; bool need_prm; };
+SosCount cert_sos(const ntg_plan *p, const NtgFamily *f, CertSos &S)
+{
+	const NtgDims &D = p->D;
+	SosCount n{0, -1, false};
+	for (int j = 0; j < D.nnltc; j++) {
+		const SosPlanRow R = sos_plan_row(p, f, j);
+		n.ncert += R.row.flag;
+		if (!R.row.flag && n.first0 < 0) n.first0 = j;
+		n.need_prm = n.need_prm || R.need_prm;
+		if (j < NTG_SOS_MAXROWS) { S.row[j] = R.row; for (int t = 0; t < NTG_SOS_MAXTERMS; t++) S.term[j][t] = R.term[t]; }
+	}
+	S.nrow = D.nnltc; S.slot0 = D.nlic + D.nltc + D.nlfc + D.nnlic;
+	S.np = n.need_prm ? p->prm_n : 0;
+	S.prm = n.need_prm ? p->T.prm : nullptr; S.pp_prm = n.need_prm ? p->T.pp_prm : 0;
+	for (int d = 0; d < NTG_MAX_ORDER; d++) {   // W_d[i][j] = C(d,i) C(d,j) / C(2d,i+j), i <= j: two exact integers, one rounding
+		double *q = S.w + ntg_sos_wtri(d);
+		for (int i = 0; i <= d; i++)
+			for (int j = i; j <= d; j++) *q++ = (double)(binom(d, i) * binom(d, j)) / (double)binom(2 * d, i + j);
+	}
+	return n;
+}
+// what both calls on sum-of-squares rows refuse about them once they know that some row is certified: more rows than the kernels' tables
+// hold, and (after the call's own partial-certificate refusal) parameters that were never set
+int cert_sos_fits(const ntg_plan *p)
+{
+	return p->D.nnltc > NTG_SOS_MAXROWS ? fail(NTG_E_UNSUPPORTED, "more than " + std::to_string(NTG_SOS_MAXROWS) + " nonlinear trajectory rows") : 0;
+}
+int cert_sos_prm(const ntg_plan *p, const SosCount &n)
+{
+	return n.need_prm && !p->prm_batch ? fail(NTG_E_BADARG, "the certified rows read per-problem parameters: set them with ntg_plan_set_params") : 0;
+}
+}   // namespace
+
+extern "C" int ntg_plan_sos_rows(const ntg_plan *p, int *flags)
+{
+	if (!p || !flags) return fail(NTG_E_BADARG, p ? "null argument" : "null plan");
+	const NtgFamily *f = ntg_family(p->D.family);
+	for (int j = 0; j < p->D.nnltc; j++) flags[j] = sos_plan_row(p, f, j).row.flag;
+	return 0;
+}
+
+extern "C" int ntg_plan_extrema_rows(const ntg_plan *p, int *flags)
+{
+	if (!p || !flags) return fail(NTG_E_BADARG, p ? "null argument" : "null plan");
+	for (int i = 0; i < p->D.nltc; i++) flags[i] = lin_row_flag(p, i).flag;
+	return ntg_plan_sos_rows(p, flags + p->D.nltc);
+}
+
+extern "C" int ntg_batch_envelope(const ntg_plan *p, int batch, const double *d_x, int nsub, const double *d_lower, const double *d_upper,
+                                  double *d_lo, double *d_hi, double *d_row_lo, double *d_row_hi, double *d_viol, int *d_where, void *stream)
+{
+	if (!p) return fail(NTG_E_BADARG, "null plan");
+	if (int rc = cert_batch(batch, d_x)) return rc > 0 ? 0 : rc;
+	if (int rc = cert_nsub(nsub)) return rc;
+	const bool want_v = d_viol || d_where, want_r = d_row_lo || d_row_hi || want_v;
+	if (!d_lo && !d_hi && !want_r) return fail(NTG_E_BADARG, "no output asked for: pass d_lo, d_hi, d_row_lo, d_row_hi, d_viol or d_where");
+	if (int rc = cert_bounds(want_v, d_lower, d_upper)) return rc;
+	if (want_r && p->D.nltc == 0) return fail(NTG_E_BADARG, "the plan has no linear trajectory rows (nltc == 0)");
+	if (int rc = cert_batch_size(p, batch, false)) return rc;
+	if (int rc = cert_host(p)) return rc;
+	for (int i = 0; want_r && i < p->D.nltc; i++) {   // every row's polygon lives on the pieces of one basis class
+		const LinRowFlag R = lin_row_flag(p, i);
+		if (!R.flag)
+			return fail(NTG_E_UNSUPPORTED, "linear trajectory row " + std::to_string(i) + " names outputs " + std::to_string(R.first) + " and " + std::to_string(R.other) +
+			                                   " of different basis classes: its envelope has no common pieces (the entry envelope d_lo / d_hi is still served)");
+	}
+	EnvArgs A{};
+	cert_base(p, batch, d_x, d_lower, d_upper, A.g);
+	cert_lin(p, A.lin);
+	A.nsub = nsub; A.npc = A.g.lmax << nsub;
+	if (ntg_envelope_lds(A) > NTG_ENVELOPE_LDS_MAX) return fail(NTG_E_UNSUPPORTED, "the extraction tables of this plan exceed 64 KiB of LDS");
+	A.lo = d_lo; A.hi = d_hi; A.row_lo = d_row_lo; A.row_hi = d_row_hi; A.viol = d_viol; A.where = d_where;
+	HIPCHK(hipSetDevice(p->device));
+	HIPCHK(ntg_launch_envelope(A, plan_ncu(p), (hipStream_t)stream));
+	return 0;
+}
+
+extern "C" int ntg_batch_envelope_sos(const ntg_plan *p, int batch, const double *d_x, int nsub, const double *d_lower, const double *d_upper,
+                                      double *d_q_lo, double *d_q_hi, double *d_viol, int *d_where, void *stream)
+{
+	if (!p) return fail(NTG_E_BADARG, "null plan");
+	if (int rc = cert_nsub(nsub)) return rc;
+	if (int rc = cert_batch(batch, d_x)) return rc > 0 ? 0 : rc;
+	const bool want_v = d_viol || d_where;
+	if (!d_q_lo && !d_q_hi && !want_v) return fail(NTG_E_BADARG, "no output asked for: pass d_q_lo, d_q_hi, d_viol or d_where");
+	if (int rc = cert_bounds(want_v, d_lower, d_upper)) return rc;
+	if (int rc = cert_host(p)) return rc;
+	if (p->D.nnltc == 0) return fail(NTG_E_BADARG, "the plan has no nonlinear trajectory rows (nnltc == 0)");
+	if (int rc = cert_batch_size(p, batch, true)) return rc;
+	const NtgFamily *f = ntg_family(p->D.family);
+	SosArgs A{};
+	const SosCount n = cert_sos(p, f, A.sos);
+	if (n.ncert == 0)
+		return fail(NTG_E_UNSUPPORTED, std::string("no nonlinear trajectory row of this plan is certified: the family ") + (f ? f->name : "?") +
+		                                   " declares none of them as a sum of squares (or the entries they name have no common pieces)");
+	if (int rc = cert_sos_fits(p)) return rc;
+	if (want_v && n.first0 >= 0)
+		return fail(NTG_E_UNSUPPORTED, "nonlinear trajectory row " + std::to_string(n.first0) + " is not certified (ntg_plan_sos_rows): d_viol / d_where would be a partial "
+		                                   "certificate; d_q_lo / d_q_hi are still served");
+	if (int rc = cert_sos_prm(p, n)) return rc;
+	cert_base(p, batch, d_x, d_lower, d_upper, A.g);
+	A.nsub = nsub; A.npc = A.g.lmax << nsub;
+	if (ntg_envelope_sos_lds(A) > NTG_ENVELOPE_LDS_MAX) return fail(NTG_E_UNSUPPORTED, "the extraction and product tables of this plan exceed 64 KiB of LDS");
+	A.q_lo = d_q_lo; A.q_hi = d_q_hi; A.viol = d_viol; A.where = d_where;
+	HIPCHK(hipSetDevice(p->device));
+	HIPCHK(ntg_launch_envelope_sos(A, plan_ncu(p), (hipStream_t)stream));
+	return 0;
+}
+
+extern "C" int ntg_batch_extrema(const ntg_plan *p, int batch, const double *d_x, double tol, int max_depth, int sides, const double *d_lower, const double *d_upper,
+                                 double *d_ext, double *d_when, int *d_status, int *d_npieces, double *d_viol, int *d_where, void *stream)
+{
+	if (!p) return fail(NTG_E_BADARG, "null plan");
+	if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(NTG_E_BADARG, "tol must be finite and >= 0");
+	if (max_depth < 0 || max_depth > NTG_EXTREMA_MAX_DEPTH) return fail(NTG_E_BADARG, "max_depth must lie in 0 .. " + std::to_string(NTG_EXTREMA_MAX_DEPTH));
+	if (sides < 1 || sides > 3) return fail(NTG_E_BADARG, "sides must be 1 (minimum), 2 (maximum) or 3 (both)");
+	if (int rc = cert_batch(batch, d_x)) return rc > 0 ? 0 : rc;
+	const bool want_v = d_viol || d_where;
+	if (!d_ext && !d_when && !d_status && !d_npieces && !want_v)
+		return fail(NTG_E_BADARG, "no output asked for: pass d_ext, d_when, d_status, d_npieces, d_viol or d_where");
+	if (int rc = cert_bounds(want_v, d_lower, d_upper)) return rc;
+	if (int rc = cert_host(p)) return rc;
+	const NtgDims &D = p->D;
+	if (D.nltc + D.nnltc == 0) return fail(NTG_E_BADARG, "the plan has no trajectory rows (nltc + nnltc == 0)");
+	if (int rc = cert_batch_size(p, batch, true)) return rc;
+	const NtgFamily *f = ntg_family(D.family);
+	ExtArgs A{};
+	SosCount n = cert_sos(p, f, A.sos);
+	int first_lin = -1;   // the linear rows come first
+	for (int i = 0; i < D.nltc; i++) {
+		const int fl = lin_row_flag(p, i).flag;
+		n.ncert += fl;
+		if (!fl && first_lin < 0) first_lin = i;
+	}
+	n.first0 = first_lin >= 0 ? first_lin : n.first0 >= 0 ? D.nltc + n.first0 : -1;
+	if (n.ncert == 0)
+		return fail(NTG_E_UNSUPPORTED, std::string("no trajectory row of this plan is certified (ntg_plan_extrema_rows): the family ") + (f ? f->name : "?") +
+		                                   " declares no nonlinear row as a sum of squares, and no linear row names outputs of one basis class");
+	if (int rc = cert_sos_fits(p)) return rc;
+	if (want_v && n.first0 >= 0)
+		return fail(NTG_E_UNSUPPORTED, "trajectory row " + std::to_string(n.first0) + " is not certified (ntg_plan_extrema_rows): d_viol / d_where would be a partial "
+		                                   "certificate; the other outputs are still served");
+	if (int rc = cert_sos_prm(p, n)) return rc;
+	cert_base(p, batch, d_x, d_lower, d_upper, A.g, A.koff, &A.nk);
+	cert_lin(p, A.lin);
+	A.max_depth = max_depth; A.sides = sides; A.tol = tol;
+	if (A.g.kmax > NTG_MAX_ORDER || ntg_extrema_lds(A) > NTG_EXTREMA_LDS_MAX)
+		return fail(NTG_E_UNSUPPORTED, "the tables and work lists of this plan exceed " + std::to_string(NTG_EXTREMA_LDS_MAX / 1024) + " KiB of LDS");
+	A.ext = d_ext; A.when = d_when; A.status = d_status; A.npieces = d_npieces; A.viol = d_viol; A.where = d_where;
+	HIPCHK(hipSetDevice(p->device));
+	HIPCHK(ntg_launch_extrema(A, plan_ncu(p), (hipStream_t)stream));
+	return 0;
+}

@@ -9,9 +9,8 @@
 //   plan_kkt.cpp    ntg_batch_kkt: first-order optimality residuals of a batch
 //   plan_cost.cpp   ntg_batch_cost: the running cost of a batch at arbitrary times under a quadrature
 //   plan_verify.cpp ntg_batch_verify: a family's analytic derivatives against central differences at the breakpoints
-//   plan_envelope.cpp ntg_batch_envelope: certified bounds of the flag entries and linear trajectory rows over the whole horizon
-//   plan_envelope_sos.cpp ntg_batch_envelope_sos: the same for the nonlinear trajectory rows a family declares as sums of squares
-//   plan_extrema.cpp ntg_batch_extrema: the minimum and maximum of every certifiable trajectory row over the horizon, by bisection
+//   plan_cert.cpp   the time certificates ntg_batch_envelope, ntg_batch_envelope_sos and ntg_batch_extrema: bounds of the flag entries and
+//                   of the trajectory rows that hold over the whole horizon; their common refusals, row tables and kernel arguments
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -142,13 +141,6 @@ int plan_ncu(const ntg_plan *p);   // compute units of the plan's device (plan.c
 // per-problem family parameters (plan_grids.cpp): doubles per problem the plan's family needs; are they set, for this batch?
 int param_count(const ntg_plan *p);
 int check_params(const ntg_plan *p, int batch);
-// sum-of-squares declarations (plan_envelope_sos.cpp).  Row j of the plan's nonlinear trajectory rows in the kernels' form.  flag 0: no
-// statement -- the family does not declare the row (or names a flag entry the plan does not have), or the entries it names belong to
-// different basis classes; cl is then the class of the first entry named, or of output 0.  f: the plan's family (null: declares nothing)
-struct NtgFamily;
-struct SosPlanRow { SosRow row; SosTerm term[NTG_SOS_MAXTERMS]; bool need_prm; };
-SosPlanRow sos_plan_row(const ntg_plan *p, const NtgFamily *f, int j);
-void sos_product_tables(double *w);   // SosArgs::w: the triangles of every degree
 // launch shape of the evaluation of `batch` problems: workgroup size, persistent grid, LDS layout; 0 or an error code  (plan.cpp)
 struct EvalShape { int nt, grid; SmemLayout L; };
 int eval_shape(const ntg_plan *p, int batch, EvalShape *s);

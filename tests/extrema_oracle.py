@@ -16,6 +16,7 @@ import numpy as np
 
 import envelope_oracle as eo
 import envelope_sos_oracle as so
+from cert_common import field_x, greville, obstacle_x, rows_spec, scaled_grids   # (the tests and tools take them from here too)
 from ntg_amd import configs as cf
 
 OK, DEPTH, FULL, NAN, NONE = 0, 1, 2, 3, -1
@@ -214,61 +215,10 @@ def exact_extrema(polys, eps):
 
 
 # ---------------- the inputs of the GPU tests ----------------
-def greville(spec, o=0):
-    k = spec.order[o]
-    t = eo.aug_knots(spec.knots[o], k, spec.mult[o])
-    return np.array([t[i + 1:i + k].mean() for i in range(spec.ncoef[o])])
-
-
-def obstacle_x(spec, nb, seed):
-    """cars that drive past the obstacle at (20, 0.5): x = 8 t and y = 0.5, both perturbed"""
-    rng = np.random.default_rng(seed)
-    gv = greville(spec)
-    return np.concatenate([8.0 * gv[None, :] + rng.standard_normal((nb, gv.size)), 0.5 + 1.5 * rng.standard_normal((nb, gv.size))], axis=1)
-
-
-def field_x(spec, lower, seed):
-    """straight routes from the start to the end position of obstacle_field_problems, perturbed"""
-    rng = np.random.default_rng(seed)
-    f = greville(spec) / spec.knots[0][-1]
-    nb = lower.shape[0]
-    xs = lower[:, 0:1] + (lower[:, 6:7] - lower[:, 0:1]) * f[None, :] + 0.5 * rng.standard_normal((nb, f.size))
-    ys = lower[:, 3:4] + (lower[:, 9:10] - lower[:, 3:4]) * f[None, :] + 0.5 * rng.standard_normal((nb, f.size))
-    return np.concatenate([xs, ys], axis=1)
-
-
-def rows_spec():
-    """the kincar plan with three linear trajectory rows declared inequalities: y, x' and x' - y' + 0.5 y''"""
-    s = cf._kincar_spec(1, 6, 3, 20, 101, 5.0, "kincar-2out-k6-l20")
-    ltc = np.zeros((3, s.nz))
-    ltc[0, 3] = 1.0
-    ltc[1, 1] = 1.0
-    ltc[2, 1] = 1.0; ltc[2, 4] = -1.0; ltc[2, 5] = 0.5
-    return dataclasses.replace(s, ltc=ltc, lin_ineq=[0] * s.nlic + [1] * 3 + [0] * s.nlfc)
-
-
 def testfam_spec():
     """testfam with its three outputs in one basis class: the linear row and nonlinear row 0 are certified, row 1 (a cosine) is not"""
     t0 = cf.config_T()
     return dataclasses.replace(t0, order=[t0.order[0]] * 3, kninterv=[t0.kninterv[0]] * 3, knots=[np.array(t0.knots[0]) for _ in range(3)])
-
-
-def scaled_grids(spec, scales):
-    """the plan's knots scaled, every breakpoint at its own fraction of its own knot interval and, in floating point too, inside it
-    (ntg_plan_set_grids wants the plan's combinatorial structure)"""
-    l = spec.kninterv[0]
-    k0 = np.asarray(spec.knots[0]); bp0 = np.asarray(spec.bps)
-    j = np.minimum(np.searchsorted(k0, bp0, side="right") - 1, l - 1)
-    fr = (bp0 - k0[j]) / (k0[j + 1] - k0[j])
-    knots = np.asarray(scales)[:, None] * k0[None, :]
-    bps = np.empty((len(scales), len(bp0)))
-    for b, kn in enumerate(knots):
-        bp = np.maximum(kn[j] + fr * (kn[j + 1] - kn[j]), kn[j])
-        inner = j < l - 1
-        bp[inner] = np.minimum(bp[inner], np.nextafter(kn[j + 1][inner], -np.inf))
-        bp[-1] = max(bp[-1], kn[-1]) if bp0[-1] >= k0[-1] else bp[-1]
-        bps[b] = bp
-    return knots, bps
 
 
 @dataclasses.dataclass

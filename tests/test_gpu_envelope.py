@@ -15,34 +15,11 @@ import torch
 
 import envelope_oracle as eo
 from ntg_amd import api, configs as cf
+from cert_common import NSAMP, cpu, kincar_spec, piece_times, rows_spec, scaled_grids, within
 from gpu_common import dev
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NSAMP = 9   # times per piece, ends included
-
-
-def cpu(out):
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}
-
-
-def within(got, ref, sl, label):
-    """got == ref to slack where ref is finite, the same infinities elsewhere; prints the largest error in slacks"""
-    fin = np.isfinite(ref)
-    assert np.array_equal(got[~fin], ref[~fin]), label + ": the empty pieces differ"
-    err = np.abs(got - np.where(fin, ref, 0.0)) / np.broadcast_to(sl, ref.shape)
-    worst = float(err[fin].max())
-    print(f"{label}: largest error {worst:.3g} slack")
-    assert worst <= 1.0, f"{label}: {worst:.3g} slack"
-
-
-def piece_times(ends):
-    """[npc, NSAMP] uniform times of every piece, ends included; ends [npc + 1]"""
-    u = np.linspace(0.0, 1.0, NSAMP)
-    t = ends[:-1, None] + (ends[1:] - ends[:-1])[:, None] * u[None, :]
-    t[:, -1] = ends[1:]
-    return np.clip(t, ends[0], ends[-1])
 
 
 def encloses(lo, hi, samples, sl, label):
@@ -54,39 +31,7 @@ def encloses(lo, hi, samples, sl, label):
     assert worst <= 1.0, label
 
 
-def scaled_grids(spec, scales):
-    """the plan's knots scaled, every breakpoint at its own fraction of its own knot interval and, in floating point too, inside it
-    (ntg_plan_set_grids wants the plan's combinatorial structure)"""
-    l = spec.kninterv[0]
-    k0 = np.asarray(spec.knots[0]); bp0 = np.asarray(spec.bps)
-    j = np.minimum(np.searchsorted(k0, bp0, side="right") - 1, l - 1)
-    fr = (bp0 - k0[j]) / (k0[j + 1] - k0[j])
-    knots = np.asarray(scales)[:, None] * k0[None, :]
-    bps = np.empty((len(scales), len(bp0)))
-    for b, kn in enumerate(knots):
-        bp = np.maximum(kn[j] + fr * (kn[j + 1] - kn[j]), kn[j])
-        inner = j < l - 1
-        bp[inner] = np.minimum(bp[inner], np.nextafter(kn[j + 1][inner], -np.inf))
-        bp[-1] = max(bp[-1], kn[-1]) if bp0[-1] >= k0[-1] else bp[-1]
-        bps[b] = bp
-    return knots, bps
-
-
 # ---------------- the plans ----------------
-def kincar_spec():
-    return cf._kincar_spec(1, 6, 3, 20, 101, 5.0, "kincar-2out-k6-l20")
-
-
-def rows_spec():
-    """the kincar plan with three linear trajectory rows declared inequalities: y, x' and x' - y' + 0.5 y''"""
-    s = kincar_spec()
-    ltc = np.zeros((3, s.nz))
-    ltc[0, 3] = 1.0
-    ltc[1, 1] = 1.0
-    ltc[2, 1] = 1.0; ltc[2, 4] = -1.0; ltc[2, 5] = 0.5
-    return dataclasses.replace(s, ltc=ltc, lin_ineq=[0] * s.nlic + [1] * 3 + [0] * s.nlfc)
-
-
 @pytest.fixture(scope="module")
 def kplan():
     return api.Plan(kincar_spec(), 0)

@@ -14,76 +14,11 @@ import torch
 import envelope_oracle as eo
 import envelope_sos_oracle as so
 from ntg_amd import api, configs as cf
+from cert_common import NSAMP, cpu, field_x, greville, obstacle_x, piece_times, scaled_grids, within
 from gpu_common import dev
 
 pytestmark = pytest.mark.gpu
-NSAMP = 9   # times per piece, ends included
 NBIG = 67   # leaves the persistent loop a partial last pass
-
-
-def cpu(out):
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}
-
-
-def within(got, ref, sl, label):
-    """got == ref to slack where ref is finite, the same infinities elsewhere; prints the largest error in slacks"""
-    fin = np.isfinite(ref)
-    assert np.array_equal(got[~fin], ref[~fin]), label + ": the pieces without a finite bound differ"
-    sl = np.broadcast_to(sl, ref.shape)
-    err = np.abs(got[fin] - ref[fin]) / sl[fin]
-    worst = float(err.max())
-    print(f"{label}: largest error {worst:.3g} slack")
-    assert worst <= 1.0, f"{label}: {worst:.3g} slack"
-
-
-def piece_times(ends):
-    """[npc, NSAMP] uniform times of every piece, ends included; ends [npc + 1]"""
-    u = np.linspace(0.0, 1.0, NSAMP)
-    t = ends[:-1, None] + (ends[1:] - ends[:-1])[:, None] * u[None, :]
-    t[:, -1] = ends[1:]
-    return np.clip(t, ends[0], ends[-1])
-
-
-def scaled_grids(spec, scales):
-    """the plan's knots scaled, every breakpoint at its own fraction of its own knot interval and, in floating point too, inside it
-    (ntg_plan_set_grids wants the plan's combinatorial structure)"""
-    l = spec.kninterv[0]
-    k0 = np.asarray(spec.knots[0]); bp0 = np.asarray(spec.bps)
-    j = np.minimum(np.searchsorted(k0, bp0, side="right") - 1, l - 1)
-    fr = (bp0 - k0[j]) / (k0[j + 1] - k0[j])
-    knots = np.asarray(scales)[:, None] * k0[None, :]
-    bps = np.empty((len(scales), len(bp0)))
-    for b, kn in enumerate(knots):
-        bp = np.maximum(kn[j] + fr * (kn[j + 1] - kn[j]), kn[j])
-        inner = j < l - 1
-        bp[inner] = np.minimum(bp[inner], np.nextafter(kn[j + 1][inner], -np.inf))
-        bp[-1] = max(bp[-1], kn[-1]) if bp0[-1] >= k0[-1] else bp[-1]
-        bps[b] = bp
-    return knots, bps
-
-
-def greville(spec, o=0):
-    k = spec.order[o]
-    t = eo.aug_knots(spec.knots[o], k, spec.mult[o])
-    return np.array([t[i + 1:i + k].mean() for i in range(spec.ncoef[o])])
-
-
-def obstacle_x(spec, nb, seed):
-    """cars that drive past the obstacle at (20, 0.5): x = 8 t and y = 0.5, both perturbed"""
-    rng = np.random.default_rng(seed)
-    gv = greville(spec)
-    return np.concatenate([8.0 * gv[None, :] + rng.standard_normal((nb, gv.size)), 0.5 + 1.5 * rng.standard_normal((nb, gv.size))], axis=1)
-
-
-def field_x(spec, lower, seed):
-    """straight routes from the start to the end position of obstacle_field_problems, perturbed"""
-    rng = np.random.default_rng(seed)
-    f = greville(spec) / spec.knots[0][-1]
-    nb = lower.shape[0]
-    xs = lower[:, 0:1] + (lower[:, 6:7] - lower[:, 0:1]) * f[None, :] + 0.5 * rng.standard_normal((nb, f.size))
-    ys = lower[:, 3:4] + (lower[:, 9:10] - lower[:, 3:4]) * f[None, :] + 0.5 * rng.standard_normal((nb, f.size))
-    return np.concatenate([xs, ys], axis=1)
 
 
 # ---------------- the plans of tests 1 and 2 ----------------

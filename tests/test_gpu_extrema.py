@@ -14,17 +14,12 @@ import torch
 
 import extrema_oracle as xo
 from ntg_amd import api, configs as cf, family
+from cert_common import NSAMP, cpu, full_list_problem
 from gpu_common import dev
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NSAMP = 9
 KEYS = ("ext", "when", "status", "npieces", "viol", "where")
-
-
-def cpu(out):
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}
 
 
 class Case:
@@ -220,10 +215,7 @@ def test_more_intervals_than_lanes_and_a_full_list():
     """80 knot intervals: level 0 takes two passes.  y repeats one shape on every interval (control points -2 .. 3, -0.25 at the knots), so
     every interval's polygon reaches 0.75 or more below the smallest end value and all 80 pieces are open after level 0: more than the list holds.  (No FULL case with twice the capacity open was
     found on 20 intervals: rows that repeat one shape there keep at most 28 pieces open and end OK once the polygons are flat to rounding.)"""
-    spec = cf.config_O(ninterv=80)
-    spec = dataclasses.replace(spec, ltc=np.eye(1, 6, 3), lin_ineq=[0] * spec.nlic + [1] + [0] * spec.nlfc)   # row 0: y
-    n = spec.ncoef[0]
-    x = np.concatenate([8.0 * xo.greville(spec), np.array([(0.0, -2.0, 3.0)[i % 3] for i in range(n)])])[None, :]
+    spec, x = full_list_problem()
     polys = xo.row_polygons(spec, x)
     ref = xo.level_oracle(polys[0][0], spec.knots[0], 0.0, sides=1)
     assert ref["status"] == xo.FULL and ref["max_open"] == 80 and ref["npieces"] == 80

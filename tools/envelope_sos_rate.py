@@ -1,19 +1,20 @@
 """Diagnostic (not a test): rate of ntg_batch_envelope_sos on config O (one obstacle row, order 6, 20 intervals: products of degree 10) and on
 config D (thrust^2 and speed^2, order 8, 40 intervals: products of degree 10 and 12, the KM = 10 instance) at nsub 0 and 2 -- time per
 call, problems/s, time per (row, piece) and the rate of the bytes it stores (2 x 8 x nnltc x npc per problem, plus 8 nC read).  For
-comparison ntg_batch_envelope's row path (an existing kernel, not the code under test) on the plan of tests/test_gpu_envelope.py's
+comparison ntg_batch_envelope's row path (an existing kernel, not the code under test) on the plan of tests/cert_common.py's
 rows_spec() -- kincar, order 6, 20 intervals, three linear rows y, x', x' - y' + 0.5 y'' -- at the same batch and nsub, and the ratio of
 the two per (row, piece).  One JSON line at the end.
 python tools/envelope_sos_rate.py [batch]"""
-import dataclasses
 import json
 import os
 import sys
 
-import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from cert_common import rows_spec   # the tests' plan with three linear rows
 from ntg_amd import api, configs as cf
 
 batch = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
@@ -29,16 +30,6 @@ def rate(fn, reps=20):
         fn()
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps
-
-
-def rows_spec():
-    """tests/test_gpu_envelope.py: rows_spec()"""
-    s = cf._kincar_spec(1, 6, 3, 20, 101, 5.0, "kincar-2out-k6-l20")
-    ltc = np.zeros((3, s.nz))
-    ltc[0, 3] = 1.0
-    ltc[1, 1] = 1.0
-    ltc[2, 1] = 1.0; ltc[2, 4] = -1.0; ltc[2, 5] = 0.5
-    return dataclasses.replace(s, ltc=ltc, lin_ineq=[0] * s.nlic + [1] * 3 + [0] * s.nlfc)
 
 
 def measure(name, spec, nsub, sos):
