@@ -36,6 +36,8 @@
  *                        breakpoints only: bounds of the sum-of-squares rows (obstacle clearance, thrust^2, speed^2) over whole pieces of time
  *   ntg_batch_extrema    nothing in the reference looks for a row's extremum between samples; constraints.c:119-160 evaluates the trajectory rows
  *                        at the breakpoints only: the minimum and maximum of every certifiable row over the horizon, enclosed to a tolerance, with their times
+ *   ntg_batch_separation nothing in the reference compares two trajectories; its only dense output is SplineInterp (colloc.c:449-484), point by
+ *                        point: the closest approach of pairs of planned bodies over the horizon, enclosed to a tolerance, with its time
  *   ntg_batch_kincar_reverse  examples/kincar.c:68-92 kincar_flat_reverse (the example's flat-to-state map), for a batch
  *   ntg(), npsoloption(), linspace(), SplineInterp(), matrix helpers: see include/ntg.h
  */
@@ -551,6 +553,65 @@ int ntg_batch_extrema(const ntg_plan *p, int batch, const double *d_x,
                       const double *d_lower, const double *d_upper,
                       double *d_ext, double *d_when, int *d_status, int *d_npieces,
                       double *d_viol, int *d_where, void *stream);
+
+/* Certified closest approach of PAIRS of trajectories: the smallest squared distance over the horizon between two planned bodies, enclosed to
+ * a tolerance, with the time of it, and by how much a required distance is missed.  The certificates above work on one problem's own rows;
+ * the distance between two vehicles is not such a row: the two may be cars of one problem or belong to different problems of the batch.  On
+ * a common knot interval both trajectories are polynomials, so their difference is one too, and the squared distance is a sum of squares of
+ * that difference: ntg_batch_envelope_sos's polygons and ntg_batch_extrema's bisection apply.  No family callback runs.
+ * Bodies.  body_outs is a HOST array [nbody][ndim], copied by the call: row g names the ndim outputs that are the coordinates of body g (three
+ * kinematic cars: {0,1}, {2,3}, {4,5}).  1 <= ndim <= NTG_SEP_MAXDIM, 1 <= nbody <= NTG_MAX_OUT.  Every output named must exist, all must
+ * belong to one basis class, and 0 <= deriv < maxderiv[o].  deriv = 0 gives the distance of positions, deriv = 1 the relative speed.
+ * Pairs.  d_pairs is a device array [npairs][4] of {a, b, ga, gb}: body ga of problem a against body gb of problem b; a == b is allowed (two
+ * cars of one problem).  The kernel checks 0 <= a, b < batch and 0 <= ga, gb < nbody before it reads anything of the pair.  A pair that fails
+ * has status NTG_SEP_BADPAIR, NaN in both entries of d_min, in d_when and in both entries of d_viol, and npieces 0; it never causes a read
+ * outside d_x.
+ * Required distance.  d_sep is a device array [npairs] or NULL; s2 = sep * sep, one rounding.  NULL means s2 = +inf: no threshold.
+ * Outputs, any may be NULL but not all five:
+ *   d_min     [npairs][2]  {min_lo, min_hi} of the squared distance
+ *   d_when    [npairs]     the time of min_hi
+ *   d_status  [npairs]     NTG_EXTREMA_OK / _DEPTH / _FULL / _NAN, or NTG_SEP_BADPAIR
+ *   d_npieces [npairs]     polygons evaluated
+ *   d_viol    [npairs][2]  {attained, certified}; requires d_sep
+ * Definition, per pair.
+ * 1. Difference coefficients.  The class of the named outputs has n coefficients per output.  For dimension t,
+ *    delta_t[i] = x[a][iC[oa_t] + i] - x[b][iC[ob_t] + i], i = 0 .. n-1, with oa_t = body_outs[ga][t] and ob_t = body_outs[gb][t]: one IEEE
+ *    subtraction per coefficient, and nothing else is rounded here.  From here on the pair is a virtual problem with ndim outputs whose
+ *    coefficients are delta.
+ * 2. Level-0 polygons.  The row is c(t) = sum_t (D^deriv delta_t(t))^2.  On knot interval j its polygon is formed by the sequence of
+ *    operations of ntg_batch_envelope_sos: extract, deriv differences, the square by the W_d tables, the terms summed in dimension order; the
+ *    terms are {dimension t, derivative deriv, shift 0, no parameter} (beta - 0.0 and beta are the same bits).  The polygon is bit-identical
+ *    to that of ntg_batch_extrema at sides = 1 on a plan whose sum-of-squares row has those terms with zero shift, given delta as coefficients.
+ * 3. Levels.  Steps 2 to 4 of ntg_batch_extrema's definition with sides = 1, and one addition to the opening rule: a piece is open iff
+ *    plo < U - tol and not plo >= s2.  A piece that cannot come closer than the required distance retires at once, so with a threshold most
+ *    pairs of a fleet end at level 0.  Statuses NTG_EXTREMA_OK / _DEPTH / _FULL / _NAN with the same meaning, the cap NTG_EXTREMA_CAP.
+ * 4. Results.  min_lo = Rlo, min_hi = U (an attained value), d_when the time of U, npieces the number of polygons evaluated.  Always
+ *    min_lo <= min over t of c <= min_hi, up to the rounding below.  With status OK, min_lo >= min(min_hi - tol, s2).
+ * 5. Violation, in squared distance.  attained = max(s2 - min_hi, 0): the pair really comes closer than required, at d_when.
+ *    certified = max(s2 - min_lo, 0): at no time does the pair come closer than required by more than this.  certified == 0 certifies the
+ *    separation over the whole horizon.  A NaN s2 makes both figures NaN; the bisection then runs as without a threshold.
+ * 6. NaN.  A NaN in any plo is handled as in ntg_batch_extrema's rule 5: both numbers and the time are NaN, the status is NAN.
+ * Rounding.  ntg_batch_extrema's slack for a quadratic row, 2^-39 * sum_t S_t^2, with S_t = max_i (|x_a,i| + |x_b,i|) * (2 (k - 1) / h_min)^deriv:
+ * the sum of magnitudes in place of max |c| covers the one rounding of delta.
+ * Arguments.  tol is finite and >= 0; 0 <= max_depth <= NTG_EXTREMA_MAX_DEPTH.
+ * Stream ordered, without scratch in HBM and without floating-point atomics: a wavefront owns a pair and keeps delta and the open pieces in
+ * LDS.  Results are bit-identical from call to call; the result of a pair does not depend on the other pairs or on the batch.  Per-problem
+ * parameters are ignored.
+ * npairs <= 0 or batch <= 0 returns 0 after the null-plan and argument checks.  NTG_E_BADARG for a null plan, d_x, body_outs or d_pairs, for
+ * ndim, nbody, deriv, tol or max_depth outside the ranges above, an output index out of range, all five outputs null, d_viol without d_sep.
+ * NTG_E_UNSUPPORTED, with a message that says why, for host-callback plans, for named outputs of different basis classes (the message names
+ * the two outputs), for a plan with per-problem grids in force (two problems then have no common knot intervals; the a == b case included),
+ * and for tables above 158 KiB of LDS: 385 product weights, l (k^2 + 2) + 1 of the class, and per wavefront of four ndim n + 64 (D_max + 2)
+ * doubles with D_max = 10 (order <= 6) or 18. */
+#define NTG_SEP_MAXDIM 4            /* == NTG_SOS_MAXTERMS */
+#define NTG_SEP_BADPAIR (-2)        /* status: a problem or body index of the pair is out of range */
+
+int ntg_batch_separation(const ntg_plan *p, int batch, const double *d_x,
+                         int nbody, int ndim, const int *body_outs, int deriv,
+                         int npairs, const int *d_pairs, const double *d_sep,
+                         double tol, int max_depth,
+                         double *d_min, double *d_when, int *d_status, int *d_npieces,
+                         double *d_viol, void *stream);
 
 /* The flat-to-state map of the kinematic car for a whole ntg_batch_interp result (examples/kincar.c:68-92 kincar_flat_reverse,
  * called per sample by the example's output loop, kincar.c:392-406): d_z [batch][ntimes][nz] -> d_state [batch][ntimes][ncars][5] =

@@ -85,6 +85,7 @@ def lib():
         L.ntg_plan_sos_rows.argtypes = [C.c_void_p, ip]
         L.ntg_batch_extrema.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_int] + [C.c_void_p] * 9
         L.ntg_plan_extrema_rows.argtypes = [C.c_void_p, ip]
+        L.ntg_batch_separation.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int] + [C.c_void_p] * 6
         L.ntg_batch_refine.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_plan_set_grids.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ntg_plan_clear_grids.argtypes = [C.c_void_p]
@@ -475,6 +476,35 @@ class Plan:
                                        _ptr(out["status"]), _ptr(out["npieces"]), _ptr(out.get("viol")), _ptr(out.get("where")), self._stream()))
         return out
 
+    def separation(self, x, pairs, bodies, deriv: int = 0, tol: float = 0.0, max_depth: int = 30, sep=None):
+        """The closest approach of pairs of planned bodies over the whole horizon, enclosed to tol, by bisection (ntg_batch_separation):
+        x [batch, nC]; bodies [nbody, ndim] (host, integers) names the outputs that are the coordinates of every body, e.g. [[0, 1], [2, 3],
+        [4, 5]] for three cars; pairs [npairs, 4] int32 on the device = (a, b, ga, gb), body ga of problem a against body gb of problem b
+        (a == b: two cars of one problem).  deriv = 0: the distance of positions, 1: the relative speed.  sep [npairs] (device) or None: the
+        required distances.  Returns a dict: min [npairs, 2] = (min_lo, min_hi) of the SQUARED distance, when [npairs] the time where min_hi
+        is attained, status [npairs] (EXTREMA_OK / _DEPTH / _FULL / _NAN, or SEP_BADPAIR for indices out of range), npieces [npairs] and,
+        with sep, viol [npairs, 2] = (attained, certified) = max(sep^2 - min_hi, 0), max(sep^2 - min_lo, 0): viol[:, 1] == 0 certifies the
+        separation over the whole horizon.  With sep, a piece that cannot come closer than required retires at once."""
+        import torch
+        sp, dev, batch = self._cert_inputs(x, None, None)
+        _check_tensor(pairs, dev, torch.int32); _check_tensor(sep, dev)
+        body = np.ascontiguousarray(np.asarray(bodies, dtype=np.int32))
+        if body.ndim != 2 or body.size == 0:
+            raise NtgError("bodies must be [nbody, ndim] output indices")
+        if pairs.dim() != 2 or pairs.shape[1] != 4:
+            raise NtgError("pairs must be an int32 tensor [npairs, 4] = (a, b, ga, gb)")
+        npairs = pairs.shape[0]
+        if sep is not None and sep.shape != (npairs,):
+            raise NtgError(f"sep must be [{npairs}]")
+        out = {"min": torch.empty((npairs, 2), dtype=torch.float64, device=dev), "when": torch.empty(npairs, dtype=torch.float64, device=dev),
+               "status": torch.empty(npairs, dtype=torch.int32, device=dev), "npieces": torch.empty(npairs, dtype=torch.int32, device=dev)}
+        if sep is not None:
+            out["viol"] = torch.empty((npairs, 2), dtype=torch.float64, device=dev)
+        _check(lib().ntg_batch_separation(self.h, batch, _ptr(x), body.shape[0], body.shape[1], body.ctypes.data_as(ip), int(deriv), npairs, _ptr(pairs), _ptr(sep),
+                                          float(tol), int(max_depth), _ptr(out["min"]), _ptr(out["when"]), _ptr(out["status"]), _ptr(out["npieces"]), _ptr(out.get("viol")),
+                                          self._stream()))
+        return out
+
     def set_grids(self, knots, bps, with_precond: bool = True):
         """Per-problem grids: knots [batch, ninterv+1], bps [batch, nbps] (device, float64).  See ntg_plan_set_grids."""
         _check_tensor(knots, knots.device); _check_tensor(bps, bps.device)
@@ -584,6 +614,7 @@ class Plan:
 ENVELOPE_MAX_NSUB = 6   # NTG_ENVELOPE_MAX_NSUB
 EXTREMA_MAX_DEPTH, EXTREMA_CAP = 30, 64   # NTG_EXTREMA_MAX_DEPTH, NTG_EXTREMA_CAP
 EXTREMA_OK, EXTREMA_DEPTH, EXTREMA_FULL, EXTREMA_NAN, EXTREMA_NONE = 0, 1, 2, 3, -1   # NTG_EXTREMA_* status codes
+SEP_MAXDIM, SEP_BADPAIR = 4, -2   # NTG_SEP_MAXDIM, NTG_SEP_BADPAIR
 
 
 def envelope_pieces(spec_or_knots, o: int = 0, nsub: int = 0) -> np.ndarray:

@@ -21,6 +21,8 @@
 //                          with its own x row, parameter row and work list.
 //   extrema_pp_kernel      per-problem grids: the same, with breaks and weights of the wave's own problem.
 // No scratch in HBM, no atomics, nothing depends on the batch around a problem.  Every private array is indexed by unrolled loop counters only.
+// The levels themselves (ext_levels) take the row as a source of level-0 polygons and a threshold flag: ext_row hands them a row of the plan,
+// separation.hpp the squared difference of two trajectories, with its "not plo >= s2" in the opening rule.  There is one level loop.
 #pragma once
 #include "envelope_sos.hpp"
 
@@ -77,25 +79,21 @@ struct ExtLds {
 	long long *keys;     // [NTG_EXTREMA_CAP]: interval << 32 | index of the piece at its level
 };
 
-// one row of problem b.  res = {min_lo, min_hi, max_lo, max_hi}, tw = {t_min, t_max}; every lane returns the same figures
-template <int KM>
-__device__ __forceinline__ void ext_row(const ExtArgs &A, const SosTables &T, const ExtLds &M, int row, int lane, double (&res)[4], double (&tw)[2], int &status, int &npieces)
+// what the levels need of a row: the breaks and interval lengths of its basis class, the number l of its knot intervals, the degree D of its
+// polygon, and the call's figures.  s2 (THR instances only): a piece whose polygon does not reach below s2 retires at once
+struct ExtRun { const double *kn, *hh; int l, D, max_depth, sides; double tol, s2; };
+
+// The definition's levels for one row, by one wave: src(j) is the row's level-0 polygon on knot interval j.  res = {min_lo, min_hi, max_lo,
+// max_hi}, tw = {t_min, t_max}; every lane returns the same figures.  THR = false is ntg_batch_extrema's opening rule; THR = true adds
+// ntg_batch_separation's "and not plo >= s2" to the lower side
+template <int KM, bool THR, class Src>
+__device__ __forceinline__ void ext_levels(const ExtRun &Q, const ExtLds &M, const Src &src, int lane, double (&res)[4], double (&tw)[2], int &status, int &npieces)
 {
 	constexpr int KD = 2 * KM - 1;
-	const bool lin = row < A.lin.nltc;
-	const double *lr = A.lin.ltc + (size_t)(lin ? row : 0) * A.lin.nz;
-	const SosRow R = T.row[lin ? 0 : row - A.lin.nltc];   // (a linear row reads none of it)
-	int cl = R.cl, D = R.D, flag = R.flag;
-	if (lin) { const EnvRowShape sh = env_row_shape(A.lin, T.c, lr); cl = sh.cl; D = sh.D; flag = sh.flag; }
-	if (!flag) {
-		res[0] = -INFINITY; res[1] = INFINITY; res[2] = -INFINITY; res[3] = INFINITY;
-		tw[0] = tw[1] = NAN; status = NTG_EXTREMA_NONE; npieces = 0;
-		return;
-	}
-	const EnvClass C = T.c[cl];
-	const double *kn = M.kns + A.koff[cl], *hh = M.tab + C.hoff;
-	const double tol = A.tol;
-	const bool s_lo = A.sides & 1, s_hi = A.sides & 2;
+	const int D = Q.D;
+	const double *kn = Q.kn, *hh = Q.hh;
+	const double tol = Q.tol;
+	const bool s_lo = Q.sides & 1, s_hi = Q.sides & 2;
 	const unsigned long long below = (1ull << lane) - 1ull;
 	double U = INFINITY, tU = INFINITY, V = -INFINITY, tV = INFINITY;   // the same in every lane after a level's butterfly
 	double Rlo = INFINITY, Rhi = -INFINITY;   // retired pieces, this lane's
@@ -105,23 +103,15 @@ __device__ __forceinline__ void ext_row(const ExtArgs &A, const SosTables &T, co
 
 	// level 0: lane + 64 t takes interval j.  Two rounds over the intervals: the ends first, then the decisions, which need U and V of the whole
 	// level.  One polygon per lane (l <= 64) stays in registers between the rounds; otherwise the second round forms it again, the same way.
-	const int npass = (C.l + 63) >> 6;
+	const int npass = (Q.l + 63) >> 6;
 	EnvPoly<KD> P;
 #pragma unroll
 	for (int s = 0; s < KD; s++) P.b[s] = 0.0;
 	for (int it = 0; it < 2 * npass; it++) {
 		const bool second = it >= npass;
 		const int j = lane + 64 * (second ? it - npass : it);
-		const bool on = j < C.l;
-		if (on && (!second || npass > 1)) {
-			if (lin) {   // the whole interval: piece 0 of 1
-				const EnvPoly<KM> L = env_poly_lin<KM>(A.lin, lr, cl, D, C, M.tab, M.xrow, j, 0, 0);
-#pragma unroll
-				for (int s = 0; s < KD; s++) P.b[s] = 0.0;
-#pragma unroll
-				for (int s = 0; s < KM; s++) P.b[s] = L.b[s];
-			} else P = sos_poly<KM>(T, row - A.lin.nltc, R, C, M.wl, M.tab, M.xrow, M.prow, j, 0, 0);
-		}
+		const bool on = j < Q.l;
+		if (on && (!second || npass > 1)) P = src(j);
 		if (!second) {
 			if (on) {
 				const double e0 = P.b[0], e1 = ext_last<KD>(P, D);
@@ -135,7 +125,7 @@ __device__ __forceinline__ void ext_row(const ExtArgs &A, const SosTables &T, co
 			if (on) {
 				P.range(D, plo, phi);
 				nan = nan || plo != plo || phi != phi;
-				open = (s_lo && plo < U - tol) || (s_hi && phi > V + tol);
+				open = (s_lo && plo < U - tol && !(THR && plo >= Q.s2)) || (s_hi && phi > V + tol);
 			}
 			const unsigned long long m = __ballot(open);
 			const int pos = nopen + __popcll(m & below);
@@ -154,14 +144,14 @@ __device__ __forceinline__ void ext_row(const ExtArgs &A, const SosTables &T, co
 			nopen += __popcll(m);
 		}
 	}
-	npieces = C.l;
+	npieces = Q.l;
 
 	// levels: the open pieces of level lam are in the list; their children form level lam + 1
 	status = NTG_EXTREMA_OK;
-	for (int lam = 0; lam <= A.max_depth; lam++) {
+	for (int lam = 0; lam <= Q.max_depth; lam++) {
 		if (nopen == 0) break;
-		if (lam == A.max_depth || nopen > NTG_EXTREMA_CAP) {
-			status = lam == A.max_depth ? NTG_EXTREMA_DEPTH : NTG_EXTREMA_FULL;
+		if (lam == Q.max_depth || nopen > NTG_EXTREMA_CAP) {
+			status = lam == Q.max_depth ? NTG_EXTREMA_DEPTH : NTG_EXTREMA_FULL;
 			if (Olo < Rlo) Rlo = Olo;
 			if (Ohi > Rhi) Rhi = Ohi;
 			break;
@@ -206,8 +196,8 @@ __device__ __forceinline__ void ext_row(const ExtArgs &A, const SosTables &T, co
 			nan = nan || llo != llo || lhi != lhi || rlo != rlo || rhi != rhi;
 		}
 		ext_wave_ends(U, tU, V, tV);
-		const bool openL = on && ((s_lo && llo < U - tol) || (s_hi && lhi > V + tol));
-		const bool openR = on && ((s_lo && rlo < U - tol) || (s_hi && rhi > V + tol));
+		const bool openL = on && ((s_lo && llo < U - tol && !(THR && llo >= Q.s2)) || (s_hi && lhi > V + tol));
+		const bool openR = on && ((s_lo && rlo < U - tol && !(THR && rlo >= Q.s2)) || (s_hi && rhi > V + tol));
 		const unsigned long long mL = __ballot(openL), mR = __ballot(openR);
 		const int posL = __popcll(mL & below) + __popcll(mR & below), posR = posL + (openL ? 1 : 0);
 		if (openL) {
@@ -244,6 +234,46 @@ __device__ __forceinline__ void ext_row(const ExtArgs &A, const SosTables &T, co
 	} else {
 		res[0] = Rlo; res[1] = U; res[2] = V; res[3] = Rhi; tw[0] = tU; tw[1] = tV;
 	}
+}
+
+// level-0 polygons of a row of ntg_batch_extrema: a linear row's (env_poly_lin, the whole interval: piece 0 of 1) or a sum-of-squares row's
+template <int KM>
+struct ExtRowSrc {
+	const ExtArgs &A; const SosTables &T; const ExtLds &M;
+	bool lin; const double *lr; int row, cl, D; SosRow R; EnvClass C;
+	__device__ __forceinline__ EnvPoly<2 * KM - 1> operator()(int j) const
+	{
+		constexpr int KD = 2 * KM - 1;
+		EnvPoly<KD> P;
+		if (lin) {
+			const EnvPoly<KM> L = env_poly_lin<KM>(A.lin, lr, cl, D, C, M.tab, M.xrow, j, 0, 0);
+#pragma unroll
+			for (int s = 0; s < KD; s++) P.b[s] = 0.0;
+#pragma unroll
+			for (int s = 0; s < KM; s++) P.b[s] = L.b[s];
+		} else P = sos_poly<KM>(T, row - A.lin.nltc, R, C, M.wl, M.tab, M.xrow, M.prow, j, 0, 0);
+		return P;
+	}
+};
+
+// one row of problem b
+template <int KM>
+__device__ __forceinline__ void ext_row(const ExtArgs &A, const SosTables &T, const ExtLds &M, int row, int lane, double (&res)[4], double (&tw)[2], int &status, int &npieces)
+{
+	const bool lin = row < A.lin.nltc;
+	const double *lr = A.lin.ltc + (size_t)(lin ? row : 0) * A.lin.nz;
+	const SosRow R = T.row[lin ? 0 : row - A.lin.nltc];   // (a linear row reads none of it)
+	int cl = R.cl, D = R.D, flag = R.flag;
+	if (lin) { const EnvRowShape sh = env_row_shape(A.lin, T.c, lr); cl = sh.cl; D = sh.D; flag = sh.flag; }
+	if (!flag) {
+		res[0] = -INFINITY; res[1] = INFINITY; res[2] = -INFINITY; res[3] = INFINITY;
+		tw[0] = tw[1] = NAN; status = NTG_EXTREMA_NONE; npieces = 0;
+		return;
+	}
+	const EnvClass C = T.c[cl];
+	const ExtRun Q{M.kns + A.koff[cl], M.tab + C.hoff, C.l, D, A.max_depth, A.sides, A.tol, INFINITY};
+	const ExtRowSrc<KM> src{A, T, M, lin, lr, row, cl, D, R, C};
+	ext_levels<KM, false>(Q, M, src, lane, res, tw, status, npieces);
 }
 
 // every row of problem b, by one wave whose x row and parameter row are in M

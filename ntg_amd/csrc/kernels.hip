@@ -23,6 +23,8 @@
 //                   Bezier product of those polygons (envelope_sos.hpp)
 //   extrema_*       minimum and maximum of those rows over the horizon, enclosed to a tolerance, by
 //                   bisection of the same polygons from a work list in LDS (extrema.hpp)
+//   separation_kernel  smallest squared distance of pairs of bodies over the horizon: the squared
+//                   difference of two trajectories as a sum-of-squares row, by that bisection (separation.hpp)
 //
 // Mapping to CDNA4: one workgroup per problem; breakpoints (then coefficients) across the
 // lanes; basis tables, knots/breakpoints and the coefficient vector staged in LDS; the only
@@ -37,6 +39,7 @@
 #include "envelope.hpp"
 #include "envelope_sos.hpp"
 #include "extrema.hpp"
+#include "separation.hpp"
 #include "kkt.hpp"
 #include "verify.hpp"
 
@@ -670,6 +673,17 @@ hipError_t ntg_launch_extrema(const ExtArgs &A, int ncu, hipStream_t st)
 	return NTG_CERT_LAUNCH(extrema, NTG_EXTREMA_NT, (A.g.batch + NTG_EXTREMA_NT / 64 - 1) / (NTG_EXTREMA_NT / 64));
 }
 #undef NTG_CERT_LAUNCH
+// ... and one of ntg_batch_separation a pass of four pairs.  Shared grids only: the entry point refuses per-problem grids, so there is no kpp
+hipError_t ntg_launch_separation(const SepArgs &A, int ncu, hipStream_t st)
+{
+	const size_t lds = ntg_separation_lds(A);
+	constexpr int NT = NTG_EXTREMA_NT;
+	if (lds > NTG_EXTREMA_LDS_MAX || A.g.kmax > NTG_MAX_ORDER || A.g.pp || A.g.nclass != 1) return hipErrorInvalidValue;
+	if (A.npairs <= 0 || A.g.batch <= 0) return hipSuccess;
+	const int units = (A.npairs + NT / 64 - 1) / (NT / 64);
+	return A.g.kmax <= 6 ? launch_cert<SepArgs>(nullptr, separation_kernel<NT, 6>, A, NT, units, ncu, lds, st)
+	                     : launch_cert<SepArgs>(nullptr, separation_kernel<NT, NTG_MAX_ORDER>, A, NT, units, ncu, lds, st);
+}
 
 // Flat flag -> state and input of the kinematic car, the map of examples/kincar.c:68-92 (kincar_flat_reverse), for every car
 // of every problem at every time of an ntg_batch_interp result: z [n][nz] with the flag of car c at entries 6 c .. 6 c + 5

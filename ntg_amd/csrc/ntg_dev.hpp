@@ -313,3 +313,28 @@ static inline size_t ntg_extrema_lds(const ExtArgs &A)
 }
 // ... and what a workgroup may ask for: 160 KiB less the static part (the row, term and class tables)
 #define NTG_EXTREMA_LDS_MAX (160 * 1024 - 2048)
+
+// ntg_batch_separation (separation.hpp): the smallest squared distance over the horizon of pairs of bodies, each body ndim outputs of one
+// basis class.  g holds that ONE class (nclass = 1, its tables at offset 0 of the LDS table, kmax its order) and the batch the pairs'
+// problem indices are checked against.  sos: the product tables, and row 0 with ndim terms {coefficient offset t n, derivative deriv, no
+// shift} -- the sum of squares of the pair's difference coefficients delta [ndim][n], which a wave stages in place of a coefficient row.
+// biC[g][t]: the coefficient offset of coordinate t of body g.  pairs [npairs][4] = {a, b, ga, gb}; sep [npairs] or null.
+// Outputs as documented at ntg_batch_separation, any may be null.
+struct SepArgs {
+	CertBase g;
+	CertSos sos;
+	int npairs, nbody, ndim, n, max_depth, pad;
+	double tol;
+	int biC[NTG_MAX_OUT][NTG_SEP_MAXDIM];
+	const int *pairs; const double *sep;
+	double *min, *when, *viol; int *status, *npieces;
+};
+static_assert(sizeof(SepArgs) <= 4096, "SepArgs travels as a kernel argument");
+static inline int ntg_separation_kd(const SepArgs &A) { return A.g.kmax <= 6 ? 11 : 2 * NTG_MAX_ORDER - 1; }
+// dynamic LDS: the unfolded product tables, the extraction table and the breaks of the class; per wave delta, the work list and its keys.
+// The limit is ntg_batch_extrema's
+static inline size_t ntg_separation_lds(const SepArgs &A)
+{
+	const size_t wave = (size_t)A.ndim * A.n + (size_t)NTG_EXTREMA_CAP * (ntg_separation_kd(A) + 1);
+	return ((size_t)NTG_SOS_WFULL + A.g.ne + A.g.lmax + 1 + (size_t)(NTG_EXTREMA_NT / 64) * wave) * 8;
+}

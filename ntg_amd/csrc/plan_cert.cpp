@@ -1,9 +1,9 @@
-// plan_cert.cpp -- the time certificates behind include/ntg_amd.h: ntg_batch_envelope, ntg_batch_envelope_sos, ntg_batch_extrema and the
-// queries ntg_plan_sos_rows and ntg_plan_extrema_rows.  What they share comes first: the refusals (each call tests them between its own
+// plan_cert.cpp -- the time certificates behind include/ntg_amd.h: ntg_batch_envelope, ntg_batch_envelope_sos, ntg_batch_extrema,
+// ntg_batch_separation and the queries ntg_plan_sos_rows and ntg_plan_extrema_rows.  What they share comes first: the refusals (each call tests them between its own
 // argument checks, in its own order), which rows of a plan are certified -- a linear trajectory row whose outputs share a basis class, from
 // the host mirror of ltc; a nonlinear row by the family's sum-of-squares declaration, NtgFamily::sos, against the plan's iz / cls -- and the
 // three parts of the kernels' arguments (CertBase, CertLin, CertSos: ntg_dev.hpp).  An entry point then reads: its own argument checks,
-// the setup, its own fields, the launch.  The arithmetic is in envelope.hpp, envelope_sos.hpp and extrema.hpp.  No family callback runs, so
+// the setup, its own fields, the launch.  The arithmetic is in envelope.hpp, envelope_sos.hpp, extrema.hpp and separation.hpp.  No family callback runs, so
 // the calls serve every built-in family and every loaded module.  They allocate nothing.
 #include "plan_priv.hpp"
 #include "family_module.hpp"
@@ -116,6 +116,15 @@ void cert_lin(const ntg_plan *p, CertLin &L)
 	L.nout = D.nout; L.nz = D.nz; L.nltc = D.nltc; L.slot0 = D.nlic; L.ltc = p->d_ltc;
 	for (int o = 0; o < D.nout; o++) { L.cls[o] = D.cls[o]; L.d[o] = D.d[o]; L.iC[o] = D.iC[o]; L.iz[o] = D.iz[o]; }
 }
+// the product tables W_d[i][j] = C(d,i) C(d,j) / C(2d,i+j), i <= j: two exact integers, one rounding
+void cert_products(CertSos &S)
+{
+	for (int d = 0; d < NTG_MAX_ORDER; d++) {
+		double *q = S.w + ntg_sos_wtri(d);
+		for (int i = 0; i <= d; i++)
+			for (int j = i; j <= d; j++) *q++ = (double)(binom(d, i) * binom(d, j)) / (double)binom(2 * d, i + j);
+	}
+}
 // the rows, terms and product tables; how many rows are certified, the first that is not (or -1), and the parameter row where a term reads it
 struct SosCount { int ncert, first0; bool need_prm; };
 SosCount cert_sos(const ntg_plan *p, const NtgFamily *f, CertSos &S)
@@ -132,11 +141,7 @@ SosCount cert_sos(const ntg_plan *p, const NtgFamily *f, CertSos &S)
 	S.nrow = D.nnltc; S.slot0 = D.nlic + D.nltc + D.nlfc + D.nnlic;
 	S.np = n.need_prm ? p->prm_n : 0;
 	S.prm = n.need_prm ? p->T.prm : nullptr; S.pp_prm = n.need_prm ? p->T.pp_prm : 0;
-	for (int d = 0; d < NTG_MAX_ORDER; d++) {   // W_d[i][j] = C(d,i) C(d,j) / C(2d,i+j), i <= j: two exact integers, one rounding
-		double *q = S.w + ntg_sos_wtri(d);
-		for (int i = 0; i <= d; i++)
-			for (int j = i; j <= d; j++) *q++ = (double)(binom(d, i) * binom(d, j)) / (double)binom(2 * d, i + j);
-	}
+	cert_products(S);
 	return n;
 }
 // what both calls on sum-of-squares rows refuse about them once they know that some row is certified: more rows than the kernels' tables
@@ -269,5 +274,55 @@ extern "C" int ntg_batch_extrema(const ntg_plan *p, int batch, const double *d_x
 	A.ext = d_ext; A.when = d_when; A.status = d_status; A.npieces = d_npieces; A.viol = d_viol; A.where = d_where;
 	HIPCHK(hipSetDevice(p->device));
 	HIPCHK(ntg_launch_extrema(A, plan_ncu(p), (hipStream_t)stream));
+	return 0;
+}
+
+extern "C" int ntg_batch_separation(const ntg_plan *p, int batch, const double *d_x, int nbody, int ndim, const int *body_outs, int deriv, int npairs, const int *d_pairs,
+                                    const double *d_sep, double tol, int max_depth, double *d_min, double *d_when, int *d_status, int *d_npieces, double *d_viol, void *stream)
+{
+	if (!p) return fail(NTG_E_BADARG, "null plan");
+	if (!d_x || !body_outs || !d_pairs) return fail(NTG_E_BADARG, "null argument");
+	if (ndim < 1 || ndim > NTG_SEP_MAXDIM) return fail(NTG_E_BADARG, "ndim must lie in 1 .. " + std::to_string(NTG_SEP_MAXDIM));
+	if (nbody < 1 || nbody > NTG_MAX_OUT) return fail(NTG_E_BADARG, "nbody must lie in 1 .. " + std::to_string(NTG_MAX_OUT));
+	if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(NTG_E_BADARG, "tol must be finite and >= 0");
+	if (max_depth < 0 || max_depth > NTG_EXTREMA_MAX_DEPTH) return fail(NTG_E_BADARG, "max_depth must lie in 0 .. " + std::to_string(NTG_EXTREMA_MAX_DEPTH));
+	const NtgDims &D = p->D;
+	for (int i = 0; i < nbody * ndim; i++) {
+		const int o = body_outs[i];
+		if (o < 0 || o >= D.nout) return fail(NTG_E_BADARG, "body " + std::to_string(i / ndim) + " names output " + std::to_string(o) + ": the plan has outputs 0 .. " + std::to_string(D.nout - 1));
+		if (deriv < 0 || deriv >= D.d[o]) return fail(NTG_E_BADARG, "deriv must lie in 0 .. maxderiv - 1 of every output named (output " + std::to_string(o) + ": " + std::to_string(D.d[o]) + ")");
+	}
+	if (!d_min && !d_when && !d_status && !d_npieces && !d_viol) return fail(NTG_E_BADARG, "no output asked for: pass d_min, d_when, d_status, d_npieces or d_viol");
+	if (d_viol && !d_sep) return fail(NTG_E_BADARG, "d_viol needs the required distances d_sep");
+	if (npairs <= 0 || batch <= 0) return 0;
+	if (int rc = cert_host(p)) return rc;
+	for (int i = 1; i < nbody * ndim; i++)   // one polygon per knot interval needs common knot intervals
+		if (D.cls[body_outs[i]] != D.cls[body_outs[0]])
+			return fail(NTG_E_UNSUPPORTED, "outputs " + std::to_string(body_outs[0]) + " and " + std::to_string(body_outs[i]) + " of the bodies belong to different basis classes: their "
+			                                   "difference has no common pieces");
+	if (p->grid_batch)
+		return fail(NTG_E_UNSUPPORTED, "the plan carries per-problem grids: two problems then have no common knot intervals (ntg_batch_separation takes plans on their own grid only)");
+	SepArgs A{};
+	cert_base(p, batch, d_x, nullptr, nullptr, A.g);
+	cert_products(A.sos);
+	{   // the one class of the bodies, alone in the tables
+		const int cl = D.cls[body_outs[0]];
+		const EnvClass C = A.g.c[cl];
+		A.g.nclass = 1; A.g.c[0] = EnvClass{C.k, C.m, C.l, 0, C.l * C.k * C.k}; A.g.ne = C.l * (C.k * C.k + 1);
+		A.g.lmax = C.l; A.g.kmax = C.k; A.g.knots[0] = A.g.knots[cl];
+		A.n = C.l * (C.k - C.m) + C.m;
+		A.sos.nrow = 1;
+		A.sos.row[0] = SosRow{ndim, 0, 2 * std::max(C.k - 1 - deriv, 0), 1};
+		for (int t = 0; t < ndim; t++) A.sos.term[0][t] = SosTerm{t * A.n, deriv, -1, 0, 0.0};
+	}
+	for (int g = 0; g < nbody; g++)
+		for (int t = 0; t < ndim; t++) A.biC[g][t] = D.iC[body_outs[g * ndim + t]];
+	A.npairs = npairs; A.nbody = nbody; A.ndim = ndim; A.max_depth = max_depth; A.tol = tol;
+	if (A.g.kmax > NTG_MAX_ORDER || ntg_separation_lds(A) > NTG_EXTREMA_LDS_MAX)
+		return fail(NTG_E_UNSUPPORTED, "the tables and work lists of this call exceed " + std::to_string(NTG_EXTREMA_LDS_MAX / 1024) + " KiB of LDS");
+	A.pairs = d_pairs; A.sep = d_sep;
+	A.min = d_min; A.when = d_when; A.status = d_status; A.npieces = d_npieces; A.viol = d_viol;
+	HIPCHK(hipSetDevice(p->device));
+	HIPCHK(ntg_launch_separation(A, plan_ncu(p), (hipStream_t)stream));
 	return 0;
 }
