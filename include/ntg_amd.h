@@ -38,6 +38,8 @@
  *                        at the breakpoints only: the minimum and maximum of every certifiable row over the horizon, enclosed to a tolerance, with their times
  *   ntg_batch_separation nothing in the reference compares two trajectories; its only dense output is SplineInterp (colloc.c:449-484), point by
  *                        point: the closest approach of pairs of planned bodies over the horizon, enclosed to a tolerance, with its time
+ *   ntg_batch_forms      nothing in the reference bounds a function of the flag between samples: the minimum and maximum over the horizon of quadratic
+ *                        forms of the flag declared at the call (speed^2, the turning numerator, weighted thrust, ellipses, rows of a module)
  *   ntg_batch_kincar_reverse  examples/kincar.c:68-92 kincar_flat_reverse (the example's flat-to-state map), for a batch
  *   ntg(), npsoloption(), linspace(), SplineInterp(), matrix helpers: see include/ntg.h
  */
@@ -436,9 +438,10 @@ int ntg_batch_envelope(const ntg_plan *p, int batch, const double *d_x, int nsub
  * Declaration.  A family declares row j of its nonlinear trajectory rows, on the host, as
  *   c_j(z) = sum_{t < nt_j} (z[v_t] - s_t)^2,   s_t = const_t + (pidx_t >= 0 ? prm_row_j[pidx_t] : 0)
  * with nt_j <= NTG_SOS_MAXTERMS, v_t a flag entry and prm_row_j the problem's parameter block of that row (ntg_plan_set_params).  Squares
- * only: no weights, no bilinear terms.  The built-in families declare: OBSTACLE row 0; OBSTACLE_FIELD every row; QUADROTOR rows 0 and 1;
+ * only: no weights, no bilinear terms (ntg_batch_forms certifies what this excludes: the form is declared at the call).  The built-in families declare: OBSTACLE row 0; OBSTACLE_FIELD every row; QUADROTOR rows 0 and 1;
  * TESTFAM row 0 (its row 1 has a cosine).  MANIP, KINCAR and VANDERPOL declare nothing.  Loaded modules declare nothing: the module
- * descriptor has no field for it yet, so every row of a module family counts as undeclared.
+ * descriptor has no field for it yet, so every row of a module family counts as undeclared (ntg_batch_forms certifies such a row: the
+ * caller declares it at the call).
  * ntg_plan_sos_rows: flags[nnltc], 1 = row j is certified by ntg_batch_envelope_sos on this plan, 0 = no statement (the row is undeclared,
  * or it names outputs of different basis classes and has no common pieces).  No device call.
  * Pieces.  Pieces, npc and the range of nsub are exactly as in ntg_batch_envelope.  A row's pieces are those of the basis class of the
@@ -486,7 +489,7 @@ int ntg_batch_envelope_sos(const ntg_plan *p, int batch, const double *d_x, int 
  * Rows.  nrow = nltc + nnltc, the linear trajectory rows first: ntg_batch_check's numbering.  ntg_plan_extrema_rows: flags[nrow], no
  * device call.  A linear row has flag 1 when the outputs it names (non-zero ltc[i][v]) belong to one basis class; a row of zeros counts as
  * class 0 and has flag 1.  A nonlinear row has the flag ntg_plan_sos_rows gives it.  Loaded modules declare no sum of squares yet: their
- * linear rows are certified, their nonlinear rows are not.
+ * linear rows are certified, their nonlinear rows are not (ntg_batch_forms certifies a quadratic one, declared at the call).
  * Outputs, any may be NULL but not all six:
  *   d_ext     [batch][nrow][4]  {min_lo, min_hi, max_lo, max_hi}
  *   d_when    [batch][nrow][2]  {t_min, t_max}
@@ -612,6 +615,74 @@ int ntg_batch_separation(const ntg_plan *p, int batch, const double *d_x,
                          double tol, int max_depth,
                          double *d_min, double *d_when, int *d_status, int *d_npieces,
                          double *d_viol, void *stream);
+
+/* Certified extrema of QUADRATIC FORMS of the flat flag that the caller declares at the call: ntg_batch_extrema's statement -- the global
+ * minimum and maximum over the horizon, each enclosed to a tolerance and each with a witness time -- for functions that are not rows of the
+ * plan, or are rows its family cannot declare: weighted squares, bilinear terms, linear terms, on every plan (built-in families, loaded
+ * modules, per-problem grids).  The speed^2 of a kinematic car, its turning numerator x' y'' - y' x'', v . a, a weighted thrust limit, an
+ * elliptical keep-out zone, a nonlinear row of a module family.  On a knot interval every flag entry is a polynomial, so a quadratic form of
+ * the flag is one too, and its Bezier polygon follows from the entries' polygons by the Bezier product of two polygons.
+ * No family callback runs.
+ * Forms.  form_nterms [nform] and terms are HOST arrays, copied by the call; terms is concatenated form after form.  Form j is
+ *   q_j(z) = sum_t term_t,   term_t = w (z[u] - a)(z[v] - b) when v >= 0,   term_t = w (z[u] - a) when v == -1 (sv and pv are then ignored)
+ * with the shifts a = su + (pu >= 0 ? fprm_b[pu] : 0) and b = sv + (pv >= 0 ? fprm_b[pv] : 0).  u and v are flag entries iz[o] + r in the
+ * layout of ntg_batch_interp.  fprm_b is row b of d_fprm [batch][nfp]: the call's own per-problem parameters (an obstacle centre, a
+ * half-plane offset), not the family's, so ntg_plan_set_params is neither needed nor read.  All entries a form names must belong to one
+ * basis class; the form's pieces are that class's knot intervals, and different forms may use different classes.  A constant offset is the
+ * caller's business: it moves the bounds.  1 <= terms per form <= NTG_FORM_MAXTERMS, 0 <= nform <= NTG_FORM_MAXFORMS.
+ * Outputs, any may be NULL but not all six:
+ *   d_ext     [batch][nform][4]  {min_lo, min_hi, max_lo, max_hi}
+ *   d_when    [batch][nform][2]  {t_min, t_max}
+ *   d_status  [batch][nform]     NTG_EXTREMA_OK / _DEPTH / _FULL / _NAN
+ *   d_npieces [batch][nform]     polygons evaluated
+ *   d_viol    [batch][2]         {attained, certified}
+ *   d_where   [batch][2]         form of each of the two violations; ties to the smallest form; -1 where the figure is 0
+ * Definition, per problem and per form.
+ * 1. Level-0 polygon of form j on knot interval i of its class (after ntg_plan_set_grids: the problem's own intervals).  For each term, in
+ *    declared order:
+ *    a. Factors.  The control points beta of entry u come from steps 1-3 of ntg_batch_envelope at nsub = 0, with the same arithmetic as
+ *       ntg_batch_envelope_sos; the degree is d = k - 1 - r_u, and a derivative of order >= k is the single point 0 with d = 0.  Then
+ *       p_i = beta_i - a.  For v >= 0 the degree e and the points q_j of entry v come the same way with the shift b.
+ *    b. Product, degree d + e.  g_m = sum_{i + j = m} W_{d,e}[i][j] * p_i * q_j, i ascending, W_{d,e}[i][j] = C(d,i) C(e,j) / C(d+e, i+j):
+ *       the numerator is an exact integer product and the division is the one rounding (the binomials are at most C(18,9), so everything
+ *       is exact in double up to that division).  W_{d,d} is therefore bit-equal to the W_d of ntg_batch_envelope_sos.  A linear term has
+ *       g_i = p_i.
+ *    c. Squares.  A square term has v == u, pu == pv and su == sv bitwise; its product is formed exactly as ntg_batch_envelope_sos forms
+ *       a square.  A form whose terms are all squares with w == 1.0 then has the same level-0 polygon, bit for bit, as the equivalent
+ *       sum-of-squares row of ntg_batch_extrema.
+ *    d. Sum.  The term's polygon is w * g_m with one rounding; it is elevated to the form's degree D_j = max_t deg_t with the formula
+ *       ntg_batch_envelope states and added to the form's polygon, terms in declared order (the product and the sum are rounded separately).
+ *       D_j <= 2 (kmax - 1) <= 18.
+ * 2. Levels, results, NaN.  Steps 2 to 5 of ntg_batch_extrema's definition, unchanged: tol, max_depth, sides, NTG_EXTREMA_CAP and the
+ *    statuses keep their meaning; the times come from the form's class.  Every form is certified: there is no status NONE and no
+ *    partial-certificate refusal.
+ * 3. Violation.  Bounds d_flo / d_fhi [batch][nform]; a bound with |bound| >= NTG_INF_BOUND is absent.  attained and certified are the
+ *    maxima over the forms exactly as in rule 7 of ntg_batch_extrema; a form with both bounds absent contributes 0.  certified == 0
+ *    certifies every declared form over the whole horizon.
+ * Rounding.  With S_x = max_i |c_{o,i}| (2(k-1)/h_min)^r + |shift| for factor x, a factor's control point carries at most 2^-42 S_x.  The
+ * slack of a form is 2^-39 * sum_t |w_t| S_u S_v, with S_v = 1 for a linear term.
+ * Arguments.  tol, max_depth and sides as in ntg_batch_extrema.  Stream ordered, without scratch in HBM and without floating-point atomics:
+ * a wavefront owns a problem and walks its forms.  Results are bit-identical from call to call and independent of the batch around a
+ * problem.  Per-problem grids are honoured with the batch rule of ntg_batch_extrema: the batch must be the grids'.
+ * batch <= 0 or nform == 0 returns 0 after the null-plan and argument checks.  NTG_E_BADARG, naming the form and term where one is at fault,
+ * for a null plan, d_x, form_nterms or terms; nform outside 0 .. NTG_FORM_MAXFORMS; a form with 0 or more than NTG_FORM_MAXTERMS terms; u outside
+ * [0, nz) or v outside [-1, nz); pu or pv outside [-1, nfp); nfp < 0, or a parameter named while d_fprm is null; a non-finite w, su or sv;
+ * tol, max_depth or sides out of range; all six outputs null; violation outputs without both bounds; a batch other than the grids'.
+ * NTG_E_UNSUPPORTED for host-callback plans, for a form that names entries of different basis classes (the message names the form and the two
+ * outputs), and for tables and work lists above 158 KiB of LDS: 3025 product weights, sum over basis classes of l (k^2 + 2) + 1, and per
+ * wavefront of four nC + nfp + 64 (D_max + 2) doubles with D_max = 10 (largest order <= 6) or 18 -- on per-problem grids the class tables
+ * count per wavefront too. */
+#define NTG_FORM_MAXFORMS 8
+#define NTG_FORM_MAXTERMS 8      /* per form */
+typedef struct { int u, v, pu, pv; double w, su, sv; } ntg_form_term;
+
+int ntg_batch_forms(const ntg_plan *p, int batch, const double *d_x,
+                    int nform, const int *form_nterms, const ntg_form_term *terms,
+                    int nfp, const double *d_fprm,
+                    double tol, int max_depth, int sides,
+                    const double *d_flo, const double *d_fhi,
+                    double *d_ext, double *d_when, int *d_status, int *d_npieces,
+                    double *d_viol, int *d_where, void *stream);
 
 /* The flat-to-state map of the kinematic car for a whole ntg_batch_interp result (examples/kincar.c:68-92 kincar_flat_reverse,
  * called per sample by the example's output loop, kincar.c:392-406): d_z [batch][ntimes][nz] -> d_state [batch][ntimes][ncars][5] =

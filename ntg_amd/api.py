@@ -44,6 +44,11 @@ class SolveOpts(C.Structure):
                 ("hessian", C.c_int), ("fixed_iters", C.c_int), ("block_threads", C.c_int), ("qn_memory", C.c_int), ("warm_start", C.c_int)]
 
 
+class FormTerm(C.Structure):
+    """ntg_form_term: w (z[u] - a)(z[v] - b), or w (z[u] - a) when v == -1; a = su + fprm[pu], b = sv + fprm[pv] (index -1: no parameter)"""
+    _fields_ = [("u", C.c_int), ("v", C.c_int), ("pu", C.c_int), ("pv", C.c_int), ("w", C.c_double), ("su", C.c_double), ("sv", C.c_double)]
+
+
 _lib = None
 
 
@@ -86,6 +91,7 @@ def lib():
         L.ntg_batch_extrema.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_int] + [C.c_void_p] * 9
         L.ntg_plan_extrema_rows.argtypes = [C.c_void_p, ip]
         L.ntg_batch_separation.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int] + [C.c_void_p] * 6
+        L.ntg_batch_forms.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, ip, C.POINTER(FormTerm), C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_int] + [C.c_void_p] * 9
         L.ntg_batch_refine.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_plan_set_grids.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ntg_plan_clear_grids.argtypes = [C.c_void_p]
@@ -505,6 +511,39 @@ class Plan:
                                           self._stream()))
         return out
 
+    def forms(self, x, forms, tol, max_depth: int = 30, sides: int = 3, fprm=None, lower=None, upper=None):
+        """The minimum and maximum over the whole horizon of quadratic forms of the flat flag declared here, each enclosed to tol, by bisection
+        (ntg_batch_forms): x [batch, nC]; forms is a list of up to FORM_MAXFORMS forms, each a list of up to FORM_MAXTERMS terms (u, v, pu, pv,
+        w, su, sv) as the constructors of ntg_amd.forms return them: w (z[u] - a)(z[v] - b), or w (z[u] - a) for v == -1, with a = su +
+        fprm[b, pu] and b = sv + fprm[b, pv].  fprm [batch, nfp] (device) are the call's own per-problem parameters.  No family callback runs,
+        so every plan is served, loaded modules and per-problem grids included.  Returns a dict like extrema's: ext [batch, nform, 4] =
+        (min_lo, min_hi, max_lo, max_hi), when [batch, nform, 2], status and npieces [batch, nform] and, with the bounds lower / upper
+        [batch, nform] of the forms, viol [batch, 2] = (attained, certified) and where [batch, 2], the form of each or -1.
+        viol[:, 1] == 0 certifies every declared form over the whole horizon."""
+        import torch
+        sp, dev, batch = self._cert_inputs(x, None, None)
+        _check_tensor(fprm, dev); _check_tensor(lower, dev); _check_tensor(upper, dev)
+        forms = [list(f) for f in forms]
+        nform = len(forms)
+        if (lower is None) != (upper is None):
+            raise NtgError("pass both bounds or neither")
+        if lower is not None and (lower.shape != (batch, nform) or upper.shape != (batch, nform)):
+            raise NtgError(f"the forms' bounds must be [{batch}, {nform}]")
+        if fprm is not None and (fprm.dim() != 2 or fprm.shape[0] != batch):
+            raise NtgError(f"fprm must be [{batch}, nfp]")
+        nterms = (C.c_int * max(nform, 1))(*[len(f) for f in forms])
+        flat = [FormTerm(*t) for f in forms for t in f]
+        terms = (FormTerm * max(len(flat), 1))(*flat)
+        rows = max(nform, 1)   # (an empty declaration gets one form of storage: the library returns before it writes)
+        out = {"ext": torch.empty((batch, rows, 4), dtype=torch.float64, device=dev), "when": torch.empty((batch, rows, 2), dtype=torch.float64, device=dev),
+               "status": torch.empty((batch, rows), dtype=torch.int32, device=dev), "npieces": torch.empty((batch, rows), dtype=torch.int32, device=dev)}
+        if lower is not None:
+            out["viol"] = torch.zeros((batch, 2), dtype=torch.float64, device=dev); out["where"] = torch.full((batch, 2), -1, dtype=torch.int32, device=dev)
+        _check(lib().ntg_batch_forms(self.h, batch, _ptr(x), nform, nterms, terms, 0 if fprm is None else int(fprm.shape[1]), _ptr(fprm), float(tol), int(max_depth),
+                                     int(sides), _ptr(lower), _ptr(upper), _ptr(out["ext"]), _ptr(out["when"]), _ptr(out["status"]), _ptr(out["npieces"]),
+                                     _ptr(out.get("viol")), _ptr(out.get("where")), self._stream()))
+        return out
+
     def set_grids(self, knots, bps, with_precond: bool = True):
         """Per-problem grids: knots [batch, ninterv+1], bps [batch, nbps] (device, float64).  See ntg_plan_set_grids."""
         _check_tensor(knots, knots.device); _check_tensor(bps, bps.device)
@@ -615,6 +654,7 @@ ENVELOPE_MAX_NSUB = 6   # NTG_ENVELOPE_MAX_NSUB
 EXTREMA_MAX_DEPTH, EXTREMA_CAP = 30, 64   # NTG_EXTREMA_MAX_DEPTH, NTG_EXTREMA_CAP
 EXTREMA_OK, EXTREMA_DEPTH, EXTREMA_FULL, EXTREMA_NAN, EXTREMA_NONE = 0, 1, 2, 3, -1   # NTG_EXTREMA_* status codes
 SEP_MAXDIM, SEP_BADPAIR = 4, -2   # NTG_SEP_MAXDIM, NTG_SEP_BADPAIR
+FORM_MAXFORMS, FORM_MAXTERMS = 8, 8   # NTG_FORM_MAXFORMS, NTG_FORM_MAXTERMS
 
 
 def envelope_pieces(spec_or_knots, o: int = 0, nsub: int = 0) -> np.ndarray:

@@ -25,6 +25,8 @@
 //                   bisection of the same polygons from a work list in LDS (extrema.hpp)
 //   separation_kernel  smallest squared distance of pairs of bodies over the horizon: the squared
 //                   difference of two trajectories as a sum-of-squares row, by that bisection (separation.hpp)
+//   forms_*         minimum and maximum over the horizon of quadratic forms of the flag declared at the
+//                   call: general Bezier products of the polygons, by that bisection (forms.hpp)
 //
 // Mapping to CDNA4: one workgroup per problem; breakpoints (then coefficients) across the
 // lanes; basis tables, knots/breakpoints and the coefficient vector staged in LDS; the only
@@ -40,6 +42,7 @@
 #include "envelope_sos.hpp"
 #include "extrema.hpp"
 #include "separation.hpp"
+#include "forms.hpp"
 #include "kkt.hpp"
 #include "verify.hpp"
 
@@ -671,6 +674,14 @@ hipError_t ntg_launch_extrema(const ExtArgs &A, int ncu, hipStream_t st)
 	if (lds > NTG_EXTREMA_LDS_MAX || A.g.kmax > NTG_MAX_ORDER || A.sos.nrow > NTG_SOS_MAXROWS) return hipErrorInvalidValue;
 	if (A.g.batch <= 0) return hipSuccess;
 	return NTG_CERT_LAUNCH(extrema, NTG_EXTREMA_NT, (A.g.batch + NTG_EXTREMA_NT / 64 - 1) / (NTG_EXTREMA_NT / 64));
+}
+// ... and one of ntg_batch_forms likewise
+hipError_t ntg_launch_forms(const FormArgs &A, int ncu, hipStream_t st)
+{
+	const size_t lds = ntg_forms_lds(A);
+	if (lds > NTG_EXTREMA_LDS_MAX || A.g.kmax > NTG_MAX_ORDER || A.nform > NTG_FORM_MAXFORMS) return hipErrorInvalidValue;
+	if (A.g.batch <= 0 || A.nform <= 0) return hipSuccess;
+	return NTG_CERT_LAUNCH(forms, NTG_EXTREMA_NT, (A.g.batch + NTG_EXTREMA_NT / 64 - 1) / (NTG_EXTREMA_NT / 64));
 }
 #undef NTG_CERT_LAUNCH
 // ... and one of ntg_batch_separation a pass of four pairs.  Shared grids only: the entry point refuses per-problem grids, so there is no kpp

@@ -338,3 +338,39 @@ static inline size_t ntg_separation_lds(const SepArgs &A)
 	const size_t wave = (size_t)A.ndim * A.n + (size_t)NTG_EXTREMA_CAP * (ntg_separation_kd(A) + 1);
 	return ((size_t)NTG_SOS_WFULL + A.g.ne + A.g.lmax + 1 + (size_t)(NTG_EXTREMA_NT / 64) * wave) * 8;
 }
+
+// ntg_batch_forms (forms.hpp): the minimum and maximum over the horizon of quadratic forms of the flat flag that the CALLER declares, each a sum
+// of weighted products w (z[u] - a)(z[v] - b) and weighted linear terms w (z[u] - a).  term[f][t] in the kernels' form: the coefficient offsets
+// iCu / iCv of the two factors' outputs, their derivative orders ru / rv (the degrees follow from the class: max(k - 1 - r, 0)), the indices
+// pu / pv into the problem's row of fprm [batch][nfp] or -1, the kind, the weight w and the shifts' constants su / sv.  row[f]: nt terms, the
+// basis class cl of every entry the form names, the degree D of its polygon.  koff / nk as in ExtArgs.  flo / fhi [batch][nform] (null unless a
+// violation is asked for).  Outputs as documented at ntg_batch_forms, any may be null.
+#define NTG_FORM_LIN 0      // w (z[u] - a)
+#define NTG_FORM_PROD 1     // w (z[u] - a)(z[v] - b)
+#define NTG_FORM_SQUARE 2   // ... with the same entry, parameter and constant twice: formed as envelope_sos.hpp forms a square
+struct FormTerm { int iCu, iCv, pu, pv; short ru, rv, kind, pad; double w, su, sv; };
+struct FormRow { int nt, cl, D, pad; };
+struct FormArgs {
+	CertBase g;
+	int nform, nfp, max_depth, sides, nk, pad;
+	double tol;
+	int koff[NTG_MAX_OUT];
+	FormRow row[NTG_FORM_MAXFORMS];
+	FormTerm term[NTG_FORM_MAXFORMS][NTG_FORM_MAXTERMS];
+	const double *fprm, *flo, *fhi;
+	double *ext, *when, *viol; int *status, *npieces, *where;
+};
+static_assert(sizeof(FormArgs) <= 4096, "FormArgs travels as a kernel argument");
+// the product tables W_{d,e}[i][j] = C(d,i) C(e,j) / C(d+e,i+j) of every pair of degrees 0 <= d, e < NTG_MAX_ORDER, [d + 1][e + 1] each, e
+// fastest: doubles of all of them, and where the table of (d, e) starts
+#define NTG_FORM_WALL ((NTG_MAX_ORDER * (NTG_MAX_ORDER + 1) / 2) * (NTG_MAX_ORDER * (NTG_MAX_ORDER + 1) / 2))
+static inline __host__ __device__ int ntg_form_woff(int d, int e) { return (NTG_MAX_ORDER * (NTG_MAX_ORDER + 1) / 2) * (d * (d + 1) / 2) + (d + 1) * (e * (e + 1) / 2); }
+static inline int ntg_forms_kd(const FormArgs &A) { return A.g.kmax <= 6 ? 11 : 2 * NTG_MAX_ORDER - 1; }
+// dynamic LDS: the product tables (built on the device); the extraction tables and the breaks of every class; per wave one coefficient row, one
+// row of fprm, the work list and its keys.  Per-problem grids: every wave has extraction tables and breaks of its own.  The limit is
+// ntg_batch_extrema's (the static part is the Pascal triangle the product tables are built from)
+static inline size_t ntg_forms_lds(const FormArgs &A)
+{
+	const size_t wave = (size_t)A.g.nC + A.nfp + (size_t)NTG_EXTREMA_CAP * (ntg_forms_kd(A) + 1), tabs = (size_t)A.g.ne + A.nk;
+	return ((size_t)NTG_FORM_WALL + (A.g.pp ? 0 : tabs) + (size_t)(NTG_EXTREMA_NT / 64) * (wave + (A.g.pp ? tabs : 0))) * 8;
+}

@@ -1,10 +1,11 @@
 // plan_cert.cpp -- the time certificates behind include/ntg_amd.h: ntg_batch_envelope, ntg_batch_envelope_sos, ntg_batch_extrema,
-// ntg_batch_separation and the queries ntg_plan_sos_rows and ntg_plan_extrema_rows.  What they share comes first: the refusals (each call tests them between its own
+// ntg_batch_separation, ntg_batch_forms and the queries ntg_plan_sos_rows and ntg_plan_extrema_rows.  What they share comes first: the refusals (each call tests them between its own
 // argument checks, in its own order), which rows of a plan are certified -- a linear trajectory row whose outputs share a basis class, from
 // the host mirror of ltc; a nonlinear row by the family's sum-of-squares declaration, NtgFamily::sos, against the plan's iz / cls -- and the
 // three parts of the kernels' arguments (CertBase, CertLin, CertSos: ntg_dev.hpp).  An entry point then reads: its own argument checks,
-// the setup, its own fields, the launch.  The arithmetic is in envelope.hpp, envelope_sos.hpp, extrema.hpp and separation.hpp.  No family callback runs, so
+// the setup, its own fields, the launch.  The arithmetic is in envelope.hpp, envelope_sos.hpp, extrema.hpp, separation.hpp and forms.hpp.  No family callback runs, so
 // the calls serve every built-in family and every loaded module.  They allocate nothing.
+#include <cstring>
 #include "plan_priv.hpp"
 #include "family_module.hpp"
 
@@ -30,6 +31,14 @@ int cert_batch_size(const ntg_plan *p, int batch, bool with_prm)
 	if (p->grid_batch && batch != p->grid_batch) return fail(NTG_E_BADARG, "the plan carries per-problem grids for another batch size");
 	if (with_prm && p->prm_batch && batch != p->prm_batch)
 		return fail(NTG_E_BADARG, "the plan carries per-problem parameters for " + std::to_string(p->prm_batch) + " problems, not " + std::to_string(batch));
+	return 0;
+}
+// tol, max_depth and sides of the bisection calls
+int cert_levels(double tol, int max_depth, int sides)
+{
+	if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(NTG_E_BADARG, "tol must be finite and >= 0");
+	if (max_depth < 0 || max_depth > NTG_EXTREMA_MAX_DEPTH) return fail(NTG_E_BADARG, "max_depth must lie in 0 .. " + std::to_string(NTG_EXTREMA_MAX_DEPTH));
+	if (sides < 1 || sides > 3) return fail(NTG_E_BADARG, "sides must be 1 (minimum), 2 (maximum) or 3 (both)");
 	return 0;
 }
 int cert_nsub(int nsub)
@@ -82,6 +91,14 @@ SosPlanRow sos_plan_row(const ntg_plan *p, const NtgFamily *f, int j)
 	if (!ok) { R.row.nt = 0; R.row.D = 0; R.need_prm = false; return R; }
 	R.row.nt = nt; R.row.flag = 1;
 	return R;
+}
+
+// flag entry v of the plan as (output, derivative order); o < 0: the plan has no such entry
+struct FlagEntry { int o, r; };
+FlagEntry flag_entry(const NtgDims &D, int v)
+{
+	for (int q = 0; q < D.nout; q++) if (v >= D.iz[q] && v < D.iz[q] + D.d[q]) return {q, v - D.iz[q]};
+	return {-1, 0};
 }
 
 // C(n, r), exact: n <= 2 (NTG_MAX_ORDER - 1)
@@ -324,5 +341,67 @@ extern "C" int ntg_batch_separation(const ntg_plan *p, int batch, const double *
 	A.min = d_min; A.when = d_when; A.status = d_status; A.npieces = d_npieces; A.viol = d_viol;
 	HIPCHK(hipSetDevice(p->device));
 	HIPCHK(ntg_launch_separation(A, plan_ncu(p), (hipStream_t)stream));
+	return 0;
+}
+
+extern "C" int ntg_batch_forms(const ntg_plan *p, int batch, const double *d_x, int nform, const int *form_nterms, const ntg_form_term *terms, int nfp, const double *d_fprm,
+                               double tol, int max_depth, int sides, const double *d_flo, const double *d_fhi,
+                               double *d_ext, double *d_when, int *d_status, int *d_npieces, double *d_viol, int *d_where, void *stream)
+{
+	if (!p) return fail(NTG_E_BADARG, "null plan");
+	if (!d_x || !form_nterms || !terms) return fail(NTG_E_BADARG, "null argument");
+	if (nform < 0 || nform > NTG_FORM_MAXFORMS) return fail(NTG_E_BADARG, "nform must lie in 0 .. " + std::to_string(NTG_FORM_MAXFORMS));
+	if (nfp < 0) return fail(NTG_E_BADARG, "nfp must be >= 0");
+	if (int rc = cert_levels(tol, max_depth, sides)) return rc;
+	const NtgDims &D = p->D;
+	FormArgs A{};
+	int cross_form = -1, cross_a = -1, cross_b = -1;   // the first form that names two basis classes, and two outputs that show it
+	const ntg_form_term *q = terms;
+	for (int f = 0; f < nform; f++) {
+		const int nt = form_nterms[f];
+		const std::string fname = "form " + std::to_string(f);
+		if (nt < 1 || nt > NTG_FORM_MAXTERMS) return fail(NTG_E_BADARG, fname + " has " + std::to_string(nt) + " terms: 1 .. " + std::to_string(NTG_FORM_MAXTERMS) + " are taken");
+		FormRow &R = A.row[f];
+		int first = -1;
+		for (int t = 0; t < nt; t++, q++) {
+			const std::string tname = fname + ", term " + std::to_string(t);
+			const bool lin = q->v == -1;
+			if (q->u < 0 || q->u >= D.nz) return fail(NTG_E_BADARG, tname + ": u = " + std::to_string(q->u) + " is no flag entry of the plan (0 .. " + std::to_string(D.nz - 1) + ")");
+			if (q->v < -1 || q->v >= D.nz) return fail(NTG_E_BADARG, tname + ": v = " + std::to_string(q->v) + " is neither -1 nor a flag entry of the plan (0 .. " + std::to_string(D.nz - 1) + ")");
+			if (q->pu < -1 || q->pu >= nfp || (!lin && (q->pv < -1 || q->pv >= nfp)))
+				return fail(NTG_E_BADARG, tname + ": pu and pv must lie in -1 .. nfp - 1 = " + std::to_string(nfp - 1));
+			if ((q->pu >= 0 || (!lin && q->pv >= 0)) && !d_fprm) return fail(NTG_E_BADARG, tname + " names a parameter, but d_fprm is null");
+			if (!std::isfinite(q->w) || !std::isfinite(q->su) || (!lin && !std::isfinite(q->sv))) return fail(NTG_E_BADARG, tname + ": w, su and sv must be finite");
+			const FlagEntry eu = flag_entry(D, q->u), ev = lin ? eu : flag_entry(D, q->v);
+			if (first < 0) { first = eu.o; R.cl = D.cls[eu.o]; }
+			for (const int o : {eu.o, ev.o})
+				if (D.cls[o] != R.cl && cross_form < 0) { cross_form = f; cross_a = first; cross_b = o; }
+			const int du = std::max(D.order[eu.o] - 1 - eu.r, 0), dv = lin ? 0 : std::max(D.order[ev.o] - 1 - ev.r, 0);
+			R.D = std::max(R.D, du + dv);
+			FormTerm &T = A.term[f][t];
+			T.iCu = D.iC[eu.o]; T.ru = (short)eu.r; T.pu = q->pu; T.su = q->su; T.w = q->w;
+			T.iCv = lin ? 0 : D.iC[ev.o]; T.rv = (short)(lin ? 0 : ev.r); T.pv = lin ? -1 : q->pv; T.sv = lin ? 0.0 : q->sv;
+			T.kind = lin ? NTG_FORM_LIN : (q->v == q->u && q->pu == q->pv && std::memcmp(&q->su, &q->sv, sizeof(double)) == 0) ? NTG_FORM_SQUARE : NTG_FORM_PROD;
+		}
+		R.nt = nt;
+	}
+	const bool want_v = d_viol || d_where;
+	if (!d_ext && !d_when && !d_status && !d_npieces && !want_v)
+		return fail(NTG_E_BADARG, "no output asked for: pass d_ext, d_when, d_status, d_npieces, d_viol or d_where");
+	if (want_v && (!d_flo || !d_fhi)) return fail(NTG_E_BADARG, "d_viol / d_where need the bounds d_flo and d_fhi");
+	if (batch <= 0 || nform == 0) return 0;
+	if (int rc = cert_batch_size(p, batch, false)) return rc;
+	if (int rc = cert_host(p)) return rc;
+	if (cross_form >= 0)
+		return fail(NTG_E_UNSUPPORTED, "form " + std::to_string(cross_form) + " names outputs " + std::to_string(cross_a) + " and " + std::to_string(cross_b) +
+		                                   " of different basis classes: it has no common pieces");
+	cert_base(p, batch, d_x, nullptr, nullptr, A.g, A.koff, &A.nk);
+	A.nform = nform; A.nfp = nfp; A.max_depth = max_depth; A.sides = sides; A.tol = tol;
+	if (A.g.kmax > NTG_MAX_ORDER || ntg_forms_lds(A) > NTG_EXTREMA_LDS_MAX)
+		return fail(NTG_E_UNSUPPORTED, "the tables and work lists of this call exceed " + std::to_string(NTG_EXTREMA_LDS_MAX / 1024) + " KiB of LDS");
+	A.fprm = d_fprm; A.flo = d_flo; A.fhi = d_fhi;
+	A.ext = d_ext; A.when = d_when; A.status = d_status; A.npieces = d_npieces; A.viol = d_viol; A.where = d_where;
+	HIPCHK(hipSetDevice(p->device));
+	HIPCHK(ntg_launch_forms(A, plan_ncu(p), (hipStream_t)stream));
 	return 0;
 }
