@@ -13,6 +13,8 @@
 // scans.  Maxima with a total order on ties (the smaller key wins): no floating-point atomics, the result does not depend on the order
 // in which anything ran.
 #pragma once
+#include "families.hpp"
+#include "wave_ops.hpp"
 #include "time_tile.hpp"   // (for the launcher only: the kernel below has the tile's steps written out)
 
 // the (violation, key) maximum of two candidates; key < 0: no violation seen

@@ -10,6 +10,8 @@
 // the tiles of a problem through one partial per tile in HBM that cost_final_kernel (kernels.hip) adds in tile order.  No floating-point
 // atomics: the result does not depend on the order in which anything ran, nor on the batch around a problem.
 #pragma once
+#include "families.hpp"
+#include "wave_ops.hpp"
 #include "time_tile.hpp"
 
 template <int BIT>

@@ -28,7 +28,8 @@
 // plan's largest order), so nothing goes to the private segment.
 #pragma once
 #include <cmath>
-#include "solve_impl.hpp"
+#include "ntg_dev.hpp"
+#include "wave_ops.hpp"
 #include "refine.hpp"
 
 // the smaller / larger of the two; a NaN, once in, stays

@@ -1,12 +1,17 @@
 // eval_fast.hpp -- NPfunobj (ntg.c:274-335) for the shape the headline workload has, with nothing else in the kernel:
 // one basis class, a running cost only, its active variables = the derivative channels CHM of every output
 // (kincar: the second derivatives, examples/kincar.c:133-137), no constraints.  Same tables, same arithmetic and the
-// same summation orders as eval_kernel's general path (solve_impl.hpp) -- Z = M C (colloc.c:318-367), the cost functor,
+// same summation orders as eval_kernel's general path (eval.hpp) -- Z = M C (colloc.c:318-367), the cost functor,
 // the banded gradient (cost.c:117-134 regrouped by coefficient) and the trapezoid rule (integrator.c:21-24) -- but every
 // decision the general kernel takes at run time (masks, channels, rows, widths) is a template constant here, the
 // gradient goes straight from registers to HBM, and a problem costs two workgroup barriers.
 #pragma once
-#include "solve_impl.hpp"
+#include <algorithm>
+#include "ntg_dev.hpp"
+#include "families.hpp"
+#include "wave_ops.hpp"
+#include "newton.hpp"       // nwt_wave_sync
+#include "lds_tables.hpp"   // chm_count, ntg_chm_match
 
 struct FastEvalDims {
 	int P, nC, nco, W;          // breakpoints, coefficients, coefficients per output, column width (entries)

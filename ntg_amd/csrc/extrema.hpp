@@ -24,6 +24,7 @@
 // The levels themselves (ext_levels) take the row as a source of level-0 polygons and a threshold flag: ext_row hands them a row of the plan,
 // separation.hpp the squared difference of two trajectories, with its "not plo >= s2" in the opening rule.  There is one level loop.
 #pragma once
+#include "wave_ops.hpp"
 #include "envelope_sos.hpp"
 
 // (value, time) minimum / maximum: on equal values the smaller time; a NaN is never taken

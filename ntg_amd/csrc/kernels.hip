@@ -5,11 +5,10 @@
 //                   reference tree, algorithm from de Boor's PGS)
 //   linrows_kernel  banded rows of the linear-constraint matrix (constraints.c:198-261)
 //   bounds_kernel   bounds() (constraints.c:5-33)
-//   eval_kernel     NPfunobj + NPfuncon (ntg.c:274-371): Z = M C (colloc.c:318-367), cost and
-//                   constraint functors, banded gradient / Jacobian assembly (cost.c:38-139,
-//                   constraints.c:88-195, colloc.c:243-316), trapezoid quadrature (integrator.c)
-//   sqp_kernel      the npsol_() call of ntg.c:250: one workgroup owns one problem for the
-//                   whole solve (feasibility, projected inverse-BFGS, line search)
+//   host*_kernel    the evaluation of host-callback plans: Z = M C (compute_z, lds_tables.hpp) and the
+//                   banded gradient / quadrature pass (cost_phase2, eval.hpp) around functors run on the host
+//   (eval_kernel and sqp_kernel, the evaluation and the npsol_() call of ntg.c:250 for the compiled
+//   families, are instantiated per family in fam_*.hip from eval.hpp and sqp_kernel.hpp)
 //   check_kernel    trajectory rows of solved problems between the breakpoints (check.hpp; the
 //                   last step of its reduction, check_final_kernel, is here)
 //   cost_kernel     running cost of solved problems at arbitrary times, weighted sum per problem
@@ -35,7 +34,10 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <algorithm>
-#include "solve_impl.hpp"
+#include "linesearch.hpp"
+#include "nwt_map.hpp"
+#include "lds_tables.hpp"
+#include "eval.hpp"
 #include "family_module.hpp"
 #include "refine.hpp"
 #include "envelope.hpp"

@@ -18,7 +18,10 @@
 // Maxima only, every sum owned by one lane in a fixed order: no floating-point atomics, the result does not depend on the order in which
 // anything ran nor on the batch around a problem.  A NaN anywhere in a maximum's inputs stays in it (an audit must not lose one).
 #pragma once
-#include "solve_impl.hpp"
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include "ntg_dev.hpp"
+#include "wave_ops.hpp"
 
 // the larger of the two; a NaN, once in, stays
 __device__ __forceinline__ double kkt_max(double a, double b) { return (b > a || b != b) ? b : a; }

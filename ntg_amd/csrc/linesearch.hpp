@@ -8,6 +8,9 @@
 // (Nocedal & Wright alg. 3.5/3.6).  DESIGN.md §4 is the normative statement.
 #pragma once
 #include <math.h>
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+#endif
 #ifndef NTG_HD
 #ifdef __HIPCC__
 #define NTG_HD __host__ __device__ __forceinline__

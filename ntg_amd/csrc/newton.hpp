@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include "ntg_dev.hpp"
 #include "nwt_map.hpp"   // NWT_PANEL, NWT_STAGE and where everything of the mode lives
+#include "wave_ops.hpp"  // lds_sync, the wave sums
 
 #define NWT_PSTRIDE 17   // LDS row stride (doubles) of a 48 x 16 panel in operand order (nwt_to_operand: diagnostics, tests/tools_mfma.hip)
 #ifndef NWT_PIVOTS

@@ -125,6 +125,11 @@ struct NtgTables {
 __host__ __device__ constexpr int colp_words(int W) { return (W / 2 + 1 + 3) & ~3; }
 // zero doubles kept after the last weighted-gradient row: a column's W reads start at its first breakpoint and may run past P
 __host__ __device__ inline int ntg_dfz_tail(const NtgDims &D) { int w = 16; for (int c = 0; c < D.nclass; c++) w = D.cls_W[c] > w ? D.cls_W[c] : w; return w; }
+// shape tests shared by the per-family dispatchers
+static inline bool ntg_all_d(const NtgDims &D, int d) { for (int o = 0; o < D.nout; o++) if (D.d[o] != d) return false; return true; }
+// 0 unless a tuned instance may run: one basis class, nC within the lanes' slots, no linear inequality rows (those
+// are handled by the generic instances only)
+static inline int ntg_uniform_order(const NtgDims &D, int nt, int ept) { return (D.uniform && D.nC <= ept * nt && D.nI == 0) ? D.order[0] : 0; }
 
 // byte offsets into dynamic LDS, computed on the host (kernels.hip: make_layout)
 #define NTG_HRC_LDS 64   // quasi-Newton memories up to this many pairs keep the pair scalars (rho, c2) in LDS, when that costs no residency

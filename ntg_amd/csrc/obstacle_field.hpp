@@ -10,6 +10,7 @@
 #pragma once
 
 #if defined(__HIP__) || defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define NTG_OF_HD __host__ __device__ __forceinline__
 #else
 #define NTG_OF_HD inline

@@ -295,7 +295,7 @@ extern "C" int ntg_batch_mpc_run(const ntg_plan *p, int batch, int nsteps, int s
 	hipStream_t st = (hipStream_t)stream, own = nullptr;
 	if (!st) { HIPCHK(hipStreamCreateWithFlags(&own, hipStreamNonBlocking)); st = own; }   // the legacy default stream cannot be captured
 	// The FIRST solve is cold whatever the caller's options say: a warm start reads the multiplier estimates of the previous solve from
-	// d_work (solve_impl.hpp: `if (sp.warm) al_lam[j] = al_t[j]`), and before the first solve the workspace holds nothing of the kind.
+	// d_work (sqp_kernel.hpp: `if (sp.warm) al_lam[j] = al_t[j]`), and before the first solve the workspace holds nothing of the kind.
 	// The estimates it leaves are shifted with the horizon, so the captured / replayed steps start warm as asked.
 	ntg_solve_opts cold;
 	if (o) { cold = *o; cold.warm_start = 0; }

@@ -1,6 +1,6 @@
 // qpdual.hpp -- the dual active-set solve of the QP-based SQP step (ntg_solve_opts.hessian = 3), twice:
 //   qp_passive_solve       scalar code, host and device: the SPECIFICATION, and the subject of the host unit test (tests/drivers/qpdual_drv.cpp);
-//   qp_passive_solve_wave  what sqp_kernel runs (solve_impl.hpp): the same matrices, ratio test and drop rule by all lanes of the group's wave on
+//   qp_passive_solve_wave  what sqp_kernel runs (sqp_kernel.hpp): the same matrices, ratio test and drop rule by all lanes of the group's wave on
 //                          the group's slots in LDS (tests/drivers/qpwave_unit.hip runs both on the GPU: same passive set, same multipliers).
 // Their round bounds differ: 3 NTG_QP_MAXA + 8 rounds for the scalar routine, 3 QA + 8 (QA = the plan's slots per group, ntg_qp_maxa) for the
 // wave routine; every round but the last removes a slot, so neither bound is reached with a working set of at most QA slots.
@@ -16,6 +16,9 @@
 // sign change (slots leave) until the multipliers of all passive slots are positive.
 #pragma once
 #include <math.h>
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+#endif
 #ifndef NTG_HD
 #ifdef __HIPCC__
 #define NTG_HD __host__ __device__ __forceinline__

@@ -19,7 +19,15 @@
 //   * waves are persistent and take problems from an atomic queue (to-convergence batches have ragged iteration counts).
 // The read-only tables (per-interval basis values, trapezoid weights, the projector Q) are shared by the waves of a workgroup.
 #pragma once
-#include "solve_impl.hpp"
+#include <type_traits>
+#include "ntg_dev.hpp"
+#include "families.hpp"
+#include "linesearch.hpp"
+#include "wave_ops.hpp"
+#include "newton.hpp"
+#include "lds_tables.hpp"
+#include "eval.hpp"        // lin_slot
+#include "direction.hpp"   // ntg_d4
 
 namespace ntgw {
 
@@ -40,19 +48,10 @@ __device__ __forceinline__ void static_while(C &&c, F &&f)
 
 // value of the previous / next lane of the wavefront (DPP wave_shr:1 / wave_shl:1; lane 0 / lane 63 receive 0).  bound_ctrl: a lane whose
 // source is out of range (or disabled) reads 0 from the DPP unit itself -- the same value in the same lanes as an "old" operand of 0, without
-// the v_mov_b32 v, 0 that operand costs in front of every shift (solve_impl.hpp: dpp_rot)
-__device__ __forceinline__ double from_prev(double v)
-{
-	const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x138, 0xf, 0xf, true);
-	const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x138, 0xf, 0xf, true);
-	return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double from_next(double v)
-{
-	const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x130, 0xf, 0xf, true);
-	const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x130, 0xf, 0xf, true);
-	return __hiloint2double(hi, lo);
-}
+// the v_mov_b32 v, 0 that operand costs in front of every shift (wave_ops.hpp: dpp_perm)
+// (names for two instances of the one move, not functions around it: a call through them is a direct call of dpp_perm)
+constexpr auto from_prev = dpp_perm<0x138>;   // wave_shr:1
+constexpr auto from_next = dpp_perm<0x130>;   // wave_shl:1
 
 // The register allocator hands out accumulator registers from a0 upwards when the 256 architectural VGPRs run short (AV-class values:
 // load results, copies).  It cannot be told to keep out, so the chain starts at a[ABASE] -- a template parameter of the kernel, visible in
@@ -93,7 +92,7 @@ __device__ __forceinline__ double bcast(double v, int lane)
 	return __hiloint2double(hi, lo);
 }
 // sums of KV per-lane values over the wavefront, every lane receives all of them
-// FEW: the interleaved rotation / permlane form for one to three values (solve_impl.hpp: wave_sums_few).  Measured: it pays on the instances
+// FEW: the interleaved rotation / permlane form for one to three values (wave_ops.hpp: wave_sums_few).  Measured: it pays on the instances
 // with one wave per SIMD (headline -0.5 %) and costs the two-waves-per-SIMD instances dearly (preconditioned solves 0.151 -> 0.178 ms per
 // 4096), so those keep the row_shr / row_bcast chains.
 template <int KV, bool FEW = false>

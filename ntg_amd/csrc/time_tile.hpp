@@ -8,7 +8,9 @@
 // to 4 % in instructions), so it keeps its text and its code.  A change to the staging, the offsets or the flag belongs in both places.
 // On the host every such kernel, check_kernel included, is launched by tile_launch below; a family names its instances once (tile_launchers).
 #pragma once
-#include "solve_impl.hpp"
+#include <hip/hip_runtime.h>
+#include "ntg_dev.hpp"
+#include "families.hpp"
 
 // the dynamic LDS of a time-tile kernel (ntg_check_lds): table [sumkd][NT + 1], coefficient row [npad], offsets [nclass][NT]
 struct TileLds { double *tab, *x; int *off; };

@@ -24,6 +24,8 @@
 // butterfly over the 64 lanes (lane ^ 1, 2, 4, 8, 16, 32), the waves through LDS in index order and the tiles of a problem through one
 // partial per tile (verify_final_kernel, kernels.hip) give a result that does not depend on the order in which anything ran.
 #pragma once
+#include "families.hpp"
+#include "wave_ops.hpp"
 #include "time_tile.hpp"
 
 // candidate (ov, ok) against the best so far (bv, bk); the start is (0, -1): a value of 0 never enters, its place stays -1

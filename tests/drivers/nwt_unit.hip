@@ -6,7 +6,7 @@
 #include <cstdlib>
 #include <cmath>
 #include <vector>
-#include "../../ntg_amd/csrc/solve_impl.hpp"
+#include "../../ntg_amd/csrc/newton.hpp"
 
 __global__ void __launch_bounds__(64) unit_kernel(double *K, int ng, int hb, double *yio, int *fail, long long *cyc)
 {

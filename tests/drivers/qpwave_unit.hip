@@ -13,7 +13,8 @@
 #include <cmath>
 #include <algorithm>
 #include <vector>
-#include "../../ntg_amd/csrc/solve_impl.hpp"
+#include "../../ntg_amd/csrc/newton.hpp"      // nwt_wave_sync, and through nwt_map.hpp the routines of qpdual.hpp
+#include "../../ntg_amd/csrc/direction.hpp"   // lds_dp
 
 struct Input { int ns, qa; std::vector<double> S, jwg, rr, nu; std::vector<int> sgn; };
 

@@ -2,7 +2,7 @@
 A DPP move whose every lane has a source -- or whose lanes without one are to read 0 -- needs no "old" operand: with bound_ctrl the DPP
 unit supplies the 0 itself, and no v_mov_b32 v, 0 is issued in front of the move.
   * from_prev / from_next (solve_wave.hpp) shift by one lane: wave_shr:1 / wave_shl:1, lane 0 / lane 63 read 0.
-  * lane_xchg (solve_impl.hpp) exchanges inside a quad or a row: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_ror:8.
+  * lane_xchg (wave_ops.hpp) exchanges inside a quad or a row: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_ror:8.
   * The limits of tests/test_wave_sweep_isa.py hold as they were."""
 import re
 

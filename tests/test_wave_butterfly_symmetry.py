@@ -1,4 +1,4 @@
-"""The halving butterfly of solve_impl.hpp (wave_sum_many: halve_step over lane bits 1, 2, 4, 8, then xsum_rows over 16 and 32), restated
+"""The halving butterfly of wave_ops.hpp (wave_sum_many: halve_step over lane bits 1, 2, 4, 8, then xsum_rows over 16 and 32), restated
 in numpy over 64 lanes with every addition in the operand order the device code uses.  Every step forms "own + partner's", and the
 partner forms the same two numbers the other way round; an IEEE addition is commutative, so the total of a value is the same bit pattern
 whichever of the 16 positions it travels in, whatever travels in the other positions and however many positions are valid (KV).  Callers
