@@ -40,6 +40,8 @@
  *                        point: the closest approach of pairs of planned bodies over the horizon, enclosed to a tolerance, with its time
  *   ntg_batch_forms      nothing in the reference bounds a function of the flag between samples: the minimum and maximum over the horizon of quadratic
  *                        forms of the flag declared at the call (speed^2, the turning numerator, weighted thrust, ellipses, rows of a module)
+ *   ntg_batch_ratios     nothing in the reference bounds the steering angle between samples; examples/kincar.c:68-92 kincar_flat_reverse computes it
+ *                        per sample: the minimum and maximum over the horizon of ratios of products of such forms (curvature^2, lateral acceleration^2)
  *   ntg_batch_kincar_reverse  examples/kincar.c:68-92 kincar_flat_reverse (the example's flat-to-state map), for a batch
  *   ntg(), npsoloption(), linspace(), SplineInterp(), matrix helpers: see include/ntg.h
  */
@@ -683,6 +685,71 @@ int ntg_batch_forms(const ntg_plan *p, int batch, const double *d_x,
                     const double *d_flo, const double *d_fhi,
                     double *d_ext, double *d_when, int *d_status, int *d_npieces,
                     double *d_viol, int *d_where, void *stream);
+
+/* Certified extrema of RATIOS of products of quadratic forms of the flat flag: ntg_batch_forms' statement for
+ *   R_r(t) = prod_{a < nnum} q_{num[a]}(z(t)) / prod_{b < nden} q_{den[b]}(z(t)),
+ * the quantities the physical limits of a flat system are made of.  With S = x'^2 + y'^2 and T = x' y'' - y' x'' of a kinematic car: the squared
+ * curvature kappa^2 = T T / (S S S), hence the steering angle tan delta = L kappa that ntg_batch_kincar_reverse computes per sample; the squared
+ * lateral acceleration T T / S; the heading slope y' / x'.  On a knot interval let N = sum n_i B_i^D and Q = sum d_i B_i^D be the Bezier polygons
+ * of numerator and denominator at one degree D, with every d_i > 0.  Then N / Q = sum_i (n_i / d_i) (d_i B_i / sum_j d_j B_j) is a convex
+ * combination of the quotients n_i / d_i: min_i n_i / d_i <= N / Q <= max_i n_i / d_i on the piece, and the end quotients are attained values.
+ * De Casteljau halves both polygons, so ntg_batch_extrema's bisection applies to the pair.  No family callback runs.
+ * Forms are declared exactly as for ntg_batch_forms (form_nterms, terms, nfp, d_fprm: same arrays, same checks, same messages); they are the
+ * factors, none of them is certified by itself.  ratios [nratio] is a HOST array, copied by the call.  nnum == 0 is the numerator 1, nden == 0
+ * the denominator 1 (a product of forms, S S); an index may repeat (a power).  Every form a ratio names must belong to one basis class;
+ * different ratios may use different classes.  0 <= nratio <= NTG_RATIO_MAXRATIOS, 0 <= nnum, nden <= NTG_RATIO_MAXFACTORS, not both 0.
+ * Outputs as for ntg_batch_forms with the ratio in the place of the form: d_ext [batch][nratio][4], d_when [batch][nratio][2], d_status and
+ * d_npieces [batch][nratio], d_viol and d_where [batch][2]; any may be NULL but not all six.
+ * Definition, per problem and per ratio.
+ * 1. Level 0, knot interval j of the ratio's class.  The polygon F_f of every form named is step 1 of ntg_batch_forms, bit for bit.  The
+ *    numerator is the chain G = F_{num[0]}; G = G (x) F_{num[a]}, a ascending, with (x) the product rule 1b of ntg_batch_forms between the chain
+ *    so far (degree d) and the form (degree e): g_m = sum_{i + j = m} W_{d,e}[i][j] * G_i * F_j, i ascending, every product and every sum
+ *    rounded; W = C(d,i) C(e,j) / C(d+e,i+j), the numerator an exact integer (below 2^53: at most C(24,12)^2), the division its one rounding.
+ *    The denominator likewise.  An empty side is the single point 1.0.  The degrees are dN = sum D_f and dD = sum D_f; the lower side is
+ *    elevated to DR = max(dN, dD) with the formula ntg_batch_envelope states (a side of ones stays ones, bit for bit).
+ * 2. Piece.  A piece carries both polygons n_0 .. n_DR and d_0 .. d_DR.  A NaN in either marks the ratio as rule 5 of ntg_batch_extrema does
+ *    (status NTG_EXTREMA_NAN), before anything else.  Otherwise, if every d_i > 0: rho_i = n_i / d_i by one IEEE division, plo = min rho_i,
+ *    phi = max rho_i.  Otherwise plo = -inf and phi = +inf: the piece is open on every side asked for.
+ * 3. Ends.  An end with d > 0 contributes rho to U / V, with its time exactly as in rule 2 of ntg_batch_extrema.  An end with d <= 0 is never
+ *    taken and marks the ratio POLE: after the end-taking of the level that marked it the loop stops with status NTG_RATIO_POLE, ext =
+ *    (-inf, +inf, -inf, +inf), NaN times, and npieces the pairs formed so far.  NAN takes precedence over POLE.
+ * 4. Levels, results, statuses.  Rules 2 to 5 of ntg_batch_extrema otherwise: tol (absolute, in units of the ratio), max_depth, sides,
+ *    NTG_EXTREMA_CAP, the statuses OK / DEPTH / FULL.  Both polygons of an open piece are halved with 0.5 * (a + b).  npieces counts pairs.
+ *    A ratio {nnum = 1, nden = 0} therefore returns what ntg_batch_forms returns for its form, bit for bit, and S / S returns 1.0 four times.
+ * 5. Violation.  Rule 7 of ntg_batch_extrema with d_rlo / d_rhi [batch][nratio], the formulas as they stand: a POLE ratio with a bound present
+ *    gives certified = +inf and attained = 0.
+ * Rounding.  With M_f = sum_t |w_t| S_u S_v, a point of form f carries at most delta_f = 2^-39 M_f (ntg_batch_forms).  Let m_f = delta_f + the
+ * largest |point| of the level-0 polygons of form f over the problem's knot intervals.  (x) is a convex combination of products (the weights of
+ * a point sum to 1), elevation and halving are convex combinations, so the points of a side stay within prod m_f, the factors' errors reach a
+ * side as prod m_f * sum_f delta_f / m_f, and the roundings of at most 3 products (22 each), 24 elevations (3 each) and 30 halvings (24 each)
+ * add less than 2^-43 prod m_f:
+ *   eps_side = prod_f m_f * (sum_f delta_f / m_f + 2^-43)      (an empty side: 2^-43)
+ * and a quotient rho carries at most (eps_N + |rho| eps_D) / (d_min - eps_D), where d_min is the smallest denominator point of the pieces that
+ * produced the figure (the division's own rounding, 2^-53 |rho|, is inside: eps_D >= 2^-43 d_min).  A certificate is claimed only where d_min >
+ * eps_D.  The a-priori figure 2^-36 prod M_f per side is also true but of no use for a ratio: M_f bounds a derivative by its coefficients,
+ * 40 times the speed of the test cars, and kappa^2 has ten factors.
+ * Arguments.  tol, max_depth and sides as in ntg_batch_extrema.  Stream ordered, without scratch in HBM and without floating-point atomics: a
+ * wavefront owns a problem and walks its ratios, lane p owns pair p.  Results are bit-identical from call to call and independent of the batch
+ * around a problem.  Per-problem grids are honoured: the batch must be the grids'.
+ * batch <= 0 or nratio == 0 returns 0 after the checks.  The refusals of ntg_batch_forms apply unchanged.  NTG_E_BADARG, naming the ratio, for
+ * nratio outside 0 .. NTG_RATIO_MAXRATIOS, nnum or nden outside 0 .. NTG_RATIO_MAXFACTORS, both sides empty, a form index outside [0, nform).
+ * NTG_E_UNSUPPORTED, naming the ratio, for a side of degree above NTG_RATIO_MAXDEG (the message names the degree), for forms of different basis
+ * classes in one ratio (it names the two forms), and for tables and work lists above 158 KiB of LDS: 3025 product weights of the forms, the
+ * tables (d + 1)(e + 1) of the distinct pairs of degrees the chains use, the class tables of ntg_batch_forms, and per wavefront nC + nfp +
+ * 64 (2 KR + 1) doubles, KR = 13 where every DR <= 12 and the largest order is <= 6, else 25; four wavefronts, two where four do not fit. */
+#define NTG_RATIO_MAXRATIOS  4
+#define NTG_RATIO_MAXFACTORS 4      /* per side; repeat an index for a power */
+#define NTG_RATIO_MAXDEG     24     /* Bezier degree of either side: kappa^2 of an order-6 car is 24 */
+#define NTG_RATIO_POLE       4      /* status: the denominator was <= 0 at a time the bisection visited */
+typedef struct { int nnum, nden; int num[NTG_RATIO_MAXFACTORS], den[NTG_RATIO_MAXFACTORS]; } ntg_ratio;
+
+int ntg_batch_ratios(const ntg_plan *p, int batch, const double *d_x,
+                     int nform, const int *form_nterms, const ntg_form_term *terms, int nfp, const double *d_fprm,
+                     int nratio, const ntg_ratio *ratios,
+                     double tol, int max_depth, int sides,
+                     const double *d_rlo, const double *d_rhi,
+                     double *d_ext, double *d_when, int *d_status, int *d_npieces,
+                     double *d_viol, int *d_where, void *stream);
 
 /* The flat-to-state map of the kinematic car for a whole ntg_batch_interp result (examples/kincar.c:68-92 kincar_flat_reverse,
  * called per sample by the example's output loop, kincar.c:392-406): d_z [batch][ntimes][nz] -> d_state [batch][ntimes][ncars][5] =

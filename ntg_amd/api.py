@@ -49,6 +49,11 @@ class FormTerm(C.Structure):
     _fields_ = [("u", C.c_int), ("v", C.c_int), ("pu", C.c_int), ("pv", C.c_int), ("w", C.c_double), ("su", C.c_double), ("sv", C.c_double)]
 
 
+class Ratio(C.Structure):
+    """ntg_ratio: the product of the forms num[:nnum] over the product of the forms den[:nden]; an empty side is 1"""
+    _fields_ = [("nnum", C.c_int), ("nden", C.c_int), ("num", C.c_int * 4), ("den", C.c_int * 4)]
+
+
 _lib = None
 
 
@@ -92,6 +97,8 @@ def lib():
         L.ntg_plan_extrema_rows.argtypes = [C.c_void_p, ip]
         L.ntg_batch_separation.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int] + [C.c_void_p] * 6
         L.ntg_batch_forms.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, ip, C.POINTER(FormTerm), C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_int] + [C.c_void_p] * 9
+        L.ntg_batch_ratios.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, ip, C.POINTER(FormTerm), C.c_int, C.c_void_p, C.c_int, C.POINTER(Ratio), C.c_double, C.c_int,
+                                       C.c_int] + [C.c_void_p] * 9
         L.ntg_batch_refine.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_plan_set_grids.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ntg_plan_clear_grids.argtypes = [C.c_void_p]
@@ -544,6 +551,42 @@ class Plan:
                                      _ptr(out.get("viol")), _ptr(out.get("where")), self._stream()))
         return out
 
+    def ratios(self, x, forms, ratios, tol, max_depth: int = 30, sides: int = 3, fprm=None, lower=None, upper=None):
+        """The minimum and maximum over the whole horizon of ratios of products of quadratic forms of the flat flag, each enclosed to tol, by
+        bisection of pairs of polygons (ntg_batch_ratios): forms as for Plan.forms; ratios is a list of up to RATIO_MAXRATIOS pairs (num, den)
+        of lists of up to RATIO_MAXFACTORS form indices, as ntg_amd.forms.ratio returns them: the product of the forms num over the product of
+        the forms den (an empty list is 1, a repeated index a power).  Returns the dict of Plan.forms with the ratio in the place of the form;
+        status RATIO_POLE: the denominator was <= 0 at a time the bisection visited, no statement.  lower / upper [batch, nratio]."""
+        import torch
+        sp, dev, batch = self._cert_inputs(x, None, None)
+        _check_tensor(fprm, dev); _check_tensor(lower, dev); _check_tensor(upper, dev)
+        forms = [list(f) for f in forms]
+        ratios = [(list(n), list(d)) for n, d in ratios]
+        nform, nratio = len(forms), len(ratios)
+        if (lower is None) != (upper is None):
+            raise NtgError("pass both bounds or neither")
+        if lower is not None and (lower.shape != (batch, nratio) or upper.shape != (batch, nratio)):
+            raise NtgError(f"the ratios' bounds must be [{batch}, {nratio}]")
+        if fprm is not None and (fprm.dim() != 2 or fprm.shape[0] != batch):
+            raise NtgError(f"fprm must be [{batch}, nfp]")
+        for r, (n, d) in enumerate(ratios):
+            if len(n) > RATIO_MAXFACTORS or len(d) > RATIO_MAXFACTORS:
+                raise NtgError(f"ratio {r}: nnum and nden must lie in 0 .. {RATIO_MAXFACTORS}")
+        nterms = (C.c_int * max(nform, 1))(*[len(f) for f in forms])
+        flat = [FormTerm(*t) for f in forms for t in f]
+        terms = (FormTerm * max(len(flat), 1))(*flat)
+        pad = lambda v: (C.c_int * 4)(*(list(v) + [0] * (4 - len(v))))
+        rat = (Ratio * max(nratio, 1))(*[Ratio(len(n), len(d), pad(n), pad(d)) for n, d in ratios])
+        rows = max(nratio, 1)   # (an empty declaration gets one ratio of storage: the library returns before it writes)
+        out = {"ext": torch.empty((batch, rows, 4), dtype=torch.float64, device=dev), "when": torch.empty((batch, rows, 2), dtype=torch.float64, device=dev),
+               "status": torch.empty((batch, rows), dtype=torch.int32, device=dev), "npieces": torch.empty((batch, rows), dtype=torch.int32, device=dev)}
+        if lower is not None:
+            out["viol"] = torch.zeros((batch, 2), dtype=torch.float64, device=dev); out["where"] = torch.full((batch, 2), -1, dtype=torch.int32, device=dev)
+        _check(lib().ntg_batch_ratios(self.h, batch, _ptr(x), nform, nterms, terms, 0 if fprm is None else int(fprm.shape[1]), _ptr(fprm), nratio, rat, float(tol),
+                                      int(max_depth), int(sides), _ptr(lower), _ptr(upper), _ptr(out["ext"]), _ptr(out["when"]), _ptr(out["status"]), _ptr(out["npieces"]),
+                                      _ptr(out.get("viol")), _ptr(out.get("where")), self._stream()))
+        return out
+
     def set_grids(self, knots, bps, with_precond: bool = True):
         """Per-problem grids: knots [batch, ninterv+1], bps [batch, nbps] (device, float64).  See ntg_plan_set_grids."""
         _check_tensor(knots, knots.device); _check_tensor(bps, bps.device)
@@ -655,6 +698,7 @@ EXTREMA_MAX_DEPTH, EXTREMA_CAP = 30, 64   # NTG_EXTREMA_MAX_DEPTH, NTG_EXTREMA_C
 EXTREMA_OK, EXTREMA_DEPTH, EXTREMA_FULL, EXTREMA_NAN, EXTREMA_NONE = 0, 1, 2, 3, -1   # NTG_EXTREMA_* status codes
 SEP_MAXDIM, SEP_BADPAIR = 4, -2   # NTG_SEP_MAXDIM, NTG_SEP_BADPAIR
 FORM_MAXFORMS, FORM_MAXTERMS = 8, 8   # NTG_FORM_MAXFORMS, NTG_FORM_MAXTERMS
+RATIO_MAXRATIOS, RATIO_MAXFACTORS, RATIO_MAXDEG, RATIO_POLE = 4, 4, 24, 4   # NTG_RATIO_MAXRATIOS, _MAXFACTORS, _MAXDEG; status NTG_RATIO_POLE
 
 
 def envelope_pieces(spec_or_knots, o: int = 0, nsub: int = 0) -> np.ndarray:

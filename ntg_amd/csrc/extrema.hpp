@@ -22,7 +22,8 @@
 //   extrema_pp_kernel      per-problem grids: the same, with breaks and weights of the wave's own problem.
 // No scratch in HBM, no atomics, nothing depends on the batch around a problem.  Every private array is indexed by unrolled loop counters only.
 // The levels themselves (ext_levels) take the row as a source of level-0 polygons and a threshold flag: ext_row hands them a row of the plan,
-// separation.hpp the squared difference of two trajectories, with its "not plo >= s2" in the opening rule.  There is one level loop.
+// separation.hpp the squared difference of two trajectories, with its "not plo >= s2" in the opening rule.  There is one level loop here;
+// ratio_levels (ratios.hpp) is its twin on pairs of polygons, kept in step by hand: whoever edits ext_levels edits that one too.
 #pragma once
 #include "wave_ops.hpp"
 #include "envelope_sos.hpp"

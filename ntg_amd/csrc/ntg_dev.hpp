@@ -379,3 +379,29 @@ static inline size_t ntg_forms_lds(const FormArgs &A)
 	const size_t wave = (size_t)A.g.nC + A.nfp + (size_t)NTG_EXTREMA_CAP * (ntg_forms_kd(A) + 1), tabs = (size_t)A.g.ne + A.nk;
 	return ((size_t)NTG_FORM_WALL + (A.g.pp ? 0 : tabs) + (size_t)(NTG_EXTREMA_NT / 64) * (wave + (A.g.pp ? tabs : 0))) * 8;
 }
+
+// ntg_batch_ratios (ratios.hpp): the minimum and maximum over the horizon of ratios of products of the forms of a FormArgs, R = prod num /
+// prod den.  f: the forms exactly as ntg_batch_forms declares them (its outputs are the ratios' [batch][nratio] arrays, flo / fhi the ratios'
+// bounds).  r[q]: the forms of each side, the basis class cl of all of them, the degrees dN / dD of the sides and DR = max of both; pn / pd:
+// for factor a >= 1 of a side the index of the product table its step of the chain uses.  Table q: degrees pd [q] (the chain so far) and
+// pe [q] (the form), (pd + 1)(pe + 1) doubles at poff [q] of the npw doubles all tables have; the kernels build them.  kr: points of the
+// private polygons (13 or 25), nw: waves of a workgroup (4, or 2 where the work lists of four do not fit).
+#define NTG_RATIO_MAXPAIRS (2 * NTG_RATIO_MAXRATIOS * (NTG_RATIO_MAXFACTORS - 1))
+struct RatioRow { unsigned char nnum, nden, cl, dN, dD, DR, num[NTG_RATIO_MAXFACTORS], den[NTG_RATIO_MAXFACTORS], pn[NTG_RATIO_MAXFACTORS - 1], pd[NTG_RATIO_MAXFACTORS - 1]; };
+struct RatioArgs {
+	FormArgs f;
+	unsigned char nratio, npair, kr, nw;
+	unsigned short npw, pad;
+	RatioRow r[NTG_RATIO_MAXRATIOS];
+	unsigned char pd[NTG_RATIO_MAXPAIRS], pe[NTG_RATIO_MAXPAIRS];
+	unsigned short poff[NTG_RATIO_MAXPAIRS];
+};
+static_assert(sizeof(RatioArgs) <= 4096, "RatioArgs travels as a kernel argument");
+// dynamic LDS: the forms' product tables and the chains' (both built on the device); the extraction tables and the breaks of every class; per
+// wave one coefficient row, one row of fprm, the work list of NTG_EXTREMA_CAP pairs of polygons and its keys.  Per-problem grids: every wave
+// has extraction tables and breaks of its own.  The limit is ntg_batch_extrema's
+static inline size_t ntg_ratios_lds(const RatioArgs &A, int nw)
+{
+	const size_t wave = (size_t)A.f.g.nC + A.f.nfp + (size_t)NTG_EXTREMA_CAP * (2 * A.kr + 1), tabs = (size_t)A.f.g.ne + A.f.nk;
+	return ((size_t)NTG_FORM_WALL + A.npw + (A.f.g.pp ? 0 : tabs) + (size_t)nw * (wave + (A.f.g.pp ? tabs : 0))) * 8;
+}

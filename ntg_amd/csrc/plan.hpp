@@ -75,6 +75,8 @@ hipError_t ntg_launch_extrema(const ExtArgs &A, int ncu, hipStream_t st);
 hipError_t ntg_launch_separation(const SepArgs &A, int ncu, hipStream_t st);
 // minimum and maximum over the horizon of quadratic forms of the flag declared at the call, by the same bisection (forms.hpp)
 hipError_t ntg_launch_forms(const FormArgs &A, int ncu, hipStream_t st);
+// minimum and maximum over the horizon of ratios of products of such forms, by the same bisection on pairs of polygons (ratios.hpp)
+hipError_t ntg_launch_ratios(const RatioArgs &A, int ncu, hipStream_t st);
 // trajectory rows at arbitrary times (check.hpp): the family's check_kernel instance, then the maximum over a problem's time tiles
 hipError_t ntg_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a);
 hipError_t ntg_launch_check_final(int batch, int ntiles, int ntimes, const double *pviol, const long long *pkey, double *viol, int *where, hipStream_t st);

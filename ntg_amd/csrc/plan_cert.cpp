@@ -1,9 +1,9 @@
 // plan_cert.cpp -- the time certificates behind include/ntg_amd.h: ntg_batch_envelope, ntg_batch_envelope_sos, ntg_batch_extrema,
-// ntg_batch_separation, ntg_batch_forms and the queries ntg_plan_sos_rows and ntg_plan_extrema_rows.  What they share comes first: the refusals (each call tests them between its own
+// ntg_batch_separation, ntg_batch_forms, ntg_batch_ratios and the queries ntg_plan_sos_rows and ntg_plan_extrema_rows.  What they share comes first: the refusals (each call tests them between its own
 // argument checks, in its own order), which rows of a plan are certified -- a linear trajectory row whose outputs share a basis class, from
 // the host mirror of ltc; a nonlinear row by the family's sum-of-squares declaration, NtgFamily::sos, against the plan's iz / cls -- and the
 // three parts of the kernels' arguments (CertBase, CertLin, CertSos: ntg_dev.hpp).  An entry point then reads: its own argument checks,
-// the setup, its own fields, the launch.  The arithmetic is in envelope.hpp, envelope_sos.hpp, extrema.hpp, separation.hpp and forms.hpp.  No family callback runs, so
+// the setup, its own fields, the launch.  The arithmetic is in envelope.hpp, envelope_sos.hpp, extrema.hpp, separation.hpp, forms.hpp and ratios.hpp.  No family callback runs, so
 // the calls serve every built-in family and every loaded module.  They allocate nothing.
 #include <cstring>
 #include "plan_priv.hpp"
@@ -344,9 +344,13 @@ extern "C" int ntg_batch_separation(const ntg_plan *p, int batch, const double *
 	return 0;
 }
 
-extern "C" int ntg_batch_forms(const ntg_plan *p, int batch, const double *d_x, int nform, const int *form_nterms, const ntg_form_term *terms, int nfp, const double *d_fprm,
-                               double tol, int max_depth, int sides, const double *d_flo, const double *d_fhi,
-                               double *d_ext, double *d_when, int *d_status, int *d_npieces, double *d_viol, int *d_where, void *stream)
+// ---------------- forms declared at the call (ntg_batch_forms, ntg_batch_ratios) ----------------
+namespace {
+// the first form that names two basis classes, and two outputs that show it
+struct FormCross { int form = -1, a = -1, b = -1; };
+// the arguments that declare the forms, checked in ntg_batch_forms' order, and the forms in the kernels' form (A.row, A.term)
+int forms_declare(const ntg_plan *p, const double *d_x, int nform, const int *form_nterms, const ntg_form_term *terms, int nfp, const double *d_fprm,
+                  double tol, int max_depth, int sides, FormArgs &A, FormCross &X)
 {
 	if (!p) return fail(NTG_E_BADARG, "null plan");
 	if (!d_x || !form_nterms || !terms) return fail(NTG_E_BADARG, "null argument");
@@ -354,8 +358,6 @@ extern "C" int ntg_batch_forms(const ntg_plan *p, int batch, const double *d_x, 
 	if (nfp < 0) return fail(NTG_E_BADARG, "nfp must be >= 0");
 	if (int rc = cert_levels(tol, max_depth, sides)) return rc;
 	const NtgDims &D = p->D;
-	FormArgs A{};
-	int cross_form = -1, cross_a = -1, cross_b = -1;   // the first form that names two basis classes, and two outputs that show it
 	const ntg_form_term *q = terms;
 	for (int f = 0; f < nform; f++) {
 		const int nt = form_nterms[f];
@@ -375,7 +377,7 @@ extern "C" int ntg_batch_forms(const ntg_plan *p, int batch, const double *d_x, 
 			const FlagEntry eu = flag_entry(D, q->u), ev = lin ? eu : flag_entry(D, q->v);
 			if (first < 0) { first = eu.o; R.cl = D.cls[eu.o]; }
 			for (const int o : {eu.o, ev.o})
-				if (D.cls[o] != R.cl && cross_form < 0) { cross_form = f; cross_a = first; cross_b = o; }
+				if (D.cls[o] != R.cl && X.form < 0) { X.form = f; X.a = first; X.b = o; }
 			const int du = std::max(D.order[eu.o] - 1 - eu.r, 0), dv = lin ? 0 : std::max(D.order[ev.o] - 1 - ev.r, 0);
 			R.D = std::max(R.D, du + dv);
 			FormTerm &T = A.term[f][t];
@@ -385,23 +387,125 @@ extern "C" int ntg_batch_forms(const ntg_plan *p, int batch, const double *d_x, 
 		}
 		R.nt = nt;
 	}
+	return 0;
+}
+// the outputs: one of them, and both bounds (named lo and hi in the message) where a violation is asked for
+int forms_outputs(const double *d_lo, const double *d_hi, const char *lo, const char *hi, double *d_ext, double *d_when, int *d_status, int *d_npieces, double *d_viol, int *d_where)
+{
 	const bool want_v = d_viol || d_where;
 	if (!d_ext && !d_when && !d_status && !d_npieces && !want_v)
 		return fail(NTG_E_BADARG, "no output asked for: pass d_ext, d_when, d_status, d_npieces, d_viol or d_where");
-	if (want_v && (!d_flo || !d_fhi)) return fail(NTG_E_BADARG, "d_viol / d_where need the bounds d_flo and d_fhi");
-	if (batch <= 0 || nform == 0) return 0;
+	if (want_v && (!d_lo || !d_hi)) return fail(NTG_E_BADARG, std::string("d_viol / d_where need the bounds ") + lo + " and " + hi);
+	return 0;
+}
+// what a non-empty call refuses about the plan and the forms
+int forms_refuse(const ntg_plan *p, int batch, const FormCross &X)
+{
 	if (int rc = cert_batch_size(p, batch, false)) return rc;
 	if (int rc = cert_host(p)) return rc;
-	if (cross_form >= 0)
-		return fail(NTG_E_UNSUPPORTED, "form " + std::to_string(cross_form) + " names outputs " + std::to_string(cross_a) + " and " + std::to_string(cross_b) +
+	if (X.form >= 0)
+		return fail(NTG_E_UNSUPPORTED, "form " + std::to_string(X.form) + " names outputs " + std::to_string(X.a) + " and " + std::to_string(X.b) +
 		                                   " of different basis classes: it has no common pieces");
+	return 0;
+}
+// the kernels' arguments but the launch figures
+void forms_args(const ntg_plan *p, int batch, const double *d_x, int nform, int nfp, double tol, int max_depth, int sides, FormArgs &A)
+{
 	cert_base(p, batch, d_x, nullptr, nullptr, A.g, A.koff, &A.nk);
 	A.nform = nform; A.nfp = nfp; A.max_depth = max_depth; A.sides = sides; A.tol = tol;
+}
+}   // namespace
+
+extern "C" int ntg_batch_forms(const ntg_plan *p, int batch, const double *d_x, int nform, const int *form_nterms, const ntg_form_term *terms, int nfp, const double *d_fprm,
+                               double tol, int max_depth, int sides, const double *d_flo, const double *d_fhi,
+                               double *d_ext, double *d_when, int *d_status, int *d_npieces, double *d_viol, int *d_where, void *stream)
+{
+	FormArgs A{};
+	FormCross X;
+	if (int rc = forms_declare(p, d_x, nform, form_nterms, terms, nfp, d_fprm, tol, max_depth, sides, A, X)) return rc;
+	if (int rc = forms_outputs(d_flo, d_fhi, "d_flo", "d_fhi", d_ext, d_when, d_status, d_npieces, d_viol, d_where)) return rc;
+	if (batch <= 0 || nform == 0) return 0;
+	if (int rc = forms_refuse(p, batch, X)) return rc;
+	forms_args(p, batch, d_x, nform, nfp, tol, max_depth, sides, A);
 	if (A.g.kmax > NTG_MAX_ORDER || ntg_forms_lds(A) > NTG_EXTREMA_LDS_MAX)
 		return fail(NTG_E_UNSUPPORTED, "the tables and work lists of this call exceed " + std::to_string(NTG_EXTREMA_LDS_MAX / 1024) + " KiB of LDS");
 	A.fprm = d_fprm; A.flo = d_flo; A.fhi = d_fhi;
 	A.ext = d_ext; A.when = d_when; A.status = d_status; A.npieces = d_npieces; A.viol = d_viol; A.where = d_where;
 	HIPCHK(hipSetDevice(p->device));
 	HIPCHK(ntg_launch_forms(A, plan_ncu(p), (hipStream_t)stream));
+	return 0;
+}
+
+extern "C" int ntg_batch_ratios(const ntg_plan *p, int batch, const double *d_x, int nform, const int *form_nterms, const ntg_form_term *terms, int nfp, const double *d_fprm,
+                                int nratio, const ntg_ratio *ratios, double tol, int max_depth, int sides, const double *d_rlo, const double *d_rhi,
+                                double *d_ext, double *d_when, int *d_status, int *d_npieces, double *d_viol, int *d_where, void *stream)
+{
+	RatioArgs A{};
+	FormCross X;
+	if (int rc = forms_declare(p, d_x, nform, form_nterms, terms, nfp, d_fprm, tol, max_depth, sides, A.f, X)) return rc;
+	if (nratio < 0 || nratio > NTG_RATIO_MAXRATIOS) return fail(NTG_E_BADARG, "nratio must lie in 0 .. " + std::to_string(NTG_RATIO_MAXRATIOS));
+	if (nratio > 0 && !ratios) return fail(NTG_E_BADARG, "null argument");
+	for (int r = 0; r < nratio; r++) {
+		const ntg_ratio &Q = ratios[r];
+		const std::string rname = "ratio " + std::to_string(r);
+		if (Q.nnum < 0 || Q.nnum > NTG_RATIO_MAXFACTORS || Q.nden < 0 || Q.nden > NTG_RATIO_MAXFACTORS)
+			return fail(NTG_E_BADARG, rname + ": nnum and nden must lie in 0 .. " + std::to_string(NTG_RATIO_MAXFACTORS));
+		if (Q.nnum + Q.nden == 0) return fail(NTG_E_BADARG, rname + " has both sides empty");
+		for (int a = 0; a < Q.nnum + Q.nden; a++) {
+			const int f = a < Q.nnum ? Q.num[a] : Q.den[a - Q.nnum];
+			if (f < 0 || f >= nform)
+				return fail(NTG_E_BADARG, rname + " names form " + std::to_string(f) + ": the call declares forms 0 .. " + std::to_string(nform - 1));
+		}
+	}
+	if (int rc = forms_outputs(d_rlo, d_rhi, "d_rlo", "d_rhi", d_ext, d_when, d_status, d_npieces, d_viol, d_where)) return rc;
+	if (batch <= 0 || nratio == 0) return 0;
+	if (int rc = forms_refuse(p, batch, X)) return rc;
+	int dmax = 0;
+	for (int r = 0; r < nratio; r++) {   // the sides' degrees, the one class, and the product tables the chains use
+		const ntg_ratio &Q = ratios[r];
+		RatioRow &R = A.r[r];
+		const std::string rname = "ratio " + std::to_string(r);
+		int deg[2] = {0, 0}, first = -1;
+		for (int side = 0; side < 2; side++) {
+			const int nf = side ? Q.nden : Q.nnum;
+			for (int a = 0; a < nf; a++) {
+				const int f = side ? Q.den[a] : Q.num[a];
+				(side ? R.den : R.num)[a] = (unsigned char)f;
+				if (first < 0) first = f;
+				else if (A.f.row[f].cl != A.f.row[first].cl)
+					return fail(NTG_E_UNSUPPORTED, rname + " names forms " + std::to_string(first) + " and " + std::to_string(f) + " of different basis classes: it has no common pieces");
+				deg[side] += A.f.row[f].D;
+			}
+			if (deg[side] > NTG_RATIO_MAXDEG)
+				return fail(NTG_E_UNSUPPORTED, rname + ": its " + (side ? "denominator" : "numerator") + " has degree " + std::to_string(deg[side]) + ", above " + std::to_string(NTG_RATIO_MAXDEG));
+		}
+		for (int side = 0; side < 2; side++) {
+			const int nf = side ? Q.nden : Q.nnum;
+			int d = 0;
+			for (int a = 0; a < nf; a++) {
+				const int e = A.f.row[side ? Q.den[a] : Q.num[a]].D;
+				if (a > 0) {
+					int q = 0;
+					while (q < A.npair && (A.pd[q] != d || A.pe[q] != e)) q++;
+					if (q == A.npair) { A.pd[q] = (unsigned char)d; A.pe[q] = (unsigned char)e; A.poff[q] = A.npw; A.npw = (unsigned short)(A.npw + (d + 1) * (e + 1)); A.npair++; }
+					(side ? R.pd : R.pn)[a - 1] = (unsigned char)q;
+				}
+				d += e;
+			}
+		}
+		R.nnum = (unsigned char)Q.nnum; R.nden = (unsigned char)Q.nden; R.cl = (unsigned char)A.f.row[first].cl;
+		R.dN = (unsigned char)deg[0]; R.dD = (unsigned char)deg[1]; R.DR = (unsigned char)std::max(deg[0], deg[1]);
+		dmax = std::max(dmax, (int)R.DR);
+	}
+	forms_args(p, batch, d_x, nform, nfp, tol, max_depth, sides, A.f);
+	A.nratio = (unsigned char)nratio;
+	A.kr = (unsigned char)(dmax <= 12 && A.f.g.kmax <= 6 ? 13 : 25);
+	A.nw = (unsigned char)(ntg_ratios_lds(A, 4) <= NTG_EXTREMA_LDS_MAX ? 4 : 2);
+	if (A.f.g.kmax > NTG_MAX_ORDER || ntg_ratios_lds(A, A.nw) > NTG_EXTREMA_LDS_MAX)
+		return fail(NTG_E_UNSUPPORTED, "the tables and work lists of this call exceed " + std::to_string(NTG_EXTREMA_LDS_MAX / 1024) + " KiB of LDS");
+	A.f.fprm = d_fprm; A.f.flo = d_rlo; A.f.fhi = d_rhi;
+	A.f.ext = d_ext; A.f.when = d_when; A.f.status = d_status; A.f.npieces = d_npieces; A.f.viol = d_viol; A.f.where = d_where;
+	HIPCHK(hipSetDevice(p->device));
+	HIPCHK(ntg_launch_ratios(A, plan_ncu(p), (hipStream_t)stream));
 	return 0;
 }

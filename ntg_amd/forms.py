@@ -10,6 +10,12 @@ A form is a list of Term; the constructors return such lists, and `+` concatenat
 
 A term is w (z[u] - a)(z[v] - b), or w (z[u] - a) when v == -1, with a = su + fprm[pu] and b = sv + fprm[pv] (a parameter index of -1 reads
 none): include/ntg_amd.h has the definition.
+
+Plan.ratios (ntg_batch_ratios) certifies ratios of products of such forms; a ratio is a pair (num, den) of lists of form indices:
+
+    forms, kappa2 = fm.curvature2(spec, (0, 1))            # [speed2, cross], ([1, 1], [0, 0, 0]): T T / (S S S)
+    out = plan.ratios(x, forms, [kappa2], tol=1e-9)
+    tan_max = fm.steering_tan_max(out, wheelbase=3.0)      # certified max |tan delta| per problem
 """
 from __future__ import annotations
 
@@ -20,6 +26,8 @@ import numpy as np
 
 MAXFORMS = 8   # NTG_FORM_MAXFORMS
 MAXTERMS = 8   # NTG_FORM_MAXTERMS, per form
+MAXRATIOS = 4     # NTG_RATIO_MAXRATIOS
+MAXFACTORS = 4    # NTG_RATIO_MAXFACTORS, per side of a ratio
 
 
 class Term(NamedTuple):
@@ -84,3 +92,39 @@ def steering_bound(ext, wheelbase: float, speed_form: int = 0, cross_form: int =
     ok = m > 0.0
     out[ok] = wheelbase * n[ok] / m[ok] ** 1.5
     return out
+
+
+def ratio(num: Sequence[int], den: Sequence[int] = ()) -> tuple:
+    """the product of the forms num over the product of the forms den (indices into the call's list of forms; an empty side is 1, a repeated
+    index a power)"""
+    num, den = [int(f) for f in num], [int(f) for f in den]
+    if not num and not den:
+        raise ValueError("a ratio needs a form on one side at least")
+    if len(num) > MAXFACTORS or len(den) > MAXFACTORS:
+        raise ValueError(f"a side of a ratio takes up to {MAXFACTORS} forms")
+    return num, den
+
+
+def curvature2(spec, outs: Sequence[int]) -> tuple:
+    """(forms, ratio) of the squared curvature kappa^2 = T T / (S S S) of the planar body with coordinates outs = (ox, oy): forms =
+    [S, T] = [speed2, cross], to be passed first in the call's list of forms (or shift the ratio's indices)"""
+    ox, oy = outs
+    return [speed2(spec, (ox, oy)), cross(spec, (ox, 1), (oy, 1))], ratio([1, 1], [0, 0, 0])
+
+
+def lateral_accel2(spec, outs: Sequence[int]) -> tuple:
+    """(forms, ratio) of the squared lateral acceleration (v^2 kappa)^2 = T T / S, forms = [S, T] as in curvature2"""
+    ox, oy = outs
+    return [speed2(spec, (ox, oy)), cross(spec, (ox, 1), (oy, 1))], ratio([1, 1], [0])
+
+
+def steering_tan_max(out, wheelbase: float, ratio_index: int = 0) -> np.ndarray:
+    """Certified largest |tan delta| = wheelbase |kappa| of the kinematic car over the whole horizon, from Plan.ratios' result `out` whose
+    ratio ratio_index is curvature2: wheelbase sqrt(max_hi).  Returns [batch]; inf where the status is not OK (a pole of the flat map at
+    v = 0, NaN, or a bisection that stopped early: no statement)."""
+    get = lambda k: out[k].detach().cpu().numpy() if hasattr(out[k], "detach") else np.asarray(out[k])
+    hi, st = get("ext")[:, ratio_index, 3].astype(np.float64), get("status")[:, ratio_index]
+    res = np.full(hi.shape[0], math.inf)
+    ok = (st == 0) & (hi >= 0.0)
+    res[ok] = wheelbase * np.sqrt(hi[ok])
+    return res
