@@ -211,6 +211,16 @@ def cases():
     E8 = cf.config_E(ninterv=8, narms=2); loE, upE = cf.manipulator_bounds(1, narms=2)
     yield "D8", D8, rng.normal(size=(2, D8.nC)) * 2, loD, upD
     yield "E8", E8, rng.normal(size=(2, E8.nC)), loE, upE
+    # shared grids with uneven knots and 3 .. 6 breakpoints per knot interval (tests/uneven_grids.py): new draws AFTER all of the above
+    import uneven_grids as ug
+    U20 = ug.FIXTURES["U20"](); loU, upU = cf.kincar_random_bounds(3, 1)
+    U16 = ug.FIXTURES["U16"](); loV, upV = cf.kincar_random_bounds(2, 1)
+    UO = ug.FIXTURES["UO"](); loO, upO = cf.obstacle_bounds(1)
+    UD8 = ug.FIXTURES["UD8"](); loD, upD = cf.quadrotor_bounds(1)
+    yield "U20", U20, rng.normal(size=(2, U20.nC)) * 5, loU, upU
+    yield "U16", U16, rng.normal(size=(2, U16.nC)) * 5, loV, upV
+    yield "UO", UO, rng.normal(size=(2, UO.nC)) * 5, loO, upO
+    yield "UD8", UD8, rng.normal(size=(2, UD8.nC)) * 2, loD, upD
 
 
 def main():

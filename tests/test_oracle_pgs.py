@@ -12,6 +12,7 @@ import scipy.interpolate as si
 import orc
 from ntg_amd import configs as cf
 from ntg_amd.spec import linspace_c
+import uneven_grids as ug
 
 dp = C.POINTER(C.c_double)
 
@@ -67,7 +68,11 @@ def test_vanderpol_end_blocks_closed_form():
     np.testing.assert_allclose(b1, ref1, rtol=0, atol=1e-14)
 
 
-@pytest.mark.parametrize("spec", [cf.config_A(), cf.config_K0(), cf.config_B(), cf.config_T()], ids=lambda s: s.name)
+# uneven knots with 0 .. 7 breakpoints per knot interval (tests/uneven_grids.py): first breakpoints on knots, one an ulp below a knot
+UNEVEN = [ug.kincar(3, "C20"), ug.kincar(2, "C16"), ug.kincar(1, "C20_7"), ug.kincar(1, "C20_0"), ug.O20(), ug.D8(), ug.E8()]
+
+
+@pytest.mark.parametrize("spec", [cf.config_A(), cf.config_K0(), cf.config_B(), cf.config_T()] + UNEVEN, ids=lambda s: s.name)
 def test_blocks_vs_scipy_and_structure(spec):
     tab = orc.export_tables(spec)
     pos = 0
