@@ -107,8 +107,51 @@ def rows_ptr(mat):
     return ptrs, mat
 
 
+def run_reference_tables(L, spec, x, lowerb, upperb):
+    """The reference functions that take no callbacks, for a spec whose callbacks live in a test driver (family < 0, tests/hostpath_cases.py):
+    LinearConstraintsMatrix, bounds, and updateZ for each of the six active-variable lists on a fresh Z.  With unequal maxderiv this
+    pins iZ, iz and iC (colloc.c:41-49) to the reference's own code."""
+    tables = orc.export_tables(spec)
+    rp = RefProblem(L, spec, tables)
+    cc = C.byref(rp.cc)
+    n, P, nz = spec.nC, spec.nbps, spec.nz
+    out = dict(blk=tables["blk"], off=tables["off"], x=x)
+    A = L.MakeFMatrix(spec.nclin, n)
+    keep = []
+
+    def fm(mat):
+        ptrs, m = rows_ptr(mat)
+        keep.append((ptrs, m))
+        return FMatrix(ptrs, nz, mat.shape[0])
+    mi, mt, mf = fm(spec.lic), fm(spec.ltc), fm(spec.lfc)
+    L.LinearConstraintsMatrix(A, C.byref(mi), C.byref(mt), C.byref(mf), cc)
+    out["A"] = np.array([[A.contents.elements[c][r] for c in range(n)] for r in range(spec.nclin)])
+    ntot = n + spec.nclin + spec.ncnln
+    DBL_MAX = np.finfo(np.float64).max
+    bl = np.zeros(ntot); bu = np.zeros(ntot)
+    lo0 = np.ascontiguousarray(lowerb[0]); up0 = np.ascontiguousarray(upperb[0])
+    args = (n, spec.nlic, spec.nltc, spec.nlfc, spec.nnlic, spec.nnltc, spec.nnlfc, P)
+    L.bounds(bu.ctypes.data_as(dp), up0.ctypes.data_as(dp), *args, C.c_double(DBL_MAX))
+    L.bounds(bl.ctypes.data_as(dp), lo0.ctypes.data_as(dp), *args, C.c_double(-DBL_MAX))
+    out.update(bl=bl, bu=bu)
+    Zl = []
+    for b in range(x.shape[0]):
+        xb = np.ascontiguousarray(x[b])
+        per = []
+        for nm, typ in (("icav", 0), ("tcav", 1), ("fcav", 2), ("icostav", 0), ("tcostav", 1), ("fcostav", 2)):
+            Z = np.zeros(nz * P)  # ntg.c:119 calloc
+            av, nav = rp.avs(list(getattr(spec, nm)))
+            L.updateZ(Z.ctypes.data_as(dp), cc, xb.ctypes.data_as(dp), av, nav, typ)
+            per.append(Z)
+        Zl.append(np.stack(per))
+    out["Z"] = np.array(Zl)   # [point][list][nZ]
+    return out
+
+
 def run_reference(L, spec, x, lowerb, upperb):
     """Drive the reference functions the way NPfunobj/NPfuncon/ntg() do (ntg.c:162-229,274-371)."""
+    if spec.family < 0:
+        return run_reference_tables(L, spec, x, lowerb, upperb)
     O = orc.lib()
     O.orc_family_set_nout(spec.nout)
     for nm in ("ucf", "icf", "fcf", "nlicf", "nltcf", "nlfcf"):
@@ -221,6 +264,10 @@ def cases():
     yield "U16", U16, rng.normal(size=(2, U16.nC)) * 5, loV, upV
     yield "UO", UO, rng.normal(size=(2, UO.nC)) * 5, loO, upO
     yield "UD8", UD8, rng.normal(size=(2, UD8.nC)) * 2, loD, upD
+    # outputs of mixed order, mult and maxderiv (tests/hostpath_cases.py, MIX5): the case brings its own points and bounds, no draw here
+    import hostpath_cases as hc
+    H = hc.CASES["MIX5"]()
+    yield "H", H.spec, H.points, H.lower[None], H.upper[None]
 
 
 def main():
@@ -228,7 +275,7 @@ def main():
     for name, spec, x, lo, up in cases():
         out = run_reference(L, spec, x, lo, up)
         np.savez_compressed(os.path.join(HERE, f"ref_{name}.npz"), **out)
-        print(name, "f", out["f"][:2], "files ok")
+        print(name, "f" if "f" in out else "Z", (out["f"] if "f" in out else out["Z"].ravel())[:2], "files ok")
 
 
 if __name__ == "__main__":
