@@ -141,6 +141,37 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _bisect_out(batch, rows, dev, bounds):
+    """the outputs of extrema, forms and ratios for (batch, rows): ext, when, status, npieces and, with bounds, viol and where.  (No row gets one
+    row of storage: the library refuses or returns before it writes, and an empty tensor would arrive as a null pointer)"""
+    import torch
+    rows = max(rows, 1)
+    out = {"ext": torch.empty((batch, rows, 4), dtype=torch.float64, device=dev), "when": torch.empty((batch, rows, 2), dtype=torch.float64, device=dev),
+           "status": torch.empty((batch, rows), dtype=torch.int32, device=dev), "npieces": torch.empty((batch, rows), dtype=torch.int32, device=dev)}
+    if bounds:
+        out["viol"] = torch.zeros((batch, 2), dtype=torch.float64, device=dev); out["where"] = torch.full((batch, 2), -1, dtype=torch.int32, device=dev)
+    return out
+
+
+def _declare_forms(forms, fprm, lower, upper, dev, batch, nrows, what, ratios=()):
+    """what forms and ratios ask of fprm [batch, nfp], the bounds [batch, nrows] of `what` and the ratios' factor counts, in that order, and
+    then the declaration as the library takes it: -> (form_nterms, terms, nfp)"""
+    _check_tensor(fprm, dev); _check_tensor(lower, dev); _check_tensor(upper, dev)
+    forms = [list(f) for f in forms]
+    if (lower is None) != (upper is None):
+        raise NtgError("pass both bounds or neither")
+    if lower is not None and (lower.shape != (batch, nrows) or upper.shape != (batch, nrows)):
+        raise NtgError(f"the {what}' bounds must be [{batch}, {nrows}]")
+    if fprm is not None and (fprm.dim() != 2 or fprm.shape[0] != batch):
+        raise NtgError(f"fprm must be [{batch}, nfp]")
+    for r, (n, d) in enumerate(ratios):
+        if len(n) > RATIO_MAXFACTORS or len(d) > RATIO_MAXFACTORS:
+            raise NtgError(f"ratio {r}: nnum and nden must lie in 0 .. {RATIO_MAXFACTORS}")
+    nterms = (C.c_int * max(len(forms), 1))(*[len(f) for f in forms])
+    flat = [FormTerm(*t) for f in forms for t in f]
+    return nterms, (FormTerm * max(len(flat), 1))(*flat), 0 if fprm is None else int(fprm.shape[1])
+
+
 class Plan:
     """Device-resident, batch-shared part of a problem (ntg_plan)."""
 
@@ -478,13 +509,8 @@ class Plan:
         viol [batch, 2] = (attained, certified) and where [batch, 2], the row of each or -1.  sides: 1 the minimum, 2 the maximum, 3 both.
         viol[:, 1] == 0 certifies every trajectory row over the whole horizon; a row extrema_rows() flags 0 comes back as
         (-inf, +inf, -inf, +inf), and viol / where are then refused."""
-        import torch
         sp, dev, batch = self._cert_inputs(x, lower, upper)
-        nrow = max(sp.nltc + sp.nnltc, 1)   # (a plan without rows gets one row of storage: the library refuses it before it writes)
-        out = {"ext": torch.empty((batch, nrow, 4), dtype=torch.float64, device=dev), "when": torch.empty((batch, nrow, 2), dtype=torch.float64, device=dev),
-               "status": torch.empty((batch, nrow), dtype=torch.int32, device=dev), "npieces": torch.empty((batch, nrow), dtype=torch.int32, device=dev)}
-        if lower is not None:
-            out["viol"] = torch.zeros((batch, 2), dtype=torch.float64, device=dev); out["where"] = torch.full((batch, 2), -1, dtype=torch.int32, device=dev)
+        out = _bisect_out(batch, sp.nltc + sp.nnltc, dev, lower is not None)
         _check(lib().ntg_batch_extrema(self.h, batch, _ptr(x), float(tol), int(max_depth), int(sides), _ptr(lower), _ptr(upper), _ptr(out["ext"]), _ptr(out["when"]),
                                        _ptr(out["status"]), _ptr(out["npieces"]), _ptr(out.get("viol")), _ptr(out.get("where")), self._stream()))
         return out
@@ -527,26 +553,12 @@ class Plan:
         (min_lo, min_hi, max_lo, max_hi), when [batch, nform, 2], status and npieces [batch, nform] and, with the bounds lower / upper
         [batch, nform] of the forms, viol [batch, 2] = (attained, certified) and where [batch, 2], the form of each or -1.
         viol[:, 1] == 0 certifies every declared form over the whole horizon."""
-        import torch
         sp, dev, batch = self._cert_inputs(x, None, None)
-        _check_tensor(fprm, dev); _check_tensor(lower, dev); _check_tensor(upper, dev)
-        forms = [list(f) for f in forms]
+        forms = list(forms)
         nform = len(forms)
-        if (lower is None) != (upper is None):
-            raise NtgError("pass both bounds or neither")
-        if lower is not None and (lower.shape != (batch, nform) or upper.shape != (batch, nform)):
-            raise NtgError(f"the forms' bounds must be [{batch}, {nform}]")
-        if fprm is not None and (fprm.dim() != 2 or fprm.shape[0] != batch):
-            raise NtgError(f"fprm must be [{batch}, nfp]")
-        nterms = (C.c_int * max(nform, 1))(*[len(f) for f in forms])
-        flat = [FormTerm(*t) for f in forms for t in f]
-        terms = (FormTerm * max(len(flat), 1))(*flat)
-        rows = max(nform, 1)   # (an empty declaration gets one form of storage: the library returns before it writes)
-        out = {"ext": torch.empty((batch, rows, 4), dtype=torch.float64, device=dev), "when": torch.empty((batch, rows, 2), dtype=torch.float64, device=dev),
-               "status": torch.empty((batch, rows), dtype=torch.int32, device=dev), "npieces": torch.empty((batch, rows), dtype=torch.int32, device=dev)}
-        if lower is not None:
-            out["viol"] = torch.zeros((batch, 2), dtype=torch.float64, device=dev); out["where"] = torch.full((batch, 2), -1, dtype=torch.int32, device=dev)
-        _check(lib().ntg_batch_forms(self.h, batch, _ptr(x), nform, nterms, terms, 0 if fprm is None else int(fprm.shape[1]), _ptr(fprm), float(tol), int(max_depth),
+        nterms, terms, nfp = _declare_forms(forms, fprm, lower, upper, dev, batch, nform, "forms")
+        out = _bisect_out(batch, nform, dev, lower is not None)
+        _check(lib().ntg_batch_forms(self.h, batch, _ptr(x), nform, nterms, terms, nfp, _ptr(fprm), float(tol), int(max_depth),
                                      int(sides), _ptr(lower), _ptr(upper), _ptr(out["ext"]), _ptr(out["when"]), _ptr(out["status"]), _ptr(out["npieces"]),
                                      _ptr(out.get("viol")), _ptr(out.get("where")), self._stream()))
         return out
@@ -557,32 +569,14 @@ class Plan:
         of lists of up to RATIO_MAXFACTORS form indices, as ntg_amd.forms.ratio returns them: the product of the forms num over the product of
         the forms den (an empty list is 1, a repeated index a power).  Returns the dict of Plan.forms with the ratio in the place of the form;
         status RATIO_POLE: the denominator was <= 0 at a time the bisection visited, no statement.  lower / upper [batch, nratio]."""
-        import torch
         sp, dev, batch = self._cert_inputs(x, None, None)
-        _check_tensor(fprm, dev); _check_tensor(lower, dev); _check_tensor(upper, dev)
-        forms = [list(f) for f in forms]
-        ratios = [(list(n), list(d)) for n, d in ratios]
+        forms, ratios = list(forms), [(list(n), list(d)) for n, d in ratios]
         nform, nratio = len(forms), len(ratios)
-        if (lower is None) != (upper is None):
-            raise NtgError("pass both bounds or neither")
-        if lower is not None and (lower.shape != (batch, nratio) or upper.shape != (batch, nratio)):
-            raise NtgError(f"the ratios' bounds must be [{batch}, {nratio}]")
-        if fprm is not None and (fprm.dim() != 2 or fprm.shape[0] != batch):
-            raise NtgError(f"fprm must be [{batch}, nfp]")
-        for r, (n, d) in enumerate(ratios):
-            if len(n) > RATIO_MAXFACTORS or len(d) > RATIO_MAXFACTORS:
-                raise NtgError(f"ratio {r}: nnum and nden must lie in 0 .. {RATIO_MAXFACTORS}")
-        nterms = (C.c_int * max(nform, 1))(*[len(f) for f in forms])
-        flat = [FormTerm(*t) for f in forms for t in f]
-        terms = (FormTerm * max(len(flat), 1))(*flat)
+        nterms, terms, nfp = _declare_forms(forms, fprm, lower, upper, dev, batch, nratio, "ratios", ratios)
         pad = lambda v: (C.c_int * 4)(*(list(v) + [0] * (4 - len(v))))
         rat = (Ratio * max(nratio, 1))(*[Ratio(len(n), len(d), pad(n), pad(d)) for n, d in ratios])
-        rows = max(nratio, 1)   # (an empty declaration gets one ratio of storage: the library returns before it writes)
-        out = {"ext": torch.empty((batch, rows, 4), dtype=torch.float64, device=dev), "when": torch.empty((batch, rows, 2), dtype=torch.float64, device=dev),
-               "status": torch.empty((batch, rows), dtype=torch.int32, device=dev), "npieces": torch.empty((batch, rows), dtype=torch.int32, device=dev)}
-        if lower is not None:
-            out["viol"] = torch.zeros((batch, 2), dtype=torch.float64, device=dev); out["where"] = torch.full((batch, 2), -1, dtype=torch.int32, device=dev)
-        _check(lib().ntg_batch_ratios(self.h, batch, _ptr(x), nform, nterms, terms, 0 if fprm is None else int(fprm.shape[1]), _ptr(fprm), nratio, rat, float(tol),
+        out = _bisect_out(batch, nratio, dev, lower is not None)
+        _check(lib().ntg_batch_ratios(self.h, batch, _ptr(x), nform, nterms, terms, nfp, _ptr(fprm), nratio, rat, float(tol),
                                       int(max_depth), int(sides), _ptr(lower), _ptr(upper), _ptr(out["ext"]), _ptr(out["when"]), _ptr(out["status"]), _ptr(out["npieces"]),
                                       _ptr(out.get("viol")), _ptr(out.get("where")), self._stream()))
         return out

@@ -22,8 +22,13 @@
 //   extrema_pp_kernel      per-problem grids: the same, with breaks and weights of the wave's own problem.
 // No scratch in HBM, no atomics, nothing depends on the batch around a problem.  Every private array is indexed by unrolled loop counters only.
 // The levels themselves (ext_levels) take the row as a source of level-0 polygons and a threshold flag: ext_row hands them a row of the plan,
-// separation.hpp the squared difference of two trajectories, with its "not plo >= s2" in the opening rule.  There is one level loop here;
-// ratio_levels (ratios.hpp) is its twin on pairs of polygons, kept in step by hand: whoever edits ext_levels edits that one too.
+// forms.hpp a declared form, separation.hpp the squared difference of two trajectories, with its "not plo >= s2" in the opening rule.
+// ratio_levels (ratios.hpp) is its twin on pairs of polygons, kept in step by hand: whoever edits ext_levels edits that one too.  One loop
+// templated over the piece gives the same bits (tests/golden holds both to recorded results) and no worse registers, but it cost the extrema
+// and separation kernels 1 to 2 % of their rate, more than their run-to-run spread: DESIGN.md has the figures.  The two loops share the
+// de Casteljau split (ext_split) and the epilogue (ExtOut: a row's outputs, and the violation of a problem folded over its rows).
+// extrema_*_kernel and separation_kernel carve their dynamic LDS by hand, in the order of BisectLds (ntg_dev.hpp), which sizes their launch:
+// formed from that description the pointers cost separation_kernel 3 to 5 us a call.  Whoever moves a table here moves it there.
 #pragma once
 #include "wave_ops.hpp"
 #include "envelope_sos.hpp"
@@ -74,12 +79,22 @@ __device__ __forceinline__ double ext_last(const EnvPoly<KD> &P, int D)
 	return __longlong_as_double(v);
 }
 
-// what a wave works with: the workgroup's (or its own) tables and its own rows and work list, all in LDS
-struct ExtLds {
-	const double *wl, *tab, *kns, *xrow, *prow;
-	double *list;        // [NTG_EXTREMA_CAP][2 KM - 1]
-	long long *keys;     // [NTG_EXTREMA_CAP]: interval << 32 | index of the piece at its level
-};
+// split in the middle by de Casteljau: Rp becomes the right child, Lp the left one
+template <int KD>
+__device__ __forceinline__ void ext_split(EnvPoly<KD> &Lp, EnvPoly<KD> &Rp, int Dl)
+{
+#pragma unroll
+	for (int s = 0; s < KD; s++) Lp.b[s] = 0.0;
+	Lp.b[0] = Rp.b[0];
+#pragma unroll
+	for (int r = 1; r < KD; r++) {
+		if (r <= Dl) {
+#pragma unroll
+			for (int s = 0; s < KD - r; s++) { if (s <= Dl - r) Rp.b[s] = 0.5 * (Rp.b[s] + Rp.b[s + 1]); }
+			Lp.b[r] = Rp.b[0];
+		}
+	}
+}
 
 // what the levels need of a row: the breaks and interval lengths of its basis class, the number l of its knot intervals, the degree D of its
 // polygon, and the call's figures.  s2 (THR instances only): a piece whose polygon does not reach below s2 retires at once
@@ -176,18 +191,7 @@ __device__ __forceinline__ void ext_levels(const ExtRun &Q, const ExtLds &M, con
 		}
 		__builtin_amdgcn_wave_barrier();   // every parent is in registers before a child is stored
 		const int j = (int)(key >> 32), i = (int)(key & 0xffffffffll);
-		// split in the middle: Rp becomes the right child, Lp the left one
-#pragma unroll
-		for (int s = 0; s < KD; s++) Lp.b[s] = 0.0;
-		Lp.b[0] = Rp.b[0];
-#pragma unroll
-		for (int r = 1; r < KD; r++) {
-			if (r <= Dl) {
-#pragma unroll
-				for (int s = 0; s < KD - r; s++) { if (s <= Dl - r) Rp.b[s] = 0.5 * (Rp.b[s] + Rp.b[s + 1]); }
-				Lp.b[r] = Rp.b[0];
-			}
-		}
+		ext_split<KD>(Lp, Rp, Dl);   // Rp becomes the right child, Lp the left one
 		double llo = 0.0, lhi = 0.0, rlo = 0.0, rhi = 0.0;
 		if (on) {
 			const double e0 = Lp.b[0], em = Rp.b[0], e1 = ext_last<KD>(Rp, Dl);
@@ -273,41 +277,57 @@ __device__ __forceinline__ void ext_row(const ExtArgs &A, const SosTables &T, co
 		return;
 	}
 	const EnvClass C = T.c[cl];
-	const ExtRun Q{M.kns + A.koff[cl], M.tab + C.hoff, C.l, D, A.max_depth, A.sides, A.tol, INFINITY};
+	const ExtRun Q{M.kns + A.q.koff[cl], M.tab + C.hoff, C.l, D, A.q.max_depth, A.q.sides, A.q.tol, INFINITY};
 	const ExtRowSrc<KM> src{A, T, M, lin, lr, row, cl, D, R, C};
 	ext_levels<KM, false>(Q, M, src, lane, res, tw, status, npieces);
 }
+
+// The outputs of a problem, by one wave: every row's figures as they come, and the largest violation of the attained (av, ak) and of the
+// certified (cv, ck) values over the rows folded so far
+struct ExtOut {
+	const CertBisect &Q; int lane;
+	double av = 0.0, cv = 0.0; long long ak = -1, ck = -1;
+	__device__ __forceinline__ bool want_v() const { return Q.viol || Q.where; }
+	__device__ __forceinline__ void row(size_t at, const double (&res)[4], const double (&tw)[2], int status, int npieces) const
+	{
+		if (lane != 0) return;
+		if (Q.ext) { Q.ext[4 * at] = res[0]; Q.ext[4 * at + 1] = res[1]; Q.ext[4 * at + 2] = res[2]; Q.ext[4 * at + 3] = res[3]; }
+		if (Q.when) { Q.when[2 * at] = tw[0]; Q.when[2 * at + 1] = tw[1]; }
+		if (Q.status) Q.status[at] = status;
+		if (Q.npieces) Q.npieces[at] = npieces;
+	}
+	// row idx with the bounds (l, u)
+	__device__ __forceinline__ void fold(double l, double u, const double (&res)[4], int idx)
+	{
+		const double a = env_viol(l, u, res[1], res[2]), c = env_viol(l, u, res[0], res[3]);   // of the attained values, of the certified ones
+		env_take(av, ak, a, (a > 0.0 || a != a) ? (long long)idx : -1ll);
+		env_take(cv, ck, c, (c > 0.0 || c != c) ? (long long)idx : -1ll);
+	}
+	__device__ __forceinline__ void problem(int b) const
+	{
+		if (!want_v() || lane != 0) return;
+		if (Q.viol) { Q.viol[2 * (size_t)b] = ak < 0 ? 0.0 : av; Q.viol[2 * (size_t)b + 1] = ck < 0 ? 0.0 : cv; }
+		if (Q.where) { Q.where[2 * (size_t)b] = (int)ak; Q.where[2 * (size_t)b + 1] = (int)ck; }
+	}
+};
 
 // every row of problem b, by one wave whose x row and parameter row are in M
 template <int KM>
 __device__ __forceinline__ void ext_problem(const ExtArgs &A, const SosTables &T, const ExtLds &M, int b, int lane)
 {
 	const int nltc = A.lin.nltc, nrow = nltc + A.sos.nrow;
-	const bool want_v = A.viol || A.where;
-	double av = 0.0, cv = 0.0; long long ak = -1, ck = -1;
+	ExtOut O{A.q, lane};
 	for (int row = 0; row < nrow; row++) {
 		double res[4], tw[2];
 		int status, npieces;
 		ext_row<KM>(A, T, M, row, lane, res, tw, status, npieces);
-		const size_t at = (size_t)b * nrow + row;
-		if (lane == 0) {
-			if (A.ext) { A.ext[4 * at] = res[0]; A.ext[4 * at + 1] = res[1]; A.ext[4 * at + 2] = res[2]; A.ext[4 * at + 3] = res[3]; }
-			if (A.when) { A.when[2 * at] = tw[0]; A.when[2 * at + 1] = tw[1]; }
-			if (A.status) A.status[at] = status;
-			if (A.npieces) A.npieces[at] = npieces;
-		}
-		if (want_v) {   // (every row has flag 1: the host has refused the others)
+		O.row((size_t)b * nrow + row, res, tw, status, npieces);
+		if (O.want_v()) {   // (every row has flag 1: the host has refused the others)
 			const int slot = row < nltc ? A.lin.slot0 + row : A.sos.slot0 + row - nltc;
-			const double l = A.g.lower[(size_t)b * A.g.nbounds + slot], u = A.g.upper[(size_t)b * A.g.nbounds + slot];
-			const double a = env_viol(l, u, res[1], res[2]), c = env_viol(l, u, res[0], res[3]);   // of the attained values, of the certified ones
-			env_take(av, ak, a, (a > 0.0 || a != a) ? (long long)row : -1ll);
-			env_take(cv, ck, c, (c > 0.0 || c != c) ? (long long)row : -1ll);
+			O.fold(A.g.lower[(size_t)b * A.g.nbounds + slot], A.g.upper[(size_t)b * A.g.nbounds + slot], res, row);
 		}
 	}
-	if (want_v && lane == 0) {
-		if (A.viol) { A.viol[2 * (size_t)b] = ak < 0 ? 0.0 : av; A.viol[2 * (size_t)b + 1] = ck < 0 ? 0.0 : cv; }
-		if (A.where) { A.where[2 * (size_t)b] = (int)ak; A.where[2 * (size_t)b + 1] = (int)ck; }
-	}
+	O.problem(b);
 }
 
 template <int NT, int KM>
@@ -321,12 +341,12 @@ extrema_shared_kernel(ExtArgs A)
 	double *wl = reinterpret_cast<double *>(smem_raw);    // the product tables, unfolded
 	double *tab = wl + NTG_SOS_WFULL;                     // weights and interval lengths of every basis class
 	double *kns = tab + A.g.ne;                           // breaks of every basis class
-	double *mine = kns + A.nk + (size_t)wave * (A.g.nC + A.sos.np + NTG_EXTREMA_CAP * (KD + 1));
+	double *mine = kns + A.q.nk + (size_t)wave * (A.g.nC + A.sos.np + NTG_EXTREMA_CAP * (KD + 1));
 	double *xrow = mine, *prow = xrow + A.g.nC, *list = prow + A.sos.np;
 	const ExtLds M{wl, tab, kns, xrow, prow, list, reinterpret_cast<long long *>(list + NTG_EXTREMA_CAP * KD)};
 	sos_stage(A.sos, A.g, T, tid);
 	sos_unfold(A.sos, wl, tid, NT);
-	env_build_classes(A.g, tab, kns, A.koff, tid, NT);
+	env_build_classes(A.g, tab, kns, A.q.koff, tid, NT);
 	for (int b0 = blockIdx.x * NW; b0 < A.g.batch; b0 += gridDim.x * NW) {
 		const int b = b0 + wave;
 		if (b >= A.g.batch) continue;
@@ -348,8 +368,8 @@ extrema_pp_kernel(ExtArgs A)
 	const EnvClass C = A.g.c[0];
 	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 	double *wl = reinterpret_cast<double *>(smem_raw);
-	double *tab = wl + NTG_SOS_WFULL + (size_t)wave * (A.g.ne + A.nk + A.g.nC + A.sos.np + NTG_EXTREMA_CAP * (KD + 1));
-	double *kns = tab + A.g.ne, *xrow = kns + A.nk, *prow = xrow + A.g.nC, *list = prow + A.sos.np;
+	double *tab = wl + NTG_SOS_WFULL + (size_t)wave * (A.g.ne + A.q.nk + A.g.nC + A.sos.np + NTG_EXTREMA_CAP * (KD + 1));
+	double *kns = tab + A.g.ne, *xrow = kns + A.q.nk, *prow = xrow + A.g.nC, *list = prow + A.sos.np;
 	const ExtLds M{wl, tab, kns, xrow, prow, list, reinterpret_cast<long long *>(list + NTG_EXTREMA_CAP * KD)};
 	sos_stage(A.sos, A.g, T, threadIdx.x);
 	sos_unfold(A.sos, wl, threadIdx.x, NT);

@@ -154,35 +154,21 @@ template <int KM>
 __device__ __forceinline__ void form_problem(const FormArgs &A, const ExtLds &M, int b, int lane)
 {
 	const int nform = A.nform;
-	const bool want_v = A.viol || A.where;
-	double av = 0.0, cv = 0.0; long long ak = -1, ck = -1;
+	ExtOut O{A.q, lane};
 	for (int f = 0; f < nform; f++) {
 		const FormRow R = A.row[f];
 		const EnvClass C = A.g.c[R.cl];
 		const FormOf F{A, f, R, C};
-		const ExtRun Q{M.kns + A.koff[R.cl], M.tab + C.hoff, C.l, R.D, A.max_depth, A.sides, A.tol, INFINITY};
+		const ExtRun Q{M.kns + A.q.koff[R.cl], M.tab + C.hoff, C.l, R.D, A.q.max_depth, A.q.sides, A.q.tol, INFINITY};
 		const FormSrc<KM> src{F, M};
 		double res[4], tw[2];
 		int status, npieces;
 		ext_levels<KM, false>(Q, M, src, lane, res, tw, status, npieces);
 		const size_t at = (size_t)b * nform + f;
-		if (lane == 0) {
-			if (A.ext) { A.ext[4 * at] = res[0]; A.ext[4 * at + 1] = res[1]; A.ext[4 * at + 2] = res[2]; A.ext[4 * at + 3] = res[3]; }
-			if (A.when) { A.when[2 * at] = tw[0]; A.when[2 * at + 1] = tw[1]; }
-			if (A.status) A.status[at] = status;
-			if (A.npieces) A.npieces[at] = npieces;
-		}
-		if (want_v) {
-			const double l = A.flo[at], u = A.fhi[at];
-			const double a = env_viol(l, u, res[1], res[2]), c = env_viol(l, u, res[0], res[3]);   // of the attained values, of the certified ones
-			env_take(av, ak, a, (a > 0.0 || a != a) ? (long long)f : -1ll);
-			env_take(cv, ck, c, (c > 0.0 || c != c) ? (long long)f : -1ll);
-		}
+		O.row(at, res, tw, status, npieces);
+		if (O.want_v()) O.fold(A.flo[at], A.fhi[at], res, f);
 	}
-	if (want_v && lane == 0) {
-		if (A.viol) { A.viol[2 * (size_t)b] = ak < 0 ? 0.0 : av; A.viol[2 * (size_t)b + 1] = ck < 0 ? 0.0 : cv; }
-		if (A.where) { A.where[2 * (size_t)b] = (int)ak; A.where[2 * (size_t)b + 1] = (int)ck; }
-	}
+	O.problem(b);
 }
 
 // the call's own parameter row of problem b, by one wave
@@ -196,23 +182,19 @@ __global__ void __launch_bounds__(NT)
 forms_shared_kernel(FormArgs A)
 {
 	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-	constexpr int NW = NT / 64, KD = 2 * KM - 1;
+	constexpr int NW = NT / 64;
 	__shared__ unsigned int pas[NTG_FORM_PASCAL * NTG_FORM_PASCAL];
 	const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-	double *wt = reinterpret_cast<double *>(smem_raw);    // the product tables of every pair of degrees
-	double *tab = wt + NTG_FORM_WALL;                     // weights and interval lengths of every basis class
-	double *kns = tab + A.g.ne;                           // breaks of every basis class
-	double *mine = kns + A.nk + (size_t)wave * (A.g.nC + A.nfp + NTG_EXTREMA_CAP * (KD + 1));
-	double *xrow = mine, *frow = xrow + A.g.nC, *list = frow + A.nfp;
-	const ExtLds M{wt, tab, kns, xrow, frow, list, reinterpret_cast<long long *>(list + NTG_EXTREMA_CAP * KD)};
-	form_build_products(wt, pas, tid, NT);
-	env_build_classes(A.g, tab, kns, A.koff, tid, NT);
+	const ExtStage S = ntg_forms_layout(A, 2 * KM - 1).wave(reinterpret_cast<double *>(smem_raw), wave);
+	const ExtLds M = S.view();   // (the kernel stages through S; everything below reads through M)
+	form_build_products(S.wl, pas, tid, NT);
+	env_build_classes(A.g, S.tab, S.kns, A.q.koff, tid, NT);
 	for (int b0 = blockIdx.x * NW; b0 < A.g.batch; b0 += gridDim.x * NW) {
 		const int b = b0 + wave;
 		if (b >= A.g.batch) continue;
 		__builtin_amdgcn_wave_barrier();   // the problem before is done with the rows
-		env_stage_rows(A.g, nullptr, b, xrow, nullptr, lane, 64);
-		form_stage_fprm(A, b, frow, lane);
+		env_stage_rows(A.g, nullptr, b, S.xrow, nullptr, lane, 64);
+		form_stage_fprm(A, b, S.prow, lane);
 		__builtin_amdgcn_wave_barrier();
 		form_problem<KM>(A, M, b, lane);
 	}
@@ -224,23 +206,21 @@ __global__ void __launch_bounds__(NT)
 forms_pp_kernel(FormArgs A)
 {
 	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-	constexpr int NW = NT / 64, KD = 2 * KM - 1;
+	constexpr int NW = NT / 64;
 	__shared__ unsigned int pas[NTG_FORM_PASCAL * NTG_FORM_PASCAL];
 	const EnvClass C = A.g.c[0];
 	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-	double *wt = reinterpret_cast<double *>(smem_raw);
-	double *tab = wt + NTG_FORM_WALL + (size_t)wave * (A.g.ne + A.nk + A.g.nC + A.nfp + NTG_EXTREMA_CAP * (KD + 1));
-	double *kns = tab + A.g.ne, *xrow = kns + A.nk, *frow = xrow + A.g.nC, *list = frow + A.nfp;
-	const ExtLds M{wt, tab, kns, xrow, frow, list, reinterpret_cast<long long *>(list + NTG_EXTREMA_CAP * KD)};
-	form_build_products(wt, pas, threadIdx.x, NT);
+	const ExtStage S = ntg_forms_layout(A, 2 * KM - 1).wave(reinterpret_cast<double *>(smem_raw), wave);
+	const ExtLds M = S.view();   // (the kernel stages through S; everything below reads through M)
+	form_build_products(S.wl, pas, threadIdx.x, NT);
 	const int per_pass = gridDim.x * NW;
 	for (int b0 = 0; b0 < A.g.batch; b0 += per_pass) {   // (the same trip count for every wave of the grid: the barriers below are uniform)
 		const int b = b0 + blockIdx.x * NW + wave;
 		const bool on = b < A.g.batch;
 		__syncthreads();
-		if (on) { env_stage_pp(A.g, nullptr, b, kns, xrow, nullptr, lane); form_stage_fprm(A, b, frow, lane); }
+		if (on) { env_stage_pp(A.g, nullptr, b, S.kns, S.xrow, nullptr, lane); form_stage_fprm(A, b, S.prow, lane); }
 		__syncthreads();
-		if (on) env_build(kns, C, tab + C.eoff, tab + C.hoff, lane, 64);
+		if (on) env_build(S.kns, C, S.tab + C.eoff, S.tab + C.hoff, lane, 64);
 		__syncthreads();
 		if (on) form_problem<KM>(A, M, b, lane);
 	}

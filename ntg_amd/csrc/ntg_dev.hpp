@@ -292,32 +292,63 @@ static inline size_t ntg_envelope_sos_lds(const SosArgs &A)
 	return ((size_t)NTG_SOS_WFULL + (size_t)(A.g.pp ? NTG_ENVELOPE_NT / 64 : 1) * (size_t)(A.g.ne + A.g.nC + A.sos.np + A.g.lmax + 1)) * 8;
 }
 
-// ntg_batch_extrema (extrema.hpp): the global minimum and maximum of every certifiable trajectory row over the horizon, each enclosed to tol,
-// with the time where the attained value sits.  Rows: the lin.nltc linear trajectory rows, then the sos.nrow nonlinear ones.  koff[cl]: the
-// breaks of class cl in the LDS table of nk doubles (the times of the piece ends need them after the weights are built).
-// Outputs as documented at ntg_batch_extrema, any may be null.
+// The bisection calls (extrema.hpp, separation.hpp, forms.hpp, ratios.hpp) share the level loop of extrema.hpp, and with it:
+//   CertBisect  the call's figures and outputs.  koff[cl]: the breaks of class cl in the LDS table of nk doubles (the times of the piece ends
+//               need them after the weights are built).  Outputs as documented at ntg_batch_extrema, any may be null.
+//   ExtLds      what a wave works with: the workgroup's (or its own) tables and its own rows and work list, all in LDS.
+//   BisectLds   where those lie in the dynamic LDS, in doubles and in this order: `front` doubles of tables every wave reads (the product
+//               tables); the extraction tables (ne) and breaks (nk) of every class; per wave the coefficient row (nrow), the parameter row
+//               (nprm) and the work list of NTG_EXTREMA_CAP elements of W doubles with one key each behind it.  Per-problem grids (pp): the
+//               class tables and breaks are the wave's own and lead its part.  The host sizes every launch from this one description
+//               (W from the plan, by the rule that picks the instance); the forms and ratios kernels form their pointers from it too,
+//               with the W of their instance's piece, staging through ExtStage and handing ExtLds, the read-only view, to everything
+//               below.  The extrema and separation kernels carve the same places by hand (extrema.hpp says why).
 #define NTG_EXTREMA_NT 256
-struct ExtArgs {
-	CertBase g;
-	CertLin lin;
-	CertSos sos;
+struct CertBisect {
 	int max_depth, sides, nk, pad;
 	double tol;
 	int koff[NTG_MAX_OUT];
 	double *ext, *when, *viol; int *status, *npieces, *where;
 };
-static_assert(sizeof(ExtArgs) <= 4096, "ExtArgs travels as a kernel argument");
-// doubles of a work-list element: the row polygon's points; the instance (KM = 6 or NTG_MAX_ORDER) follows from the plan's largest order
-static inline int ntg_extrema_kd(const ExtArgs &A) { return A.g.kmax <= 6 ? 11 : 2 * NTG_MAX_ORDER - 1; }
-// dynamic LDS: the unfolded product tables; the extraction tables and the breaks of every class; per wave one coefficient row, one parameter
-// row, the work list (NTG_EXTREMA_CAP polygons) and its keys.  Per-problem grids: every wave has extraction tables and breaks of its own.
-static inline size_t ntg_extrema_lds(const ExtArgs &A)
-{
-	const size_t wave = (size_t)A.g.nC + A.sos.np + (size_t)NTG_EXTREMA_CAP * (ntg_extrema_kd(A) + 1), tabs = (size_t)A.g.ne + A.nk;
-	return ((size_t)NTG_SOS_WFULL + (A.g.pp ? 0 : tabs) + (size_t)(NTG_EXTREMA_NT / 64) * (wave + (A.g.pp ? tabs : 0))) * 8;
-}
+struct ExtLds {
+	const double *wl, *tab, *kns, *xrow, *prow;
+	double *list;        // [NTG_EXTREMA_CAP][W]
+	long long *keys;     // [NTG_EXTREMA_CAP]: interval << 32 | index of the piece at its level
+};
+// ... and the same places writable, for the kernel that stages them; everything below the staging gets the view
+struct ExtStage {
+	double *wl, *tab, *kns, *xrow, *prow, *list;
+	long long *keys;
+	__host__ __device__ __forceinline__ ExtLds view() const { return ExtLds{wl, tab, kns, xrow, prow, list, keys}; }
+};
+struct BisectLds {
+	int front, ne, nk, nrow, nprm, W, pp;
+	__host__ __device__ __forceinline__ size_t wave_doubles() const { return (size_t)(pp ? ne + nk : 0) + nrow + nprm + (size_t)NTG_EXTREMA_CAP * (W + 1); }
+	__host__ __device__ __forceinline__ size_t bytes(int nw) const { return ((size_t)front + (pp ? 0 : ne + nk) + (size_t)nw * wave_doubles()) * 8; }
+	__host__ __device__ __forceinline__ ExtStage wave(double *base, int w) const   // (inlined: the pointers stay in registers)
+	{
+		double *tab = base + front + (pp ? (size_t)w * wave_doubles() : 0), *kns = tab + ne;
+		double *xrow = kns + nk + (pp ? 0 : (size_t)w * wave_doubles()), *prow = xrow + nrow, *list = prow + nprm;
+		return ExtStage{base, tab, kns, xrow, prow, list, reinterpret_cast<long long *>(list + NTG_EXTREMA_CAP * W)};
+	}
+};
 // ... and what a workgroup may ask for: 160 KiB less the static part (the row, term and class tables)
 #define NTG_EXTREMA_LDS_MAX (160 * 1024 - 2048)
+// doubles of a single polygon as a work-list element; the instance (KM = 6 or NTG_MAX_ORDER) follows from the plan's largest order
+static inline __host__ __device__ int ntg_bisect_kd(const CertBase &G) { return G.kmax <= 6 ? 11 : 2 * NTG_MAX_ORDER - 1; }
+
+// ntg_batch_extrema (extrema.hpp): the global minimum and maximum of every certifiable trajectory row over the horizon, each enclosed to tol,
+// with the time where the attained value sits.  Rows: the lin.nltc linear trajectory rows, then the sos.nrow nonlinear ones.
+struct ExtArgs {
+	CertBase g;
+	CertLin lin;
+	CertSos sos;
+	CertBisect q;
+};
+static_assert(sizeof(ExtArgs) <= 4096, "ExtArgs travels as a kernel argument");
+// dynamic LDS: the unfolded product tables in front; a coefficient row and the rows' parameter row per wave
+static __host__ __device__ __forceinline__ BisectLds ntg_extrema_layout(const ExtArgs &A, int W) { return BisectLds{NTG_SOS_WFULL, A.g.ne, A.q.nk, A.g.nC, A.sos.np, W, A.g.pp}; }
+static inline size_t ntg_extrema_lds(const ExtArgs &A) { return ntg_extrema_layout(A, ntg_bisect_kd(A.g)).bytes(NTG_EXTREMA_NT / 64); }
 
 // ntg_batch_separation (separation.hpp): the smallest squared distance over the horizon of pairs of bodies, each body ndim outputs of one
 // basis class.  g holds that ONE class (nclass = 1, its tables at offset 0 of the LDS table, kmax its order) and the batch the pairs'
@@ -335,21 +366,17 @@ struct SepArgs {
 	double *min, *when, *viol; int *status, *npieces;
 };
 static_assert(sizeof(SepArgs) <= 4096, "SepArgs travels as a kernel argument");
-static inline int ntg_separation_kd(const SepArgs &A) { return A.g.kmax <= 6 ? 11 : 2 * NTG_MAX_ORDER - 1; }
-// dynamic LDS: the unfolded product tables, the extraction table and the breaks of the class; per wave delta, the work list and its keys.
-// The limit is ntg_batch_extrema's
-static inline size_t ntg_separation_lds(const SepArgs &A)
-{
-	const size_t wave = (size_t)A.ndim * A.n + (size_t)NTG_EXTREMA_CAP * (ntg_separation_kd(A) + 1);
-	return ((size_t)NTG_SOS_WFULL + A.g.ne + A.g.lmax + 1 + (size_t)(NTG_EXTREMA_NT / 64) * wave) * 8;
-}
+// dynamic LDS: the unfolded product tables in front; the breaks of the one class; per wave delta where a coefficient row would be, no
+// parameter row.  The limit is ntg_batch_extrema's
+static __host__ __device__ __forceinline__ BisectLds ntg_separation_layout(const SepArgs &A, int W) { return BisectLds{NTG_SOS_WFULL, A.g.ne, A.g.lmax + 1, A.ndim * A.n, 0, W, 0}; }
+static inline size_t ntg_separation_lds(const SepArgs &A) { return ntg_separation_layout(A, ntg_bisect_kd(A.g)).bytes(NTG_EXTREMA_NT / 64); }
 
 // ntg_batch_forms (forms.hpp): the minimum and maximum over the horizon of quadratic forms of the flat flag that the CALLER declares, each a sum
 // of weighted products w (z[u] - a)(z[v] - b) and weighted linear terms w (z[u] - a).  term[f][t] in the kernels' form: the coefficient offsets
 // iCu / iCv of the two factors' outputs, their derivative orders ru / rv (the degrees follow from the class: max(k - 1 - r, 0)), the indices
 // pu / pv into the problem's row of fprm [batch][nfp] or -1, the kind, the weight w and the shifts' constants su / sv.  row[f]: nt terms, the
-// basis class cl of every entry the form names, the degree D of its polygon.  koff / nk as in ExtArgs.  flo / fhi [batch][nform] (null unless a
-// violation is asked for).  Outputs as documented at ntg_batch_forms, any may be null.
+// basis class cl of every entry the form names, the degree D of its polygon.  flo / fhi [batch][nform] (null unless a violation is asked
+// for).  Outputs (q) as documented at ntg_batch_forms, any may be null.
 #define NTG_FORM_LIN 0      // w (z[u] - a)
 #define NTG_FORM_PROD 1     // w (z[u] - a)(z[v] - b)
 #define NTG_FORM_SQUARE 2   // ... with the same entry, parameter and constant twice: formed as envelope_sos.hpp forms a square
@@ -357,28 +384,21 @@ struct FormTerm { int iCu, iCv, pu, pv; short ru, rv, kind, pad; double w, su, s
 struct FormRow { int nt, cl, D, pad; };
 struct FormArgs {
 	CertBase g;
-	int nform, nfp, max_depth, sides, nk, pad;
-	double tol;
-	int koff[NTG_MAX_OUT];
+	int nform, nfp;
+	CertBisect q;
 	FormRow row[NTG_FORM_MAXFORMS];
 	FormTerm term[NTG_FORM_MAXFORMS][NTG_FORM_MAXTERMS];
 	const double *fprm, *flo, *fhi;
-	double *ext, *when, *viol; int *status, *npieces, *where;
 };
 static_assert(sizeof(FormArgs) <= 4096, "FormArgs travels as a kernel argument");
 // the product tables W_{d,e}[i][j] = C(d,i) C(e,j) / C(d+e,i+j) of every pair of degrees 0 <= d, e < NTG_MAX_ORDER, [d + 1][e + 1] each, e
 // fastest: doubles of all of them, and where the table of (d, e) starts
 #define NTG_FORM_WALL ((NTG_MAX_ORDER * (NTG_MAX_ORDER + 1) / 2) * (NTG_MAX_ORDER * (NTG_MAX_ORDER + 1) / 2))
 static inline __host__ __device__ int ntg_form_woff(int d, int e) { return (NTG_MAX_ORDER * (NTG_MAX_ORDER + 1) / 2) * (d * (d + 1) / 2) + (d + 1) * (e * (e + 1) / 2); }
-static inline int ntg_forms_kd(const FormArgs &A) { return A.g.kmax <= 6 ? 11 : 2 * NTG_MAX_ORDER - 1; }
-// dynamic LDS: the product tables (built on the device); the extraction tables and the breaks of every class; per wave one coefficient row, one
-// row of fprm, the work list and its keys.  Per-problem grids: every wave has extraction tables and breaks of its own.  The limit is
+// dynamic LDS: the product tables (built on the device) in front; a coefficient row and a row of fprm per wave.  The limit is
 // ntg_batch_extrema's (the static part is the Pascal triangle the product tables are built from)
-static inline size_t ntg_forms_lds(const FormArgs &A)
-{
-	const size_t wave = (size_t)A.g.nC + A.nfp + (size_t)NTG_EXTREMA_CAP * (ntg_forms_kd(A) + 1), tabs = (size_t)A.g.ne + A.nk;
-	return ((size_t)NTG_FORM_WALL + (A.g.pp ? 0 : tabs) + (size_t)(NTG_EXTREMA_NT / 64) * (wave + (A.g.pp ? tabs : 0))) * 8;
-}
+static __host__ __device__ __forceinline__ BisectLds ntg_forms_layout(const FormArgs &A, int W) { return BisectLds{NTG_FORM_WALL, A.g.ne, A.q.nk, A.g.nC, A.nfp, W, A.g.pp}; }
+static inline size_t ntg_forms_lds(const FormArgs &A) { return ntg_forms_layout(A, ntg_bisect_kd(A.g)).bytes(NTG_EXTREMA_NT / 64); }
 
 // ntg_batch_ratios (ratios.hpp): the minimum and maximum over the horizon of ratios of products of the forms of a FormArgs, R = prod num /
 // prod den.  f: the forms exactly as ntg_batch_forms declares them (its outputs are the ratios' [batch][nratio] arrays, flo / fhi the ratios'
@@ -397,11 +417,7 @@ struct RatioArgs {
 	unsigned short poff[NTG_RATIO_MAXPAIRS];
 };
 static_assert(sizeof(RatioArgs) <= 4096, "RatioArgs travels as a kernel argument");
-// dynamic LDS: the forms' product tables and the chains' (both built on the device); the extraction tables and the breaks of every class; per
-// wave one coefficient row, one row of fprm, the work list of NTG_EXTREMA_CAP pairs of polygons and its keys.  Per-problem grids: every wave
-// has extraction tables and breaks of its own.  The limit is ntg_batch_extrema's
-static inline size_t ntg_ratios_lds(const RatioArgs &A, int nw)
-{
-	const size_t wave = (size_t)A.f.g.nC + A.f.nfp + (size_t)NTG_EXTREMA_CAP * (2 * A.kr + 1), tabs = (size_t)A.f.g.ne + A.f.nk;
-	return ((size_t)NTG_FORM_WALL + A.npw + (A.f.g.pp ? 0 : tabs) + (size_t)nw * (wave + (A.f.g.pp ? tabs : 0))) * 8;
-}
+// dynamic LDS: the forms' product tables and the chains' (both built on the device) in front; a coefficient row and a row of fprm per wave; a
+// work-list element is a pair of polygons, numerator first.  The limit is ntg_batch_extrema's
+static __host__ __device__ __forceinline__ BisectLds ntg_ratios_layout(const RatioArgs &A, int W) { return BisectLds{NTG_FORM_WALL + A.npw, A.f.g.ne, A.f.q.nk, A.f.g.nC, A.f.nfp, W, A.f.g.pp}; }
+static inline size_t ntg_ratios_lds(const RatioArgs &A, int nw) { return ntg_ratios_layout(A, 2 * A.kr).bytes(nw); }

@@ -33,13 +33,22 @@ int cert_batch_size(const ntg_plan *p, int batch, bool with_prm)
 		return fail(NTG_E_BADARG, "the plan carries per-problem parameters for " + std::to_string(p->prm_batch) + " problems, not " + std::to_string(batch));
 	return 0;
 }
-// tol, max_depth and sides of the bisection calls
-int cert_levels(double tol, int max_depth, int sides)
+// tol and max_depth of the bisection calls; sides of those that have both
+int cert_levels(double tol, int max_depth)
 {
 	if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(NTG_E_BADARG, "tol must be finite and >= 0");
 	if (max_depth < 0 || max_depth > NTG_EXTREMA_MAX_DEPTH) return fail(NTG_E_BADARG, "max_depth must lie in 0 .. " + std::to_string(NTG_EXTREMA_MAX_DEPTH));
-	if (sides < 1 || sides > 3) return fail(NTG_E_BADARG, "sides must be 1 (minimum), 2 (maximum) or 3 (both)");
 	return 0;
+}
+int cert_sides(int sides)
+{
+	return sides < 1 || sides > 3 ? fail(NTG_E_BADARG, "sides must be 1 (minimum), 2 (maximum) or 3 (both)") : 0;
+}
+// the call's figures and outputs, for the level loop and the epilogue the bisection kernels share (koff / nk: cert_base)
+void cert_bisect(CertBisect &Q, double tol, int max_depth, int sides, double *d_ext, double *d_when, int *d_status, int *d_npieces, double *d_viol, int *d_where)
+{
+	Q.tol = tol; Q.max_depth = max_depth; Q.sides = sides;
+	Q.ext = d_ext; Q.when = d_when; Q.status = d_status; Q.npieces = d_npieces; Q.viol = d_viol; Q.where = d_where;
 }
 int cert_nsub(int nsub)
 {
@@ -253,9 +262,8 @@ extern "C" int ntg_batch_extrema(const ntg_plan *p, int batch, const double *d_x
                                  double *d_ext, double *d_when, int *d_status, int *d_npieces, double *d_viol, int *d_where, void *stream)
 {
 	if (!p) return fail(NTG_E_BADARG, "null plan");
-	if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(NTG_E_BADARG, "tol must be finite and >= 0");
-	if (max_depth < 0 || max_depth > NTG_EXTREMA_MAX_DEPTH) return fail(NTG_E_BADARG, "max_depth must lie in 0 .. " + std::to_string(NTG_EXTREMA_MAX_DEPTH));
-	if (sides < 1 || sides > 3) return fail(NTG_E_BADARG, "sides must be 1 (minimum), 2 (maximum) or 3 (both)");
+	if (int rc = cert_levels(tol, max_depth)) return rc;
+	if (int rc = cert_sides(sides)) return rc;
 	if (int rc = cert_batch(batch, d_x)) return rc > 0 ? 0 : rc;
 	const bool want_v = d_viol || d_where;
 	if (!d_ext && !d_when && !d_status && !d_npieces && !want_v)
@@ -283,12 +291,11 @@ extern "C" int ntg_batch_extrema(const ntg_plan *p, int batch, const double *d_x
 		return fail(NTG_E_UNSUPPORTED, "trajectory row " + std::to_string(n.first0) + " is not certified (ntg_plan_extrema_rows): d_viol / d_where would be a partial "
 		                                   "certificate; the other outputs are still served");
 	if (int rc = cert_sos_prm(p, n)) return rc;
-	cert_base(p, batch, d_x, d_lower, d_upper, A.g, A.koff, &A.nk);
+	cert_base(p, batch, d_x, d_lower, d_upper, A.g, A.q.koff, &A.q.nk);
 	cert_lin(p, A.lin);
-	A.max_depth = max_depth; A.sides = sides; A.tol = tol;
+	cert_bisect(A.q, tol, max_depth, sides, d_ext, d_when, d_status, d_npieces, d_viol, d_where);
 	if (A.g.kmax > NTG_MAX_ORDER || ntg_extrema_lds(A) > NTG_EXTREMA_LDS_MAX)
 		return fail(NTG_E_UNSUPPORTED, "the tables and work lists of this plan exceed " + std::to_string(NTG_EXTREMA_LDS_MAX / 1024) + " KiB of LDS");
-	A.ext = d_ext; A.when = d_when; A.status = d_status; A.npieces = d_npieces; A.viol = d_viol; A.where = d_where;
 	HIPCHK(hipSetDevice(p->device));
 	HIPCHK(ntg_launch_extrema(A, plan_ncu(p), (hipStream_t)stream));
 	return 0;
@@ -301,8 +308,7 @@ extern "C" int ntg_batch_separation(const ntg_plan *p, int batch, const double *
 	if (!d_x || !body_outs || !d_pairs) return fail(NTG_E_BADARG, "null argument");
 	if (ndim < 1 || ndim > NTG_SEP_MAXDIM) return fail(NTG_E_BADARG, "ndim must lie in 1 .. " + std::to_string(NTG_SEP_MAXDIM));
 	if (nbody < 1 || nbody > NTG_MAX_OUT) return fail(NTG_E_BADARG, "nbody must lie in 1 .. " + std::to_string(NTG_MAX_OUT));
-	if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(NTG_E_BADARG, "tol must be finite and >= 0");
-	if (max_depth < 0 || max_depth > NTG_EXTREMA_MAX_DEPTH) return fail(NTG_E_BADARG, "max_depth must lie in 0 .. " + std::to_string(NTG_EXTREMA_MAX_DEPTH));
+	if (int rc = cert_levels(tol, max_depth)) return rc;
 	const NtgDims &D = p->D;
 	for (int i = 0; i < nbody * ndim; i++) {
 		const int o = body_outs[i];
@@ -356,7 +362,8 @@ int forms_declare(const ntg_plan *p, const double *d_x, int nform, const int *fo
 	if (!d_x || !form_nterms || !terms) return fail(NTG_E_BADARG, "null argument");
 	if (nform < 0 || nform > NTG_FORM_MAXFORMS) return fail(NTG_E_BADARG, "nform must lie in 0 .. " + std::to_string(NTG_FORM_MAXFORMS));
 	if (nfp < 0) return fail(NTG_E_BADARG, "nfp must be >= 0");
-	if (int rc = cert_levels(tol, max_depth, sides)) return rc;
+	if (int rc = cert_levels(tol, max_depth)) return rc;
+	if (int rc = cert_sides(sides)) return rc;
 	const NtgDims &D = p->D;
 	const ntg_form_term *q = terms;
 	for (int f = 0; f < nform; f++) {
@@ -408,11 +415,11 @@ int forms_refuse(const ntg_plan *p, int batch, const FormCross &X)
 		                                   " of different basis classes: it has no common pieces");
 	return 0;
 }
-// the kernels' arguments but the launch figures
-void forms_args(const ntg_plan *p, int batch, const double *d_x, int nform, int nfp, double tol, int max_depth, int sides, FormArgs &A)
+// the kernels' arguments but the launch figures, the forms' parameters and the bounds
+void forms_args(const ntg_plan *p, int batch, const double *d_x, int nform, int nfp, FormArgs &A)
 {
-	cert_base(p, batch, d_x, nullptr, nullptr, A.g, A.koff, &A.nk);
-	A.nform = nform; A.nfp = nfp; A.max_depth = max_depth; A.sides = sides; A.tol = tol;
+	cert_base(p, batch, d_x, nullptr, nullptr, A.g, A.q.koff, &A.q.nk);
+	A.nform = nform; A.nfp = nfp;
 }
 }   // namespace
 
@@ -426,11 +433,11 @@ extern "C" int ntg_batch_forms(const ntg_plan *p, int batch, const double *d_x, 
 	if (int rc = forms_outputs(d_flo, d_fhi, "d_flo", "d_fhi", d_ext, d_when, d_status, d_npieces, d_viol, d_where)) return rc;
 	if (batch <= 0 || nform == 0) return 0;
 	if (int rc = forms_refuse(p, batch, X)) return rc;
-	forms_args(p, batch, d_x, nform, nfp, tol, max_depth, sides, A);
+	forms_args(p, batch, d_x, nform, nfp, A);
+	cert_bisect(A.q, tol, max_depth, sides, d_ext, d_when, d_status, d_npieces, d_viol, d_where);
 	if (A.g.kmax > NTG_MAX_ORDER || ntg_forms_lds(A) > NTG_EXTREMA_LDS_MAX)
 		return fail(NTG_E_UNSUPPORTED, "the tables and work lists of this call exceed " + std::to_string(NTG_EXTREMA_LDS_MAX / 1024) + " KiB of LDS");
 	A.fprm = d_fprm; A.flo = d_flo; A.fhi = d_fhi;
-	A.ext = d_ext; A.when = d_when; A.status = d_status; A.npieces = d_npieces; A.viol = d_viol; A.where = d_where;
 	HIPCHK(hipSetDevice(p->device));
 	HIPCHK(ntg_launch_forms(A, plan_ncu(p), (hipStream_t)stream));
 	return 0;
@@ -497,14 +504,14 @@ extern "C" int ntg_batch_ratios(const ntg_plan *p, int batch, const double *d_x,
 		R.dN = (unsigned char)deg[0]; R.dD = (unsigned char)deg[1]; R.DR = (unsigned char)std::max(deg[0], deg[1]);
 		dmax = std::max(dmax, (int)R.DR);
 	}
-	forms_args(p, batch, d_x, nform, nfp, tol, max_depth, sides, A.f);
+	forms_args(p, batch, d_x, nform, nfp, A.f);
+	cert_bisect(A.f.q, tol, max_depth, sides, d_ext, d_when, d_status, d_npieces, d_viol, d_where);
 	A.nratio = (unsigned char)nratio;
 	A.kr = (unsigned char)(dmax <= 12 && A.f.g.kmax <= 6 ? 13 : 25);
 	A.nw = (unsigned char)(ntg_ratios_lds(A, 4) <= NTG_EXTREMA_LDS_MAX ? 4 : 2);
 	if (A.f.g.kmax > NTG_MAX_ORDER || ntg_ratios_lds(A, A.nw) > NTG_EXTREMA_LDS_MAX)
 		return fail(NTG_E_UNSUPPORTED, "the tables and work lists of this call exceed " + std::to_string(NTG_EXTREMA_LDS_MAX / 1024) + " KiB of LDS");
 	A.f.fprm = d_fprm; A.f.flo = d_rlo; A.f.fhi = d_rhi;
-	A.f.ext = d_ext; A.f.when = d_when; A.f.status = d_status; A.f.npieces = d_npieces; A.f.viol = d_viol; A.f.where = d_where;
 	HIPCHK(hipSetDevice(p->device));
 	HIPCHK(ntg_launch_ratios(A, plan_ncu(p), (hipStream_t)stream));
 	return 0;

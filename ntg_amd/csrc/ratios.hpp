@@ -12,14 +12,14 @@
 //             point 1); the side of lower degree elevated to DR = max(dN, dD).
 //   levels    ext_levels' sequence (extrema.hpp) on pairs: the ends' quotients into U / V, a piece open if its quotients reach below U - tol
 //             (above V + tol) or a denominator point is <= 0; an end with denominator <= 0 stops the loop after its level: status POLE.
-// The level loop is written out here, not an instance of ext_levels.  ext_levels was generalised over a piece type (the list element's width,
-// load / store / split / range, the end-taking with a pole flag, and the exit after it under `if constexpr`), with the single polygon as the
-// default piece and every operation of the existing instances in its old order: the device assembly of kernels.hip then differed from the
-// parent's in 93 000 of 201 000 lines (other register numbers and another schedule through the extrema, separation and forms kernels).  The
-// maintainers' condition for one shared loop is identical assembly of the existing instances, so ext_levels stays as it is and ratio_levels
-// follows it line by line: the same level-0 rounds, the same ballots and list positions, the same retirement.  What differs is the piece
-// (two polygons of up to 25 points), its range (a row of divisions guarded by the denominator's sign) and the exit on a pole.  With a
-// denominator of ones the two loops take the same decisions on the same bits (n / 1.0 == n), which tests/test_gpu_ratios.py holds them to.
+// The level loop is written out here, not an instance of ext_levels: ratio_levels follows ext_levels line by line -- the same level-0
+// rounds, the same ballots and list positions, the same retirement, the same split routine (ext_split).  What differs is the piece (two
+// polygons of up to 25 points), its range (a row of divisions guarded by the denominator's sign) and the exit on a pole.  ext_levels was
+// twice generalised over a piece type.  The first time the condition was identical assembly of the existing instances, which no change
+// of the template meets.  The second time the condition was equal bits, no worse registers and a rate within the run-to-run spread: bits and
+// registers held, the ratio instances were even faster, but the single-polygon instances of extrema and separation lost 1 to 2 %.
+// With a denominator of ones the two loops take the same decisions on the same bits (n / 1.0 == n), which tests/test_gpu_ratios.py holds
+// them to; tests/golden/bisect_calls.npz holds both to recorded results.
 //
 //   ratios_shared_kernel  plans on their own grid: persistent workgroups of four waves (two where four work lists do not fit); the forms'
 //                         product tables, the chains' product tables, the extraction weights and the breaks of every basis class are built once
@@ -150,22 +150,6 @@ __device__ __forceinline__ void ratio_end(double n, double d, double t, double &
 	} else if (d <= 0.0) pole = true;
 }
 
-template <int KR>
-__device__ __forceinline__ void ratio_split(EnvPoly<KR> &Lp, EnvPoly<KR> &Rp, int Dl)
-{
-#pragma unroll
-	for (int s = 0; s < KR; s++) Lp.b[s] = 0.0;
-	Lp.b[0] = Rp.b[0];
-#pragma unroll
-	for (int r = 1; r < KR; r++) {
-		if (r <= Dl) {
-#pragma unroll
-			for (int s = 0; s < KR - r; s++) { if (s <= Dl - r) Rp.b[s] = 0.5 * (Rp.b[s] + Rp.b[s + 1]); }
-			Lp.b[r] = Rp.b[0];
-		}
-	}
-}
-
 // The definition's levels for one ratio, by one wave: ext_levels' sequence on pairs.  list: [NTG_EXTREMA_CAP][2 KR], numerator first
 template <int KM, int KR>
 __device__ __forceinline__ void ratio_levels(const ExtRun &Q, const ExtLds &M, const RatioArgs &A, const RatioRow &R, const double *pw, int lane, double (&res)[4], double (&tw)[2], int &status, int &npieces)
@@ -256,8 +240,8 @@ __device__ __forceinline__ void ratio_levels(const ExtRun &Q, const ExtLds &M, c
 		}
 		__builtin_amdgcn_wave_barrier();   // every parent is in registers before a child is stored
 		const int j = (int)(key >> 32), i = (int)(key & 0xffffffffll);
-		ratio_split<KR>(Lp.n, Rp.n, Dl);
-		ratio_split<KR>(Lp.d, Rp.d, Dl);
+		ext_split<KR>(Lp.n, Rp.n, Dl);
+		ext_split<KR>(Lp.d, Rp.d, Dl);
 		double llo = 0.0, lhi = 0.0, rlo = 0.0, rhi = 0.0;
 		if (on) {
 			const double t0 = ext_time(kn, hh, j, 2 * i, lam + 1, inv), tm = ext_time(kn, hh, j, 2 * i + 1, lam + 1, inv), t1 = ext_time(kn, hh, j, 2 * i + 2, lam + 1, inv);
@@ -318,34 +302,30 @@ __device__ __forceinline__ void ratio_problem(const RatioArgs &A, const ExtLds &
 {
 	const FormArgs &F = A.f;
 	const int nratio = ratio_u8(A.nratio);
-	const bool want_v = F.viol || F.where;
-	double av = 0.0, cv = 0.0; long long ak = -1, ck = -1;
+	ExtOut O{F.q, lane};
 	for (int r = 0; r < nratio; r++) {
 		const RatioRow &R = A.r[r];
 		const int cl = ratio_u8(R.cl);
 		const EnvClass C = F.g.c[cl];
-		const ExtRun Q{M.kns + F.koff[cl], M.tab + C.hoff, C.l, ratio_u8(R.DR), F.max_depth, F.sides, F.tol, INFINITY};
+		const ExtRun Q{M.kns + F.q.koff[cl], M.tab + C.hoff, C.l, ratio_u8(R.DR), F.q.max_depth, F.q.sides, F.q.tol, INFINITY};
 		double res[4], tw[2];
 		int status, npieces;
 		ratio_levels<KM, KR>(Q, M, A, R, pw, lane, res, tw, status, npieces);
 		const size_t at = (size_t)b * nratio + r;
-		if (lane == 0) {
-			if (F.ext) { F.ext[4 * at] = res[0]; F.ext[4 * at + 1] = res[1]; F.ext[4 * at + 2] = res[2]; F.ext[4 * at + 3] = res[3]; }
-			if (F.when) { F.when[2 * at] = tw[0]; F.when[2 * at + 1] = tw[1]; }
-			if (F.status) F.status[at] = status;
-			if (F.npieces) F.npieces[at] = npieces;
-		}
-		if (want_v) {
-			const double l = F.flo[at], u = F.fhi[at];
-			const double a = env_viol(l, u, res[1], res[2]), c = env_viol(l, u, res[0], res[3]);   // of the attained values, of the certified ones
-			env_take(av, ak, a, (a > 0.0 || a != a) ? (long long)r : -1ll);
-			env_take(cv, ck, c, (c > 0.0 || c != c) ? (long long)r : -1ll);
-		}
+		O.row(at, res, tw, status, npieces);
+		if (O.want_v()) O.fold(F.flo[at], F.fhi[at], res, r);
 	}
-	if (want_v && lane == 0) {
-		if (F.viol) { F.viol[2 * (size_t)b] = ak < 0 ? 0.0 : av; F.viol[2 * (size_t)b + 1] = ck < 0 ? 0.0 : cv; }
-		if (F.where) { F.where[2 * (size_t)b] = (int)ak; F.where[2 * (size_t)b + 1] = (int)ck; }
-	}
+	O.problem(b);
+}
+
+// the wave's part of the dynamic LDS, its list elements as wide as the instance's piece (npw comes from the kernel argument as a short: made
+// a scalar again); the chains' product tables lie behind the forms' in front: wl + NTG_FORM_WALL
+template <int KR>
+__device__ __forceinline__ ExtStage ratio_lds(const RatioArgs &A, double *base, int wave)
+{
+	BisectLds L = ntg_ratios_layout(A, 2 * KR);
+	L.front = __builtin_amdgcn_readfirstlane(L.front);
+	return L.wave(base, wave);
 }
 
 // (launched with 64 A.nw threads: the workgroup's size is the call's, not the instance's)
@@ -357,22 +337,18 @@ ratios_shared_kernel(RatioArgs A)
 	__shared__ unsigned int pas[NTG_FORM_PASCAL * NTG_FORM_PASCAL];
 	const FormArgs &F = A.f;
 	const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, NT = blockDim.x, NW = NT >> 6;
-	double *wt = reinterpret_cast<double *>(smem_raw);    // the forms' product tables
-	double *pw = wt + NTG_FORM_WALL;                      // the chains' product tables
-	double *tab = pw + __builtin_amdgcn_readfirstlane((int)A.npw);                           // weights and interval lengths of every basis class
-	double *kns = tab + F.g.ne;                           // breaks of every basis class
-	double *mine = kns + F.nk + (size_t)wave * (F.g.nC + F.nfp + NTG_EXTREMA_CAP * (2 * KR + 1));
-	double *xrow = mine, *frow = xrow + F.g.nC, *list = frow + F.nfp;
-	const ExtLds M{wt, tab, kns, xrow, frow, list, reinterpret_cast<long long *>(list + NTG_EXTREMA_CAP * 2 * KR)};
-	form_build_products(wt, pas, tid, NT);
+	const ExtStage S = ratio_lds<KR>(A, reinterpret_cast<double *>(smem_raw), wave);
+	const ExtLds M = S.view();
+	double *pw = S.wl + NTG_FORM_WALL;
+	form_build_products(S.wl, pas, tid, NT);
 	ratio_build_products(A, pw, tid, NT);
-	env_build_classes(F.g, tab, kns, F.koff, tid, NT);
+	env_build_classes(F.g, S.tab, S.kns, F.q.koff, tid, NT);
 	for (int b0 = blockIdx.x * NW; b0 < F.g.batch; b0 += gridDim.x * NW) {
 		const int b = b0 + wave;
 		if (b >= F.g.batch) continue;
 		__builtin_amdgcn_wave_barrier();   // the problem before is done with the rows
-		env_stage_rows(F.g, nullptr, b, xrow, nullptr, lane, 64);
-		form_stage_fprm(F, b, frow, lane);
+		env_stage_rows(F.g, nullptr, b, S.xrow, nullptr, lane, 64);
+		form_stage_fprm(F, b, S.prow, lane);
 		__builtin_amdgcn_wave_barrier();
 		ratio_problem<KM, KR>(A, M, pw, b, lane);
 	}
@@ -388,21 +364,19 @@ ratios_pp_kernel(RatioArgs A)
 	const FormArgs &F = A.f;
 	const EnvClass C = F.g.c[0];
 	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, NT = blockDim.x, NW = NT >> 6;
-	double *wt = reinterpret_cast<double *>(smem_raw);
-	double *pw = wt + NTG_FORM_WALL;
-	double *tab = pw + __builtin_amdgcn_readfirstlane((int)A.npw) + (size_t)wave * (F.g.ne + F.nk + F.g.nC + F.nfp + NTG_EXTREMA_CAP * (2 * KR + 1));
-	double *kns = tab + F.g.ne, *xrow = kns + F.nk, *frow = xrow + F.g.nC, *list = frow + F.nfp;
-	const ExtLds M{wt, tab, kns, xrow, frow, list, reinterpret_cast<long long *>(list + NTG_EXTREMA_CAP * 2 * KR)};
-	form_build_products(wt, pas, threadIdx.x, NT);
+	const ExtStage S = ratio_lds<KR>(A, reinterpret_cast<double *>(smem_raw), wave);
+	const ExtLds M = S.view();
+	double *pw = S.wl + NTG_FORM_WALL;
+	form_build_products(S.wl, pas, threadIdx.x, NT);
 	ratio_build_products(A, pw, threadIdx.x, NT);
 	const int per_pass = gridDim.x * NW;
 	for (int b0 = 0; b0 < F.g.batch; b0 += per_pass) {   // (the same trip count for every wave of the grid: the barriers below are uniform)
 		const int b = b0 + blockIdx.x * NW + wave;
 		const bool on = b < F.g.batch;
 		__syncthreads();
-		if (on) { env_stage_pp(F.g, nullptr, b, kns, xrow, nullptr, lane); form_stage_fprm(F, b, frow, lane); }
+		if (on) { env_stage_pp(F.g, nullptr, b, S.kns, S.xrow, nullptr, lane); form_stage_fprm(F, b, S.prow, lane); }
 		__syncthreads();
-		if (on) env_build(kns, C, tab + C.eoff, tab + C.hoff, lane, 64);
+		if (on) env_build(S.kns, C, S.tab + C.eoff, S.tab + C.hoff, lane, 64);
 		__syncthreads();
 		if (on) ratio_problem<KM, KR>(A, M, pw, b, lane);
 	}

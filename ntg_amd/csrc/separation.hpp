@@ -9,7 +9,8 @@
 //   level 0   sos_poly (envelope_sos.hpp) with the terms {dimension t, derivative deriv, shift 0, no parameter} on every knot interval: the
 //             polygon ntg_batch_extrema forms for such a row, bit for bit.
 //   levels    ext_levels (extrema.hpp) with sides = 1, in its threshold instance: a piece whose polygon does not reach below s2 = sep * sep
-//             retires at once, so a pair that keeps its distance ends at level 0.  No second copy of the level loop exists.
+//             retires at once, so a pair that keeps its distance ends at level 0.  No copy of the level loop is made for it (the one
+//             copy that exists is ratio_levels of ratios.hpp, for pairs of polygons).
 // separation_kernel: persistent workgroups of four waves; the term and class tables, the unfolded product tables, the extraction weights and
 // the breaks of the one class are built once into LDS; every wave then streams pairs with its own delta and work list.  After the set-up
 // there is no workgroup barrier (ext_levels says why its list needs none; delta is written and read by one wave, whose LDS operations
