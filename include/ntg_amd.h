@@ -232,7 +232,10 @@ void ntg_plan_clear_params(ntg_plan *p);
 
 /* SplineInterp (colloc.c:449-484) for a whole batch: the flat flag of every problem at ntimes points in time shared by
  * the batch (d_times [ntimes], inside the knot range of every output) -> d_z [batch][ntimes][nz], entry iz[o]+r =
- * D^r z_o(t).  This is the input of a flat-to-state map such as kincar_flat_reverse (kincar.c:68-92). */
+ * D^r z_o(t).  This is the input of a flat-to-state map such as kincar_flat_reverse (kincar.c:68-92).  The call is stream ordered: it
+ * never waits for the stream and reads no host memory after it returns, so it may sit in a captured stream.  Scratch (the basis at the
+ * times) is stream ordered, released on every path and does not grow with batch * ntimes * nz (per-problem grids: the batch goes through
+ * in chunks). */
 int ntg_batch_interp(const ntg_plan *p, int batch, const double *d_x, int ntimes, const double *d_times, double *d_z,
                      void *stream);
 /* The same with the layout of d_times stated by the caller instead of implied by the plan's state: problem b reads its ntimes points at

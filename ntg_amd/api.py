@@ -231,23 +231,22 @@ class Plan:
             pass
 
     # ---- setup tables (host copies) ----
-    def tables(self):
+    def _host_tables(self, fill):
+        """blk, off and A [nclin, nC] as fill(blk, off, A) -- ntg_plan_tables or ntg_plan_grid_tables -- writes them"""
         sp = self.spec
         nblk = sum(sp.nbps * k * d for k, d in zip(sp.order, sp.maxderiv))
         blk = np.zeros(nblk); off = np.zeros((sp.nout, sp.nbps), dtype=np.int32)
         A = np.zeros((sp.nC, max(sp.nclin, 1)))
-        _check(lib().ntg_plan_tables(self.h, blk.ctypes.data_as(dp), off.ctypes.data_as(ip), A.ctypes.data_as(dp)))
+        _check(fill(blk.ctypes.data_as(dp), off.ctypes.data_as(ip), A.ctypes.data_as(dp)))
         return dict(blk=blk, off=off, A=(A.T.copy() if sp.nclin else np.zeros((0, sp.nC))))
+
+    def tables(self):
+        return self._host_tables(lambda *out: lib().ntg_plan_tables(self.h, *out))
 
     def grid_tables(self, b: int):
         """tables() of problem b's grid after set_grids: its basis blocks, the plan's offsets, and A [nclin, nC] with the equality and
         inequality rows the solver reads for that problem.  Raises without per-problem grids or for b outside [0, batch)."""
-        sp = self.spec
-        nblk = sum(sp.nbps * k * d for k, d in zip(sp.order, sp.maxderiv))
-        blk = np.zeros(nblk); off = np.zeros((sp.nout, sp.nbps), dtype=np.int32)
-        A = np.zeros((sp.nC, max(sp.nclin, 1)))
-        _check(lib().ntg_plan_grid_tables(self.h, int(b), blk.ctypes.data_as(dp), off.ctypes.data_as(ip), A.ctypes.data_as(dp)))
-        return dict(blk=blk, off=off, A=(A.T.copy() if sp.nclin else np.zeros((0, sp.nC))))
+        return self._host_tables(lambda *out: lib().ntg_plan_grid_tables(self.h, int(b), *out))
 
     # ---- batched entry points; tensors are torch CUDA(HIP) float64/int32, contiguous ----
     def bounds(self, lower, upper):
@@ -299,16 +298,11 @@ class Plan:
         """Flat flag of every problem at the given times: x [batch, nC], times [ntimes] -> [batch, ntimes, nz].
         After set_grids: times [batch, ntimes], every problem at its own times on its own knots."""
         import torch
-        assert x.is_cuda and x.dtype == torch.float64 and x.is_contiguous() and times.is_cuda and times.dtype == torch.float64
+        _check_tensor(x, x.device)
+        if not (times.is_cuda and times.dtype == torch.float64):
+            raise NtgError("times must be a float64 tensor on the plan's device")
         batch = x.shape[0]
-        if times.dim() == 1:
-            stride = 0                       # one time vector for the batch (with per-problem grids: every problem on its own knots)
-        elif times.dim() == 2 and self.grid_batch and times.shape[0] == batch:
-            stride = times.shape[1]
-        elif times.dim() == 2:
-            raise NtgError("per-problem times [batch, ntimes] need per-problem grids of that batch (set_grids); pass a 1-D time vector")
-        else:
-            raise NtgError("times must be [ntimes] or, after set_grids, [batch, ntimes]")
+        stride = self._times_stride(batch, times)
         ntimes = times.shape[-1]
         z = torch.empty((batch, ntimes, self.spec.nz), dtype=torch.float64, device=x.device)
         _check(lib().ntg_batch_interp_strided(self.h, batch, _ptr(x), ntimes, _ptr(times.contiguous()), stride, _ptr(z), self._stream()))

@@ -9,7 +9,7 @@
 // on per-problem grids every problem brings its own.  The problem's coefficient row is staged in LDS once per problem, the flag of a
 // lane's time lives in registers (compile-time indices: every output of a family has maxderiv DM).
 // Reduction: the per-lane maximum carries its key row * ntimes + time index; 64 lanes by DPP / permlane exchanges, the waves of the
-// workgroup through LDS, the tiles of a problem through one (violation, key) pair per tile in HBM that check_final_kernel (kernels.hip)
+// workgroup through LDS, the tiles of a problem through one (violation, key) pair per tile in HBM that check_final_kernel (times.hip)
 // scans.  Maxima with a total order on ties (the smaller key wins): no floating-point atomics, the result does not depend on the order
 // in which anything ran.
 #pragma once

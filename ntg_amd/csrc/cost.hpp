@@ -7,7 +7,7 @@
 // its group; the tile's basis table transposed in LDS, the coefficient row staged per problem, the flag in registers.
 // Sum, in a fixed order: a lane's term w_i L_i (0 past the end of the tile); the 64 lanes of a wave by the butterfly lane ^ 1, 2, 4, 8,
 // 16, 32 (every lane ends with the same double: an addition's operands commute); the waves of the workgroup through LDS in index order;
-// the tiles of a problem through one partial per tile in HBM that cost_final_kernel (kernels.hip) adds in tile order.  No floating-point
+// the tiles of a problem through one partial per tile in HBM that cost_final_kernel (times.hip) adds in tile order.  No floating-point
 // atomics: the result does not depend on the order in which anything ran, nor on the batch around a problem.
 #pragma once
 #include "families.hpp"

@@ -1,6 +1,6 @@
 // eval.hpp -- the evaluation: augmented-Lagrangian rows, the cost passes (Z = M C, functors, banded gradient,
 // quadrature), the constraint rows and their Jacobian, and eval_kernel on top of them.  sqp_kernel.hpp evaluates
-// through eval_cost; kernels.hip uses cost_phase2 for the host-callback kernels.
+// through eval_cost; hostpath.hip uses cost_phase2 for the host-callback kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

@@ -54,7 +54,7 @@ constexpr int FAT_NLDS = 10, FAT_NLDS2 = 6, PPG_NLDS = 2, LEAN_NLDS = NTGW_LEAN_
 
 }   // namespace
 
-// Does the wave kernel take this solve, and with what launch shape / workspace?  (solve_setup of plan.cpp sizes the workspace with it.)
+// Does the wave kernel take this solve, and with what launch shape / workspace?  (solve_setup of plan_solve.cpp sizes the workspace with it.)
 bool ntg_wave_plan(const NtgDims &D, const NtgTables &T, const SolveParams &sp, int batch, int ncu, NtgWavePlan *w)
 {
 	if (getenv("NTG_AMD_NOWAVE")) return false;

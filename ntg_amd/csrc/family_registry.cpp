@@ -1,6 +1,6 @@
 // family_registry.cpp -- the one table of problem families: the built-in ones by id, and user families loaded at run time
-// (ntg_family_load / ntg_family_info of include/ntg_amd.h).  Every reader on the host -- plan construction, the launch dispatch of
-// kernels.hip -- asks ntg_family(id) and gets the family's descriptor (NtgFamily, family_module.hpp).
+// (ntg_family_load / ntg_family_info of include/ntg_amd.h).  Every reader on the host -- plan construction, the launch dispatch
+// below -- asks ntg_family(id) and gets the family's descriptor (NtgFamily, family_module.hpp).
 //
 // A module is a shared object built from include/ntg_amd_family.hpp (ntg_amd/family.py: build_module): the generic eval_kernel /
 // sqp_kernel instances of one family and one exported entry point that returns its descriptor (family_module.hpp).  Loading is a
@@ -44,6 +44,20 @@ const NtgFamily *ntg_family(int family)
 	if (family >= 0 && family < (int)(sizeof(g_builtin) / sizeof(g_builtin[0]))) return g_builtin[family];
 	return module_family(family);
 }
+
+// family dispatch: every family, built in (its translation unit fam_*.hip picks between its tuned -- compile-time nout / order -- instances
+// and the generic one) or loaded from a module, launches its eval_kernel, sqp_kernel, check_kernel, cost_kernel and verify_kernel
+// instances through its descriptor
+template <class Call> static hipError_t via_family(const NtgDims &D, Call call)
+{
+	const NtgFamily *f = ntg_family(D.family);
+	return f ? call(*f) : hipErrorInvalidValue;
+}
+hipError_t ntg_launch_eval(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a) { return via_family(D, [&](const NtgFamily &f) { return f.launch_eval(D, T, L, a); }); }
+hipError_t ntg_launch_sqp(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const SolveParams &sp, const SqpArgs &a) { return via_family(D, [&](const NtgFamily &f) { return f.launch_sqp(D, T, L, sp, a); }); }
+hipError_t ntg_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a) { return via_family(D, [&](const NtgFamily &f) { return f.launch_check(D, T, a); }); }
+hipError_t ntg_launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a) { return via_family(D, [&](const NtgFamily &f) { return f.launch_cost(D, T, a); }); }
+hipError_t ntg_launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a) { return via_family(D, [&](const NtgFamily &f) { return f.launch_verify(D, T, a); }); }
 
 static std::string hex64(unsigned long long v)
 {

@@ -1,6 +1,6 @@
 // kkt.hpp -- kkt_kernel: first-order optimality residuals of a batch of points (ntg_batch_kkt), fused: r = g - A' lam_A - J' lam_c on the
 // band ntg_batch_eval just wrote, the violation and signed complementarity of every linear and nonlinear row, the maxima per problem.
-// The dense Jacobian (ntg.c:250-253: the cJac NPSOL hands back next to clambda) is never formed.  Included by kernels.hip only: the pass is
+// The dense Jacobian (ntg.c:250-253: the cJac NPSOL hands back next to clambda) is never formed.  Included by certs.hip only: the pass is
 // the same for every family, built in or loaded.
 //
 // Mapping: one workgroup per problem, persistent workgroups walk the chunk.  r and x live in LDS for the whole pass.

@@ -1,6 +1,6 @@
 // lds_tables.hpp -- the LDS view of a plan: the carve-up of dynamic LDS (Smem), staging of the plan's tables into it,
 // Z = M C at a breakpoint (compute_z) with the channel-mask helpers, the column form's reader and the lanes' coefficient
-// map.  Used by eval.hpp, direction.hpp and sqp_kernel.hpp, and by the host-callback kernels of kernels.hip.
+// map.  Used by eval.hpp, direction.hpp and sqp_kernel.hpp, and by the host-callback kernels of hostpath.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ntg_dev.hpp"

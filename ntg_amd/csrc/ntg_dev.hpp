@@ -131,7 +131,7 @@ static inline bool ntg_all_d(const NtgDims &D, int d) { for (int o = 0; o < D.no
 // are handled by the generic instances only)
 static inline int ntg_uniform_order(const NtgDims &D, int nt, int ept) { return (D.uniform && D.nC <= ept * nt && D.nI == 0) ? D.order[0] : 0; }
 
-// byte offsets into dynamic LDS, computed on the host (kernels.hip: make_layout)
+// byte offsets into dynamic LDS, computed on the host (layout.cpp: ntg_make_layout)
 #define NTG_HRC_LDS 64   // quasi-Newton memories up to this many pairs keep the pair scalars (rho, c2) in LDS, when that costs no residency
 
 struct SmemLayout {
@@ -201,6 +201,22 @@ struct CostArgs {
 struct VerifyArgs {
 	CheckArgs t;
 	double *pval; long long *pkey;
+};
+
+// basis_kernel's output at the caller's times for problems [b0, b0 + nb) of the batch, as the host's one builder of these tables hands it
+// out (plan_times.cpp): the fields of that name in CheckArgs, with the meaning stated there.  The tables are indexed by the problem within
+// [b0, b0 + nb), everything of the caller's by the problem of the batch.
+struct TimeTables {
+	int b0, nb, pp;
+	int gbase[NTG_MAX_OUT];
+	long long pp_tab;
+	const double *tblk; const int *toff;
+};
+// interp_kernel (times.hip): the flat flag of the problems of t at ntimes times each; x [batch][nC], z [batch][ntimes][nz]
+struct InterpArgs {
+	TimeTables t;
+	int ntimes;
+	const double *x; double *z;
 };
 
 // kkt_kernel (kkt.hpp): problems [b0, b0 + nb) of the batch, grid persistent workgroups.  x, lam ([batch][nC + nclin + ncnln], the first nC

@@ -5,7 +5,7 @@
 // path alternates: HIP kernel updateZ -> host callbacks per breakpoint -> HIP kernel banded
 // assembly + quadrature.  The SQP iteration around it (what npsol_ does at ntg.c:250) runs on
 // the host with the same algorithm as the device sqp_kernel (linesearch.hpp is shared).
-// Everything numerical between "x" and "f, g, c, cJac" is computed by kernels.hip; with no
+// Everything numerical between "x" and "f, g, c, cJac" is computed by the kernels of hostpath.hip; with no
 // GPU, ntg() reports inform = 9 and prints why -- there is no CPU fallback.
 #include <hip/hip_runtime.h>
 #include <algorithm>

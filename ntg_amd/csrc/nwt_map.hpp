@@ -1,5 +1,5 @@
 // nwt_map.hpp -- the map of the memory of the structured Newton mode (newton.hpp) and the QP-based SQP step (qpdual.hpp) of sqp_kernel.  The host
-// sizes the workspace (plan.cpp, nwt_doubles) and the LDS area (kernels.hip, ntg_make_layout) from it.  sqp_kernel computes the same offsets in its
+// sizes the workspace (plan_solve.cpp, nwt_doubles) and the LDS area (layout.cpp, ntg_make_layout) from it.  sqp_kernel computes the same offsets in its
 // prologue (nwt_ksz, qp_pp, nwt_yall, qpbase, ...: DESIGN.md section 2 says why they stay there); whoever changes one side changes the other.
 // Plain host / device code: tests/drivers/nwt_map_drv.cpp prints it for a table of shapes.
 #pragma once

@@ -48,54 +48,34 @@ void ntg_plan_dense_A(const ntg_plan *p, double *A);
 // sets the message ntg_last_error() returns (this thread), returns code
 int ntg_fail(int code, const std::string &msg);
 
-// LDS carve-up: tables + (with_x) the coefficient vector + nvec further vectors of nC doubles.
+// ---- layout.cpp: the LDS carve-up, tables + (with_x) the coefficient vector + nvec further vectors of nC doubles ----
 //   eval_kernel   nvec 0 (the gradient is assembled into the x buffer once x is no longer needed)
 //   host path     nvec 1
 //   sqp_kernel    nvec 5 (xt, gp, gp+, d, g) with x -- or, BIG, nvec 1 (xt) without x: the rest lives in HBM/L2
 SmemLayout ntg_make_layout(const NtgDims &D, int nthreads, int nvec, int with_x, int hrc_pairs = 0, int qp = 0);
+
+// ---- family_registry.cpp: the family's instance of eval_kernel, sqp_kernel and the three time-tile kernels (check.hpp, cost.hpp,
+// verify.hpp), through its descriptor; hipErrorInvalidValue: no such family, or no instance for this shape ----
 hipError_t ntg_launch_eval(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const EvalArgs &a);
 hipError_t ntg_launch_sqp(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const SolveParams &sp, const SqpArgs &a);
-// one wavefront per problem (solve_wave.hpp, fam_kincar_wave.hip): does it take this solve, and its launch shape / HBM workspace
+hipError_t ntg_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a);
+hipError_t ntg_launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a);
+hipError_t ntg_launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a);
+
+// ---- fam_kincar_wave.hip: one wavefront per problem (solve_wave.hpp): does it take this solve, and its launch shape / HBM workspace ----
 struct NtgWavePlan { int fat, nwv, grid, cap, hbm_slots, nlds, ppg, noagpr; size_t lds, hist_doubles; };   // ppg: per-problem grids (wave-private value tables)
 bool ntg_wave_plan(const NtgDims &D, const NtgTables &T, const SolveParams &sp, int batch, int ncu, NtgWavePlan *w);
 hipError_t ntg_launch_sqp_wave(const NtgDims &D, const NtgTables &T, const SolveParams &sp, const SqpArgs &a, const NtgWavePlan &w);
+
+// ---- basis.hip: the basis at the breakpoints (or a caller's times) of ngrids grids, the banded linear rows, bounds() ----
 hipError_t ntg_launch_basis(int ngrids, int l, int k, int m, int d, int P, const double *knots, const double *bps,
                             long long knots_stride, long long bps_stride, double *blk, int *off, hipStream_t st);
-hipError_t ntg_launch_interp(const NtgDims &D, int batch, int ntimes, const double *x, const double *tblk, const int *toff,
-                             const int *tblk_base, double *z, hipStream_t st, int pp = 0);
-// coefficients on a finer knot grid (refine.hpp); pp: per-problem grids
-hipError_t ntg_launch_refine(const RefineArgs &A, int pp, int ncu, hipStream_t st);
-// bounds of the flag entries and linear trajectory rows over pieces of the knot intervals (envelope.hpp)
-hipError_t ntg_launch_envelope(const EnvArgs &A, int ncu, hipStream_t st);
-// bounds of the nonlinear trajectory rows declared as sums of squares over the same pieces (envelope_sos.hpp)
-hipError_t ntg_launch_envelope_sos(const SosArgs &A, int ncu, hipStream_t st);
-// minimum and maximum of the certifiable trajectory rows over the horizon, by bisection (extrema.hpp)
-hipError_t ntg_launch_extrema(const ExtArgs &A, int ncu, hipStream_t st);
-// smallest squared distance of pairs of bodies over the horizon, by the same bisection (separation.hpp)
-hipError_t ntg_launch_separation(const SepArgs &A, int ncu, hipStream_t st);
-// minimum and maximum over the horizon of quadratic forms of the flag declared at the call, by the same bisection (forms.hpp)
-hipError_t ntg_launch_forms(const FormArgs &A, int ncu, hipStream_t st);
-// minimum and maximum over the horizon of ratios of products of such forms, by the same bisection on pairs of polygons (ratios.hpp)
-hipError_t ntg_launch_ratios(const RatioArgs &A, int ncu, hipStream_t st);
-// trajectory rows at arbitrary times (check.hpp): the family's check_kernel instance, then the maximum over a problem's time tiles
-hipError_t ntg_launch_check(const NtgDims &D, const NtgTables &T, const CheckArgs &a);
-hipError_t ntg_launch_check_final(int batch, int ntiles, int ntimes, const double *pviol, const long long *pkey, double *viol, int *where, hipStream_t st);
-// running cost at arbitrary times (cost.hpp): the family's cost_kernel instance, launched like check_kernel, then the sum over a problem's time tiles
-hipError_t ntg_launch_cost(const NtgDims &D, const NtgTables &T, const CostArgs &a);
-hipError_t ntg_launch_cost_final(int batch, int ntiles, const double *pcost, double *cost, hipStream_t st);
-// a family's derivatives against central differences at the breakpoints (verify.hpp): the family's verify_kernel instance, launched like
-// check_kernel with the breakpoints as the times, then the maximum over a problem's tiles and the keys taken apart
-hipError_t ntg_launch_verify(const NtgDims &D, const NtgTables &T, const VerifyArgs &a);
-hipError_t ntg_launch_verify_final(int batch, int ntiles, int nbps, int nz, const double *pval, const long long *pkey, double *err, int *where, double *leak,
-                                   int *leak_where, hipStream_t st);
-// first-order optimality residuals (kkt.hpp): one chunk of problems, after ntg_launch_eval (mode 2) and ntg_launch_bounds filled its scratch
-hipError_t ntg_launch_kkt(const NtgDims &D, const NtgTables &T, const KktArgs &a);
-hipError_t ntg_launch_kincar_reverse(long long nsamp, int nz, int ncars, double wheelbase, int reverse_gear, const double *z, double *out, hipStream_t st);
-hipError_t ntg_launch_count_notconv(int batch, const int *inform, int *count, hipStream_t st);
 hipError_t ntg_launch_linrows(const NtgDims &D, const NtgTables &T, const double *lic, const double *ltc,
                               const double *lfc, double *aband, int *rbp, hipStream_t st);
 hipError_t ntg_launch_bounds(const NtgDims &D, int batch, const double *lo, const double *up, double *bl, double *bu,
                              hipStream_t st);
+
+// ---- hostpath.hip: the kernels around the host callbacks of ntg() (ntg_host.cpp) ----
 hipError_t ntg_launch_hostz(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const double *x, u64 mI,
                             u64 mT, u64 mF, double *Z, hipStream_t st);
 hipError_t ntg_launch_hostcost(const NtgDims &D, const NtgTables &T, const SmemLayout &L, const double *fT,
@@ -103,8 +83,38 @@ hipError_t ntg_launch_hostcost(const NtgDims &D, const NtgTables &T, const SmemL
                                hipStream_t st);
 hipError_t ntg_launch_hostcon(const NtgDims &D, const NtgTables &T, const double *dc, double *jband, double *cjac,
                               hipStream_t st);
+
+// ---- times.hip: the flat flag at times (one chunk of problems), the last step of each time-tile reduction over a problem's tiles, the
+// kinematic car's flat-to-state map ----
+hipError_t ntg_launch_interp(const NtgDims &D, const InterpArgs &a, hipStream_t st);
+hipError_t ntg_launch_check_final(int batch, int ntiles, int ntimes, const double *pviol, const long long *pkey, double *viol, int *where, hipStream_t st);
+hipError_t ntg_launch_cost_final(int batch, int ntiles, const double *pcost, double *cost, hipStream_t st);
+hipError_t ntg_launch_verify_final(int batch, int ntiles, int nbps, int nz, const double *pval, const long long *pkey, double *err, int *where, double *leak,
+                                   int *leak_where, hipStream_t st);
+hipError_t ntg_launch_kincar_reverse(long long nsamp, int nz, int ncars, double wheelbase, int reverse_gear, const double *z, double *out, hipStream_t st);
+
+// ---- mpc.hip: the receding-horizon shift of coefficients and bounds, of the multiplier estimates, and the count of unconverged problems ----
+hipError_t ntg_launch_mpc_shift(const NtgDims &D, const NtgTables &T, int batch, int sbp, int sknot, const double *lic,
+                                double *x, double *lower, double *upper, hipStream_t st);
 hipError_t ntg_launch_mpc_shift_lambda(const NtgDims &D, int batch, int sbp, double *alw, hipStream_t st);
-// per-problem grids: device-side setup algebra (grids.hip)
+hipError_t ntg_launch_count_notconv(int batch, const int *inform, int *count, hipStream_t st);
+
+// ---- certs.hip: the kernels written once for every family -- the time certificates (envelope.hpp, envelope_sos.hpp, extrema.hpp,
+// separation.hpp, forms.hpp), refine (refine.hpp; pp: per-problem grids) and one chunk of kkt (kkt.hpp, after ntg_launch_eval in mode 2
+// and ntg_launch_bounds filled its scratch); hipErrorInvalidValue: the tables exceed the LDS ----
+hipError_t ntg_launch_envelope(const EnvArgs &A, int ncu, hipStream_t st);
+hipError_t ntg_launch_envelope_sos(const SosArgs &A, int ncu, hipStream_t st);
+hipError_t ntg_launch_extrema(const ExtArgs &A, int ncu, hipStream_t st);
+hipError_t ntg_launch_separation(const SepArgs &A, int ncu, hipStream_t st);
+hipError_t ntg_launch_forms(const FormArgs &A, int ncu, hipStream_t st);
+hipError_t ntg_launch_refine(const RefineArgs &A, int pp, int ncu, hipStream_t st);
+hipError_t ntg_launch_kkt(const NtgDims &D, const NtgTables &T, const KktArgs &a);
+
+// ---- ratios.hip: minimum and maximum over the horizon of ratios of products of forms, by the certificates' bisection on pairs of
+// polygons (ratios.hpp) ----
+hipError_t ntg_launch_ratios(const RatioArgs &A, int ncu, hipStream_t st);
+
+// ---- grids.hip: per-problem grids, the device-side setup algebra ----
 struct NtgGridLin {
 	const double *blk, *linrows; const int *plan_off, *erow, *csr_ptr, *csr_col, *csc_ptr, *csc_row, *sinv_ptr, *sinv_col, *q_col, *q_row2coef;
 	const unsigned char *q_pad; double *csr_val, *csc_val, *sinv_val, *q_val; int *err;
@@ -123,5 +133,3 @@ hipError_t ntg_launch_grid_prec(const NtgDims &D, int batch, const NtgGridPrec &
 // outputs' band factors of every grid, from the per-problem channel rows and breakpoints
 struct NtgGridNwt { const double *rowv, *bps; const int *plan_off; const short *lo, *hi; double *k0, *lf; int *err; int k0_sz, lf_sz; };
 hipError_t ntg_launch_grid_nwt(const NtgDims &D, int batch, const NtgGridNwt &g, hipStream_t st);
-hipError_t ntg_launch_mpc_shift(const NtgDims &D, const NtgTables &T, int batch, int sbp, int sknot, const double *lic,
-                                double *x, double *lower, double *upper, hipStream_t st);

@@ -1,11 +1,9 @@
 // plan_cost.cpp -- ntg_batch_cost: the running cost of a batch of trajectories at arbitrary times, summed under the caller's quadrature
-// weights (cost.hpp).  The walk over the batch is ntg_batch_check's (time_tile_walk, plan.cpp): the basis at the times in stream-ordered
+// weights (cost.hpp).  The walk over the batch is ntg_batch_check's (time_tile_walk, plan_times.cpp): the basis at the times in stream-ordered
 // scratch, per-problem grids in chunks of problems under the scratch cap.  Scratch of its own: one partial sum per problem and tile of
 // NTG_CHECK_NT times, added in tile order by cost_final_kernel.  Its owner (StreamScratch) releases it on every path.
 #include "plan_priv.hpp"
 #include "family_module.hpp"
-
-#define NTG_COST_SCRATCH_CAP (64ll << 20)
 
 static int batch_cost(const ntg_plan *p, int batch, const double *d_x, int ntimes, const double *d_times, const double *d_weights,
                       long long times_stride, double *d_cost, double *d_vals, void *stream, long long scratch_cap)
@@ -38,7 +36,7 @@ static int batch_cost(const ntg_plan *p, int batch, const double *d_x, int ntime
 extern "C" int ntg_batch_cost(const ntg_plan *p, int batch, const double *d_x, int ntimes, const double *d_times, const double *d_weights,
                               long long times_stride, double *d_cost, double *d_vals, void *stream)
 {
-	return batch_cost(p, batch, d_x, ntimes, d_times, d_weights, times_stride, d_cost, d_vals, stream, NTG_COST_SCRATCH_CAP);
+	return batch_cost(p, batch, d_x, ntimes, d_times, d_weights, times_stride, d_cost, d_vals, stream, NTG_TIME_SCRATCH_CAP);
 }
 // diagnostic: the same with the scratch cap of the per-problem time tables stated by the caller (tests force several chunks with it)
 extern "C" int ntg_debug_batch_cost(const ntg_plan *p, int batch, const double *d_x, int ntimes, const double *d_times, const double *d_weights,

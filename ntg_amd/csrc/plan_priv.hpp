@@ -1,16 +1,21 @@
 // plan_priv.hpp -- what the host translation units behind include/ntg_amd.h share and nobody else sees: error reporting, the owners
 // of device allocations and of stream-ordered scratch, the small algebra used by more than one of them, and the functions one unit offers
 // the others.
-//   plan.cpp        entry points of the batched calls, the solve setup (which kernel, which layout, which part of the workspace)
+//   plan.cpp        error handling, device queries, and the calls that are one launch each: eval (and its launch shape), bounds,
+//                   kincar_reverse, basis_batch
+//   plan_solve.cpp  ntg_batch_solve and the receding-horizon calls; the solve setup (which kernel, which layout, which part of the workspace)
+//   plan_times.cpp  the calls at the caller's times: the one builder of the basis tables at the times, ntg_batch_interp, the walk of the
+//                   time-tile kernels, ntg_batch_check
+//   plan_cost.cpp   ntg_batch_cost: the running cost of a batch at arbitrary times under a quadrature
+//   plan_verify.cpp ntg_batch_verify: a family's analytic derivatives against central differences at the breakpoints
 //   plan_build.cpp  ntg_plan_create: spec validation, basis classes, channel tables, linear rows; the structured-Newton tables; the
 //                   preconditioner; plan queries
 //   plan_grids.cpp  per-problem grids (ntg_plan_set_grids) and per-problem family parameters
 //   plan_refine.cpp ntg_batch_refine: which pairs of plans it takes, the break conditions on shared grids, the launch
 //   plan_kkt.cpp    ntg_batch_kkt: first-order optimality residuals of a batch
-//   plan_cost.cpp   ntg_batch_cost: the running cost of a batch at arbitrary times under a quadrature
-//   plan_verify.cpp ntg_batch_verify: a family's analytic derivatives against central differences at the breakpoints
 //   plan_cert.cpp   the time certificates ntg_batch_envelope, ntg_batch_envelope_sos and ntg_batch_extrema: bounds of the flag entries and
 //                   of the trajectory rows that hold over the whole horizon; their common refusals, row tables and kernel arguments
+// (layout.cpp and family_registry.cpp are host units too; they need plan.hpp only.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -138,16 +143,25 @@ static inline int block_output(const NtgDims &D, int q)
 int precond_block(const std::vector<double> &H0, const std::vector<double> &A, int m, int n, std::vector<double> &W0);
 int build_precond(ntg_plan *p);   // the caller holds ntg_plan::precond_mutex
 int plan_ncu(const ntg_plan *p);   // compute units of the plan's device (plan.cpp)
+// workgroup size of the evaluation, and of the solve unless the options or the structured Newton mode ask for another: breakpoints and
+// coefficients are spread over the lanes
+static inline int auto_threads(const NtgDims &D) { return (D.P <= 128 && D.nC <= 512) ? 128 : (D.nC <= 1024 ? 256 : 512); }
 // per-problem family parameters (plan_grids.cpp): doubles per problem the plan's family needs; are they set, for this batch?
 int param_count(const ntg_plan *p);
 int check_params(const ntg_plan *p, int batch);
 // launch shape of the evaluation of `batch` problems: workgroup size, persistent grid, LDS layout; 0 or an error code  (plan.cpp)
 struct EvalShape { int nt, grid; SmemLayout L; };
 int eval_shape(const ntg_plan *p, int batch, EvalShape *s);
-// the calls on time tiles (ntg_batch_check in plan.cpp, ntg_batch_cost, ntg_batch_verify): what they refuse about the batch, the stride,
-// the parameters and the LDS; the walk over the batch with the basis at the times in stream-ordered scratch, launch() once per chunk of
-// problems (plan.cpp); and their common tail: the walk, the final kernel behind it (the walk's tables are released before it is
-// enqueued), and what the call returns.
+// ---- the calls at the caller's times (plan_times.cpp) ----
+// The builder of the time tables: basis_kernel's output at the times in stream-ordered scratch that it owns and releases when it returns;
+// use() once per chunk of problems with the chunk's tables by value (TimeTables, ntg_dev.hpp).  Shared grid: one set of tables, one
+// chunk.  Per-problem grids: chunks whose tables stay under scratch_cap bytes, at least one problem each.  The one cap of every call:
+#define NTG_TIME_SCRATCH_CAP (64ll << 20)
+hipError_t time_tables_walk(const ntg_plan *p, int batch, int ntimes, const double *d_times, long long times_stride, long long scratch_cap,
+                            hipStream_t st, const std::function<hipError_t(const TimeTables &)> &use);
+// The calls on time tiles (ntg_batch_check, ntg_batch_cost, ntg_batch_verify): what they refuse about the batch, the stride, the
+// parameters and the LDS; the walk over the builder's chunks, launch() once per chunk; and their common tail: the walk, the final
+// kernel behind it (the walk's tables are released before it is enqueued), and what the call returns.
 //   a     the tile fields of the call's arguments: the caller set x and st, the walk fills the rest before every launch
 //   what  the call's name in the refusal of a shape without an instance
 //   e     the outcome of the caller's own allocations: a failure skips the walk and is reported like one of its own

@@ -1,12 +1,10 @@
 // plan_verify.cpp -- ntg_batch_verify: the analytic derivatives of the plan's family against central differences, at the breakpoints
-// (verify.hpp).  The walk over the batch is ntg_batch_check's (time_tile_walk, plan.cpp) with the breakpoints as the times -- the plan's,
+// (verify.hpp).  The walk over the batch is ntg_batch_check's (time_tile_walk, plan_times.cpp) with the breakpoints as the times -- the plan's,
 // or after ntg_plan_set_grids every problem's own: the basis at them in stream-ordered scratch, per-problem grids in chunks of problems
 // under the scratch cap.  Scratch of its own: one (value, key) pair per problem, tile of NTG_CHECK_NT breakpoints, slot and kind, which
 // verify_final_kernel scans in tile order.  Its owner (StreamScratch) releases it on every path.
 #include "plan_priv.hpp"
 #include "family_module.hpp"
-
-#define NTG_VERIFY_SCRATCH_CAP (64ll << 20)
 
 static int batch_verify(const ntg_plan *p, int batch, const double *d_x, double *d_err, int *d_where, double *d_leak, int *d_leak_where,
                         void *stream, long long scratch_cap)
@@ -41,7 +39,7 @@ static int batch_verify(const ntg_plan *p, int batch, const double *d_x, double 
 extern "C" int ntg_batch_verify(const ntg_plan *p, int batch, const double *d_x, double *d_err, int *d_where, double *d_leak, int *d_leak_where,
                                 void *stream)
 {
-	return batch_verify(p, batch, d_x, d_err, d_where, d_leak, d_leak_where, stream, NTG_VERIFY_SCRATCH_CAP);
+	return batch_verify(p, batch, d_x, d_err, d_where, d_leak, d_leak_where, stream, NTG_TIME_SCRATCH_CAP);
 }
 // diagnostic: the same with the scratch cap of the per-problem time tables stated by the caller (tests force several chunks with it)
 extern "C" int ntg_debug_batch_verify(const ntg_plan *p, int batch, const double *d_x, double *d_err, int *d_where, double *d_leak,

@@ -1,5 +1,5 @@
 // ratios.hip -- the kernels of ntg_batch_ratios (ratios.hpp) and their launcher: a translation unit of its own, because the instances carry
-// polygons of 13 or 25 points for both plan sizes and would double the build time of kernels.hip.
+// polygons of 13 or 25 points for both plan sizes and would double the build time of certs.hip.
 //
 //   ratios_shared_kernel / ratios_pp_kernel <KM, KR>   KM = 6 or NTG_MAX_ORDER: the forms' polygons, as in forms.hpp; KR = 13 or 25: points of the
 //                                                     pair's polygons, the smallest that holds the largest degree of the call's ratios

@@ -7,7 +7,7 @@
 // and d[0] is the result.  Every denominator spans the non-empty interval [tau[mu], tau[mu+1]].  The form (1 - a) d0 + a d1 is kept on
 // purpose: on identical grids every a that reaches d[0] is exactly 1, so the coefficients come back bit for bit.
 // Neither augmented knot vector is materialised: both are read through the fine break sequence (RefKnots below, the rule of AugKnots in
-// kernels.hip); a coarse break takes the value of its partner among the fine breaks, so the inclusion of the knot vectors is exact although
+// basis.hip); a coarse break takes the value of its partner among the fine breaks, so the inclusion of the knot vectors is exact although
 // the two break sequences were accumulated separately (linspace) and differ in the last bits.
 //
 //   refine_shared_kernel  both plans on their own grids: the weights do not depend on the problem.  A workgroup runs the triangle on the k

@@ -22,7 +22,7 @@
 // Reduction: a candidate is (value, key) with key = (function * nbps + breakpoint) * nz + entry; the larger value wins, on equal
 // values the smaller key, a NaN beats every number (ntg_batch_kkt's rule) and among NaNs the smaller key wins: a total order, so the
 // butterfly over the 64 lanes (lane ^ 1, 2, 4, 8, 16, 32), the waves through LDS in index order and the tiles of a problem through one
-// partial per tile (verify_final_kernel, kernels.hip) give a result that does not depend on the order in which anything ran.
+// partial per tile (verify_final_kernel, times.hip) give a result that does not depend on the order in which anything ran.
 #pragma once
 #include "families.hpp"
 #include "wave_ops.hpp"

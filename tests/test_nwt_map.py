@@ -1,7 +1,7 @@
 """csrc/nwt_map.hpp, the one memory map of the structured Newton mode and the QP-based SQP step, compiled for the host
 (tests/drivers/nwt_map_drv.cpp) over a table of shapes -- one and several groups, two-sided on and off, with and without free outputs, QP on
 and off, 128 / 256 / 512 lanes, odd nC and ncnln -- against the three formulas it replaced, restated here (they are the specification):
-the workspace doubles of plan.cpp's nwt_doubles, the LDS bytes and the reduction scratch of ntg_make_layout, and the offsets sqp_kernel
+the workspace doubles of plan_solve.cpp's nwt_doubles, the LDS bytes and the reduction scratch of ntg_make_layout, and the offsets sqp_kernel
 computed for itself.  The areas of each region follow one another without overlap and end at the totals."""
 import os
 import subprocess
@@ -40,7 +40,7 @@ def test_table_covers_the_layouts(rows):
 
 
 def test_workspace_is_nwt_doubles(rows):
-    """plan.cpp, nwt_doubles (per problem)"""
+    """plan_solve.cpp, nwt_doubles (per problem)"""
     for r in rows:
         rev = r["ngrp"] * (16 * r["jb"] + 48) * (r["hb"] + 1) if r["tw"] else 0
         qa = qp_maxa(r["ngrp"], r["nt"])
@@ -49,7 +49,7 @@ def test_workspace_is_nwt_doubles(rows):
 
 
 def test_lds_is_the_layouts(rows):
-    """kernels.hip, ntg_make_layout: the area behind SmemLayout::nwt_y and the reduction scratch"""
+    """layout.cpp, ntg_make_layout: the area behind SmemLayout::nwt_y and the reduction scratch"""
     for r in rows:
         vec = 16 * (r["ja"] + 3) + 48 + 16 * (r["jb"] + 3) + 48 if r["tw"] else 16 * ((r["ng"] + 15) // 16) + 48
         steady = r["ngrp"] * (vec + (2 if r["tw"] else 1) * NWT_PANEL) * 8 + r["nfo"] * (16 * ((r["ngf"] + 15) // 16) + 48) * 8

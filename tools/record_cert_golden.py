@@ -1,10 +1,11 @@
 """Record a bitwise fixture of the time certificates with the library named by NTG_AMD_LIB -- meant for the library of the commit BEFORE a
 change that must not move a bit.
 
-  NTG_AMD_LIB=LIB python tools/record_cert_golden.py [cert|bisect] [OUT.npz]     on the GPU
+  NTG_AMD_LIB=LIB python tools/record_cert_golden.py [cert|bisect|interp] [OUT.npz]     on the GPU
 
   cert     tests/golden/cert_calls.npz (tests/test_gpu_cert_golden.py): envelope, envelope_sos, extrema; cases in tests/cert_golden_cases.py
-  bisect   tests/golden/bisect_calls.npz (tests/test_gpu_bisect_golden.py): separation, forms, ratios; cases in tests/bisect_golden_cases.py"""
+  bisect   tests/golden/bisect_calls.npz (tests/test_gpu_bisect_golden.py): separation, forms, ratios; cases in tests/bisect_golden_cases.py
+  interp   tests/golden/interp_calls.npz (tests/test_gpu_interp_golden.py): Plan.interp, inputs and flags; cases in tests/interp_golden_cases.py"""
 import importlib
 import os
 import sys
@@ -12,7 +13,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-SETS = {"cert": ("cert_golden_cases", "cert_calls.npz"), "bisect": ("bisect_golden_cases", "bisect_calls.npz")}
+SETS = {"cert": ("cert_golden_cases", "cert_calls.npz"), "bisect": ("bisect_golden_cases", "bisect_calls.npz"),
+        "interp": ("interp_golden_cases", "interp_calls.npz")}
 
 
 def main():
