@@ -42,6 +42,8 @@
  *                        forms of the flag declared at the call (speed^2, the turning numerator, weighted thrust, ellipses, rows of a module)
  *   ntg_batch_ratios     nothing in the reference bounds the steering angle between samples; examples/kincar.c:68-92 kincar_flat_reverse computes it
  *                        per sample: the minimum and maximum over the horizon of ratios of products of such forms (curvature^2, lateral acceleration^2)
+ *   ntg_batch_trig       nothing in the reference bounds a row between samples; constraints.c:119-160 evaluates the manipulator's rows at the
+ *                        breakpoints only: the minimum and maximum over the horizon of sums of sines and cosines of the flag (a tip's height and reach)
  *   ntg_batch_kincar_reverse  examples/kincar.c:68-92 kincar_flat_reverse (the example's flat-to-state map), for a batch
  *   ntg(), npsoloption(), linspace(), SplineInterp(), matrix helpers: see include/ntg.h
  */
@@ -753,6 +755,76 @@ int ntg_batch_ratios(const ntg_plan *p, int batch, const double *d_x,
                      const double *d_rlo, const double *d_rhi,
                      double *d_ext, double *d_when, int *d_status, int *d_npieces,
                      double *d_viol, int *d_where, void *stream);
+
+/* Certified extrema of SINES AND COSINES of the flat flag, declared at the call: ntg_batch_forms' statement -- the global minimum and maximum
+ * over the horizon, each enclosed to a tolerance and each with a witness time -- for
+ *   h_j(z) = sum_t w_t g_t(theta_t(z)),   theta_t = sum_i coef[i] * z[ent[i]] + phase + (pp >= 0 ? fprm_b[pp] : 0),
+ * g_t = sin, cos or the identity by kind.  The tip height sin qa + sin(qa + qb) + sin(qa + qb + qc) of a manipulator, its x-coordinate (cosines),
+ * a wall in front of the arm n . tip <= d (sines with a phase), a heading angle.  These are no polynomials in the flag, so none of the other
+ * certificates takes them.  On a piece of a knot interval the angle theta_t is a polynomial with a Bezier polygon Theta_t; about the centre c of
+ * that polygon sin(theta) = sin c + cos c (theta - c) + R with |R| <= rho^2 / 2, rho the polygon's radius: the linear part is a polygon again,
+ * and the remainder is of the same order in the piece width as the gap between a polygon and its function, so ntg_batch_extrema's bisection
+ * converges as it does for polynomial rows.  No family callback runs: every plan is served (built-in families, loaded modules, per-problem grids).
+ * Forms.  form_nterms [nform] and terms are HOST arrays, copied by the call; terms is concatenated form after form.  Entries ent[i] are flag
+ * entries iz[o] + r in the layout of ntg_batch_interp; 1 <= nent <= NTG_TRIG_MAXENT.  fprm_b is row b of d_fprm [batch][nfp], the call's own
+ * per-problem parameters.  Every entry of a form belongs to one basis class; different forms may use different classes.
+ * 1 <= terms per form <= NTG_TRIG_MAXTERMS, 0 <= nform <= NTG_TRIG_MAXFORMS.
+ * Outputs as for ntg_batch_forms, any may be NULL but not all six: d_ext [batch][nform][4] = {min_lo, min_hi, max_lo, max_hi}, d_when
+ * [batch][nform][2], d_status [batch][nform] (NTG_EXTREMA_OK / _DEPTH / _FULL / _NAN), d_npieces [batch][nform], d_viol [batch][2] =
+ * {attained, certified} and d_where [batch][2] against d_flo / d_fhi [batch][nform].
+ * Definition, per problem and per form.  Every product and every sum below is rounded separately (no fused multiply-add).
+ * 1. Level-0 angle polygons, knot interval j of the form's class.  The control points of each entry come from steps 1-3 of ntg_batch_envelope at
+ *    nsub = 0 with ntg_batch_forms' arithmetic (rule 1a there, shift 0): degree k - 1 - r, a derivative of order >= k is the single point 0.
+ *    Each entry polygon is multiplied by its coef (one rounding), elevated with the formula ntg_batch_envelope states, and the entry polygons
+ *    are summed in declared order; then phase + fprm_b[pp] is added to every point.  A SIN or COS term is elevated to D_j, the largest entry
+ *    degree of the whole form (D_j <= 9).  A LIN term is elevated to the largest entry degree of the term, multiplied by w_t (one rounding),
+ *    elevated to D_j and added to the form's linear polygon Lambda, LIN terms in declared order: rule 1d of ntg_batch_forms.  A piece carries
+ *    the angle polygons Theta_t,0..D of its SIN and COS terms and, if the form has a LIN term, Lambda: at most NTG_TRIG_MAXTERMS polygons.
+ * 2. Piece enclosure.  For a SIN or COS term lo_t = min_m Theta_t,m, hi_t = max_m Theta_t,m, c_t = 0.5 * (lo_t + hi_t),
+ *    rho_t = max(hi_t - c_t, c_t - lo_t), (S, C) = sincos(c_t), and T_t,m = w_t * (S + C * (Theta_t,m - c_t)) for SIN,
+ *    T_t,m = w_t * (C - S * (Theta_t,m - c_t)) for COS.  P_m = 0 + sum_t T_t,m over the SIN and COS terms in declared order, + Lambda_m last;
+ *    r = sum_t |w_t| * rho_t * rho_t * 0.5 over the same terms, from 0; plo = min_m P_m - r, phi = max_m P_m + r.  If the form has no LIN
+ *    term, plo = max(plo, -W) and phi = min(phi, W) with W = sum_t |w_t| (a NaN stays).
+ * 3. Ends.  The value at a piece end is 0 + sum_t w_t g_t(Theta_t,end) over the SIN and COS terms in declared order, + Lambda_end last;
+ *    Theta_t,end is the polygon's first or last point, which de Casteljau carries over bit for bit.  These are the attained values U / V, with
+ *    the times and the smaller-time tie rule of rule 2 of ntg_batch_extrema.
+ * 4. Levels, results, NaN, violation.  Rules 2 to 7 of ntg_batch_extrema, unchanged.  Every polygon of an open piece is halved with
+ *    0.5 * (a + b).  npieces counts pieces: l at level 0, two per open piece afterwards.  Every form is certified: there is no status NONE.
+ * 5. A form whose terms are all LIN with nent = 1, coef = 1.0, phase = 0 and pp = -1 returns what ntg_batch_forms returns for the linear
+ *    terms w (z[u] - 0): ext, when, status and npieces are equal under ==.  That is why the LIN terms share one polygon.
+ * Rounding.  With S_i as in ntg_batch_forms for entry i, A_t = |phase_t| + |fprm_b[pp]| + sum_i |coef_i| S_i bounds the angle of term t.  A
+ * point of Theta_t carries at most 2^-41 A_t: 2^-42 sum_i |coef_i| S_i from the entries, the elevations and at most 270 halvings the rest
+ * (counted as for ntg_batch_forms).  The enclosure of rule 2 is exact mathematics for the polygon it is given, sin and cos have the Lipschitz
+ * constant 1, the device sincos is taken at 4 ulp, and the roundings of rule 2 add less than 2^-49 (1 + A_t) per term and 2^-51 A_t^2 for the
+ * remainder.  The slack of a form is
+ *   slack_j = 2^-39 * sum_t |w_t| (1 + A_t)      for A_t <= 2^11; a term with a larger A_t adds 2^-51 |w_t| A_t^2     (DESIGN.md 2n).
+ * Figures are returned as computed; the slack is part of the contract.
+ * Arguments.  tol, max_depth and sides as in ntg_batch_extrema.  Stream ordered, without scratch in HBM and without floating-point atomics: a
+ * wavefront owns a problem and walks its forms, lane p owns open piece p.  Results are bit-identical from call to call and independent of
+ * the batch around a problem.  Per-problem grids are honoured: the batch must be the grids'.
+ * batch <= 0 or nform == 0 returns 0 after the checks.  NTG_E_BADARG, naming the form and term where one is at fault, for a null plan, d_x,
+ * form_nterms or terms; nform outside 0 .. NTG_TRIG_MAXFORMS; a form with 0 or more than NTG_TRIG_MAXTERMS terms; kind outside 0 .. 2; nent
+ * outside 1 .. NTG_TRIG_MAXENT; an entry outside [0, nz); pp outside [-1, nfp); nfp < 0, or a parameter named while d_fprm is null; a
+ * non-finite coef, phase or w; tol, max_depth or sides out of range; all six outputs null; violation outputs without both bounds; a batch
+ * other than the grids'.  NTG_E_UNSUPPORTED for host-callback plans, for a form that names entries of different basis classes (the message
+ * names the form and the two outputs), and for tables and work lists above 158 KiB of LDS: sum over basis classes of l (k^2 + 2) + 1, and
+ * per wavefront nC + nfp + 64 (4 KM + 3) doubles, KM = 6 (largest order <= 6) or 10 -- on per-problem grids the class tables count per
+ * wavefront too; four wavefronts, two where four do not fit. */
+#define NTG_TRIG_MAXFORMS 8
+#define NTG_TRIG_MAXTERMS 4      /* per form */
+#define NTG_TRIG_MAXENT   4      /* flag entries per angle */
+#define NTG_TRIG_SIN 0
+#define NTG_TRIG_COS 1
+#define NTG_TRIG_LIN 2           /* the angle itself: w * theta */
+typedef struct { int kind, nent, pp, pad; int ent[NTG_TRIG_MAXENT]; double coef[NTG_TRIG_MAXENT]; double phase, w; } ntg_trig_term;
+
+int ntg_batch_trig(const ntg_plan *p, int batch, const double *d_x,
+                   int nform, const int *form_nterms, const ntg_trig_term *terms,
+                   int nfp, const double *d_fprm,
+                   double tol, int max_depth, int sides,
+                   const double *d_flo, const double *d_fhi,
+                   double *d_ext, double *d_when, int *d_status, int *d_npieces,
+                   double *d_viol, int *d_where, void *stream);
 
 /* The flat-to-state map of the kinematic car for a whole ntg_batch_interp result (examples/kincar.c:68-92 kincar_flat_reverse,
  * called per sample by the example's output loop, kincar.c:392-406): d_z [batch][ntimes][nz] -> d_state [batch][ntimes][ncars][5] =

@@ -54,6 +54,14 @@ class Ratio(C.Structure):
     _fields_ = [("nnum", C.c_int), ("nden", C.c_int), ("num", C.c_int * 4), ("den", C.c_int * 4)]
 
 
+class TrigTerm(C.Structure):
+    """ntg_trig_term: w g(theta), theta = sum_i coef[i] z[ent[i]] + phase + fprm[pp] (index -1: no parameter); g = sin, cos or the identity by kind"""
+    _fields_ = [("kind", C.c_int), ("nent", C.c_int), ("pp", C.c_int), ("pad", C.c_int), ("ent", C.c_int * 4), ("coef", C.c_double * 4), ("phase", C.c_double), ("w", C.c_double)]
+
+
+TRIG_MAXFORMS, TRIG_MAXTERMS, TRIG_MAXENT = 8, 4, 4   # NTG_TRIG_*
+TRIG_SIN, TRIG_COS, TRIG_LIN = 0, 1, 2
+
 _lib = None
 
 
@@ -99,6 +107,7 @@ def lib():
         L.ntg_batch_forms.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, ip, C.POINTER(FormTerm), C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_int] + [C.c_void_p] * 9
         L.ntg_batch_ratios.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, ip, C.POINTER(FormTerm), C.c_int, C.c_void_p, C.c_int, C.POINTER(Ratio), C.c_double, C.c_int,
                                        C.c_int] + [C.c_void_p] * 9
+        L.ntg_batch_trig.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, ip, C.POINTER(TrigTerm), C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_int] + [C.c_void_p] * 9
         L.ntg_batch_refine.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_plan_set_grids.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ntg_plan_clear_grids.argtypes = [C.c_void_p]
@@ -573,6 +582,31 @@ class Plan:
         _check(lib().ntg_batch_ratios(self.h, batch, _ptr(x), nform, nterms, terms, nfp, _ptr(fprm), nratio, rat, float(tol),
                                       int(max_depth), int(sides), _ptr(lower), _ptr(upper), _ptr(out["ext"]), _ptr(out["when"]), _ptr(out["status"]), _ptr(out["npieces"]),
                                       _ptr(out.get("viol")), _ptr(out.get("where")), self._stream()))
+        return out
+
+    def trig(self, x, forms, tol, max_depth: int = 30, sides: int = 3, fprm=None, lower=None, upper=None):
+        """The minimum and maximum over the whole horizon of sums of sines and cosines of the flat flag declared here, each enclosed to tol, by
+        bisection (ntg_batch_trig): forms is a list of up to TRIG_MAXFORMS forms, each a list of up to TRIG_MAXTERMS ntg_amd.trig.Term
+        (kind, ent, coef, phase, pp, w): w g(theta), theta = sum_i coef[i] z[ent[i]] + phase + fprm[b, pp], g = sin, cos or the identity.  The
+        constructors of ntg_amd.trig build them (tip_height, tip_x, wall, heading).  No family callback runs: the manipulator's rows, which
+        Plan.extrema refuses, are certified this way.  Returns the dict of Plan.forms; lower / upper [batch, nform]."""
+        sp, dev, batch = self._cert_inputs(x, None, None)
+        forms = [list(f) for f in forms]
+        nform = len(forms)
+        _declare_forms([], fprm, lower, upper, dev, batch, nform, "forms")
+        for f, form in enumerate(forms):
+            for t, q in enumerate(form):
+                if not 1 <= len(q.ent) <= TRIG_MAXENT or len(q.ent) != len(q.coef):
+                    raise NtgError(f"form {f}, term {t}: 1 .. {TRIG_MAXENT} entries with one coef each")
+        pad = lambda v, ty: (ty * 4)(*(list(v) + [0] * (4 - len(v))))
+        flat = [TrigTerm(int(q.kind), len(q.ent), int(q.pp), 0, pad([int(e) for e in q.ent], C.c_int), pad([float(c) for c in q.coef], C.c_double), float(q.phase), float(q.w))
+                for form in forms for q in form]
+        nterms = (C.c_int * max(nform, 1))(*[len(f) for f in forms])
+        terms = (TrigTerm * max(len(flat), 1))(*flat)
+        out = _bisect_out(batch, nform, dev, lower is not None)
+        _check(lib().ntg_batch_trig(self.h, batch, _ptr(x), nform, nterms, terms, 0 if fprm is None else int(fprm.shape[1]), _ptr(fprm), float(tol), int(max_depth),
+                                    int(sides), _ptr(lower), _ptr(upper), _ptr(out["ext"]), _ptr(out["when"]), _ptr(out["status"]), _ptr(out["npieces"]),
+                                    _ptr(out.get("viol")), _ptr(out.get("where")), self._stream()))
         return out
 
     def set_grids(self, knots, bps, with_precond: bool = True):

@@ -437,3 +437,30 @@ static_assert(sizeof(RatioArgs) <= 4096, "RatioArgs travels as a kernel argument
 // work-list element is a pair of polygons, numerator first.  The limit is ntg_batch_extrema's
 static __host__ __device__ __forceinline__ BisectLds ntg_ratios_layout(const RatioArgs &A, int W) { return BisectLds{NTG_FORM_WALL + A.npw, A.f.g.ne, A.f.q.nk, A.f.g.nC, A.f.nfp, W, A.f.g.pp}; }
 static inline size_t ntg_ratios_lds(const RatioArgs &A, int nw) { return ntg_ratios_layout(A, 2 * A.kr).bytes(nw); }
+
+// ntg_batch_trig (trig.hpp): the minimum and maximum over the horizon of sums of sines and cosines of linear combinations of the flat flag that
+// the CALLER declares, h = sum_t w_t g_t(theta_t).  term[f][t] in the kernels' form and ORDER: the form's SIN and COS terms first, in declared
+// order (row[f].ntrig of them: term t is polygon t of a piece), then its nlin LIN terms in declared order, whose weighted angle polygons are
+// summed at level 0 into the one polygon a piece carries behind the trig terms'.  iC / r: coefficient offset of the output and derivative order
+// of every entry (the degree follows from the class: max(k - 1 - r, 0)); dt: the largest of those degrees; pp: index into the problem's row of
+// fprm [batch][nfp] or -1.  row[f]: the basis class cl of every entry the form names, the degree D of its polygons (the largest dt), and
+// W = sum_t |w_t|, declared order.  nprm: doubles of the wave's fprm row in LDS (nfp, padded so that the work list starts at 16 bytes), nw:
+// waves of a workgroup (4, or 2 where the work lists of four do not fit).  flo / fhi [batch][nform] (null unless a violation is asked for).
+// Outputs (q) as documented at ntg_batch_trig, any may be null.
+struct TrigTerm { int iC[NTG_TRIG_MAXENT]; short r[NTG_TRIG_MAXENT]; short kind, nent, dt, pad; int pp, pad2; double coef[NTG_TRIG_MAXENT]; double phase, w; };
+struct TrigRow { int ntrig, nlin, cl, D; double W; };
+struct TrigArgs {
+	CertBase g;
+	int nform, nfp, nprm, nw;
+	CertBisect q;
+	TrigRow row[NTG_TRIG_MAXFORMS];
+	TrigTerm term[NTG_TRIG_MAXFORMS][NTG_TRIG_MAXTERMS];
+	const double *fprm, *flo, *fhi;
+};
+static_assert(sizeof(TrigArgs) <= 4096, "TrigArgs travels as a kernel argument");
+// doubles of a work-list element: NTG_TRIG_MAXTERMS polygons of KM points (KM = 6 or NTG_MAX_ORDER, by the plan's largest order) and two of
+// padding -- an odd number of 16-byte slots, so that the lanes' wide reads of their own pieces spread over the banks
+static inline __host__ __device__ int ntg_trig_w(const CertBase &G) { return NTG_TRIG_MAXTERMS * (G.kmax <= 6 ? 6 : NTG_MAX_ORDER) + 2; }
+// dynamic LDS: no tables in front; a coefficient row and a row of fprm per wave.  The limit is ntg_batch_extrema's
+static __host__ __device__ __forceinline__ BisectLds ntg_trig_layout(const TrigArgs &A, int W) { return BisectLds{0, A.g.ne, A.q.nk, A.g.nC, A.nprm, W, A.g.pp}; }
+static inline size_t ntg_trig_lds(const TrigArgs &A, int nw) { return ntg_trig_layout(A, ntg_trig_w(A.g)).bytes(nw); }

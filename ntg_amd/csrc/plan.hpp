@@ -114,6 +114,10 @@ hipError_t ntg_launch_kkt(const NtgDims &D, const NtgTables &T, const KktArgs &a
 // polygons (ratios.hpp) ----
 hipError_t ntg_launch_ratios(const RatioArgs &A, int ncu, hipStream_t st);
 
+// ---- trig.hip: minimum and maximum over the horizon of sums of sines and cosines of the flag, by the certificates' bisection on pieces
+// of several angle polygons (trig.hpp) ----
+hipError_t ntg_launch_trig(const TrigArgs &A, int ncu, hipStream_t st);
+
 // ---- grids.hip: per-problem grids, the device-side setup algebra ----
 struct NtgGridLin {
 	const double *blk, *linrows; const int *plan_off, *erow, *csr_ptr, *csr_col, *csc_ptr, *csc_row, *sinv_ptr, *sinv_col, *q_col, *q_row2coef;

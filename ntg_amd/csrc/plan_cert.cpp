@@ -1,9 +1,9 @@
 // plan_cert.cpp -- the time certificates behind include/ntg_amd.h: ntg_batch_envelope, ntg_batch_envelope_sos, ntg_batch_extrema,
-// ntg_batch_separation, ntg_batch_forms, ntg_batch_ratios and the queries ntg_plan_sos_rows and ntg_plan_extrema_rows.  What they share comes first: the refusals (each call tests them between its own
+// ntg_batch_separation, ntg_batch_forms, ntg_batch_ratios, ntg_batch_trig and the queries ntg_plan_sos_rows and ntg_plan_extrema_rows.  What they share comes first: the refusals (each call tests them between its own
 // argument checks, in its own order), which rows of a plan are certified -- a linear trajectory row whose outputs share a basis class, from
 // the host mirror of ltc; a nonlinear row by the family's sum-of-squares declaration, NtgFamily::sos, against the plan's iz / cls -- and the
 // three parts of the kernels' arguments (CertBase, CertLin, CertSos: ntg_dev.hpp).  An entry point then reads: its own argument checks,
-// the setup, its own fields, the launch.  The arithmetic is in envelope.hpp, envelope_sos.hpp, extrema.hpp, separation.hpp, forms.hpp and ratios.hpp.  No family callback runs, so
+// the setup, its own fields, the launch.  The arithmetic is in envelope.hpp, envelope_sos.hpp, extrema.hpp, separation.hpp, forms.hpp, ratios.hpp and trig.hpp.  No family callback runs, so
 // the calls serve every built-in family and every loaded module.  They allocate nothing.
 #include <cstring>
 #include "plan_priv.hpp"
@@ -514,5 +514,72 @@ extern "C" int ntg_batch_ratios(const ntg_plan *p, int batch, const double *d_x,
 	A.f.fprm = d_fprm; A.f.flo = d_rlo; A.f.fhi = d_rhi;
 	HIPCHK(hipSetDevice(p->device));
 	HIPCHK(ntg_launch_ratios(A, plan_ncu(p), (hipStream_t)stream));
+	return 0;
+}
+
+// ---------------- sines and cosines declared at the call (ntg_batch_trig) ----------------
+extern "C" int ntg_batch_trig(const ntg_plan *p, int batch, const double *d_x, int nform, const int *form_nterms, const ntg_trig_term *terms, int nfp, const double *d_fprm,
+                              double tol, int max_depth, int sides, const double *d_flo, const double *d_fhi,
+                              double *d_ext, double *d_when, int *d_status, int *d_npieces, double *d_viol, int *d_where, void *stream)
+{
+	if (!p) return fail(NTG_E_BADARG, "null plan");
+	if (!d_x || !form_nterms || !terms) return fail(NTG_E_BADARG, "null argument");
+	if (nform < 0 || nform > NTG_TRIG_MAXFORMS) return fail(NTG_E_BADARG, "nform must lie in 0 .. " + std::to_string(NTG_TRIG_MAXFORMS));
+	if (nfp < 0) return fail(NTG_E_BADARG, "nfp must be >= 0");
+	if (int rc = cert_levels(tol, max_depth)) return rc;
+	if (int rc = cert_sides(sides)) return rc;
+	const NtgDims &D = p->D;
+	TrigArgs A{};
+	FormCross X;
+	const ntg_trig_term *q = terms;
+	for (int f = 0; f < nform; f++) {
+		const int nt = form_nterms[f];
+		const std::string fname = "form " + std::to_string(f);
+		if (nt < 1 || nt > NTG_TRIG_MAXTERMS) return fail(NTG_E_BADARG, fname + " has " + std::to_string(nt) + " terms: 1 .. " + std::to_string(NTG_TRIG_MAXTERMS) + " are taken");
+		TrigRow &R = A.row[f];
+		TrigTerm lin[NTG_TRIG_MAXTERMS];   // the LIN terms go behind the SIN and COS terms, both in declared order
+		int first = -1;
+		for (int t = 0; t < nt; t++, q++) {
+			const std::string tname = fname + ", term " + std::to_string(t);
+			if (q->kind < NTG_TRIG_SIN || q->kind > NTG_TRIG_LIN) return fail(NTG_E_BADARG, tname + ": kind = " + std::to_string(q->kind) + " is none of NTG_TRIG_SIN, _COS, _LIN (0 .. 2)");
+			if (q->nent < 1 || q->nent > NTG_TRIG_MAXENT) return fail(NTG_E_BADARG, tname + ": nent = " + std::to_string(q->nent) + " must lie in 1 .. " + std::to_string(NTG_TRIG_MAXENT));
+			for (int i = 0; i < q->nent; i++)
+				if (q->ent[i] < 0 || q->ent[i] >= D.nz)
+					return fail(NTG_E_BADARG, tname + ": ent[" + std::to_string(i) + "] = " + std::to_string(q->ent[i]) + " is no flag entry of the plan (0 .. " + std::to_string(D.nz - 1) + ")");
+			if (q->pp < -1 || q->pp >= nfp) return fail(NTG_E_BADARG, tname + ": pp must lie in -1 .. nfp - 1 = " + std::to_string(nfp - 1));
+			if (q->pp >= 0 && !d_fprm) return fail(NTG_E_BADARG, tname + " names a parameter, but d_fprm is null");
+			bool finite = std::isfinite(q->w) && std::isfinite(q->phase);
+			for (int i = 0; i < q->nent; i++) finite = finite && std::isfinite(q->coef[i]);
+			if (!finite) return fail(NTG_E_BADARG, tname + ": coef, phase and w must be finite");
+			TrigTerm T{};
+			for (int i = 0; i < q->nent; i++) {
+				const FlagEntry e = flag_entry(D, q->ent[i]);
+				if (first < 0) { first = e.o; R.cl = D.cls[e.o]; }
+				if (D.cls[e.o] != R.cl && X.form < 0) { X.form = f; X.a = first; X.b = e.o; }
+				T.iC[i] = D.iC[e.o]; T.r[i] = (short)e.r; T.coef[i] = q->coef[i];
+				T.dt = std::max(T.dt, (short)std::max(D.order[e.o] - 1 - e.r, 0));
+			}
+			T.kind = (short)q->kind; T.nent = (short)q->nent; T.pp = q->pp; T.phase = q->phase; T.w = q->w;
+			R.D = std::max(R.D, (int)T.dt);
+			R.W += std::fabs(q->w);
+			if (q->kind == NTG_TRIG_LIN) lin[R.nlin++] = T;
+			else A.term[f][R.ntrig++] = T;
+		}
+		for (int t = 0; t < R.nlin; t++) A.term[f][R.ntrig + t] = lin[t];
+	}
+	if (int rc = forms_outputs(d_flo, d_fhi, "d_flo", "d_fhi", d_ext, d_when, d_status, d_npieces, d_viol, d_where)) return rc;
+	if (batch <= 0 || nform == 0) return 0;
+	if (int rc = forms_refuse(p, batch, X)) return rc;
+	cert_base(p, batch, d_x, nullptr, nullptr, A.g, A.q.koff, &A.q.nk);
+	A.q.nk += (A.g.ne + A.q.nk) & 1;   // the work lists start at 16 bytes: the lanes read their pieces in 16-byte words
+	A.nform = nform; A.nfp = nfp; A.nprm = nfp + ((A.g.nC + nfp) & 1);
+	cert_bisect(A.q, tol, max_depth, sides, d_ext, d_when, d_status, d_npieces, d_viol, d_where);
+	A.nw = ntg_trig_lds(A, 4) <= NTG_EXTREMA_LDS_MAX ? 4 : 2;
+	if (A.g.kmax > NTG_MAX_ORDER || ntg_trig_lds(A, A.nw) > NTG_EXTREMA_LDS_MAX)
+		return fail(NTG_E_UNSUPPORTED, "the tables and work lists of this call exceed " + std::to_string(NTG_EXTREMA_LDS_MAX / 1024) + " KiB of LDS: the class tables, and per wavefront nC + nfp + " +
+		                                   std::to_string(NTG_EXTREMA_CAP) + " (4 KM + 3) doubles, KM = 6 or 10");
+	A.fprm = d_fprm; A.flo = d_flo; A.fhi = d_fhi;
+	HIPCHK(hipSetDevice(p->device));
+	HIPCHK(ntg_launch_trig(A, plan_ncu(p), (hipStream_t)stream));
 	return 0;
 }
