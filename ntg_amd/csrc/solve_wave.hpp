@@ -65,6 +65,13 @@ constexpr auto from_next = dpp_perm<0x130>;   // wave_shl:1
 #ifndef NTGW_ABASE_ALT
 #define NTGW_ABASE_ALT 16
 #endif
+// variant builds (tools/mkvariant.sh): 0 takes the roots in lanes / the |g|^2 sum at accepted steps out of the one-wave-per-SIMD instances again
+#ifndef NTGW_ROOTS_IN_LANES
+#define NTGW_ROOTS_IN_LANES 1
+#endif
+#ifndef NTGW_G2_LATE
+#define NTGW_G2_LATE 1
+#endif
 // accumulator registers a[ABASE + 2 IDX], a[ABASE + 2 IDX + 1] as one double.  The kernel lists a0..a255 as clobbers once (which makes
 // the kernel descriptor allocate them all).
 template <int ABASE, int IDX>
@@ -95,9 +102,14 @@ __device__ __forceinline__ double bcast(double v, int lane)
 // FEW: the interleaved rotation / permlane form for one to three values (wave_ops.hpp: wave_sums_few).  Measured: it pays on the instances
 // with one wave per SIMD (headline -0.5 %) and costs the two-waves-per-SIMD instances dearly (preconditioned solves 0.151 -> 0.178 ms per
 // 4096), so those keep the row_shr / row_bcast chains.
-template <int KV, bool FEW = false>
+// ROOTS (many values only): bit k set -- v[k] receives the square root of its total instead of the total.  After the butterfly lane L holds
+// the total of value L & 15, so ONE root sequence in every lane roots them all (a lane whose total is not selected computes a value nobody
+// reads) and the broadcasts that follow carry roots and totals alike; taken after the broadcasts the same sequence ran once per value, on
+// 64 identical lanes each time.
+template <int KV, bool FEW = false, unsigned ROOTS = 0>
 __device__ __forceinline__ void wave_sums(double (&v)[KV], int lane)
 {
+	static_assert(ROOTS == 0 || KV >= 4, "roots in lanes: the many-value form only");
 	if constexpr (KV < 4) {
 		if constexpr (FEW) wave_sums_few<KV>(v);
 		else {
@@ -113,9 +125,23 @@ __device__ __forceinline__ void wave_sums(double (&v)[KV], int lane)
 		int ln = lane;
 		asm volatile("" : "+v"(ln));
 		const double t = wave_sum_many<KV>(w, ln);   // lane L: total of value L & 15
+		if constexpr (ROOTS != 0) {
+			const double ts = sqrt(t);
 #pragma unroll
-		for (int k = 0; k < KV; k++) v[k] = bcast(t, k);
+			for (int k = 0; k < KV; k++) v[k] = bcast(((ROOTS >> k) & 1u) ? ts : t, k);
+		} else {
+#pragma unroll
+			for (int k = 0; k < KV; k++) v[k] = bcast(t, k);
+		}
 	}
+}
+// the wave's total of one per-lane value, by the few-value form: its chains are independent per value, so this is the number the same
+// value gives as one of two or three summed together
+__device__ __forceinline__ double wave_total_few(double v)
+{
+	double one[1] = {v};
+	wave_sums_few<1>(one);
+	return one[0];
 }
 
 struct WaveArgs {
@@ -807,7 +833,7 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 			ls.init(0.0, 0.0, 0.0, 0.0, sp.ls_mu, sp.ls_eta, sp.ls_maxfev);
 			double ls_a = 0.0;
 			double tstep = 0.0;            // the point to evaluate is x + tstep (-d): a line-search trial, or x itself (first and final evaluation)
-			double r4[4] = {0, 0, 0, 0};   // gp.d, d.d, x.x, gp.gp of the current iterate
+			double r4[4] = {0, 0, 0, 0};   // gp.d, d.d, x.x, gp.gp of the current iterate (NORMS below: gp.d, d.d, |x|, |gp|)
 			// One step of the line search on the values of the trial just evaluated, into rc_: 1 accept, 0 / 2 another trial at ls_a (2: the last
 			// one, taken whatever it gives), anything else failed.  A macro, so that its two places of use (one per form of the loop below, never
 			// both in one instance) compile as the text written there: as a lambda the step is optimised on its own before it is inlined, and
@@ -845,6 +871,20 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 			// instances keep the single loop: nested, they spill more scalars.  (An enumerator, not a constexpr local: a local is an object of the
 			// function, and one more of those, dead or not, renames registers all through the instances that are meant to stay as they were.)
 			enum { NEST = (MINW == 1) };
+			// Norms and |g|^2 on the one-wave-per-SIMD instances (enumerators again; the two-waves-per-SIMD instances keep every line below as it was).
+			// NORMS: the square roots of the totals of the 16-wide butterflies are taken in lanes, before the broadcasts (wave_sums: ROOTS), so
+			//   r4[2], r4[3] carry |x| and |gp| -- not their squares -- across the major loop and r6[4], r6[5] arrive as |s|, |y|; NTGW_ROOT(v) is
+			//   the norm of either form.  Every root is taken from the same operand bits as before.  r4[1] stays d.d and is rooted at the start
+			//   of a major: after an accepted step it is a few-value total, uniform from lane 0, and a root carried in its place is a uniform
+			//   value in a vector register across the loop (compiled: the allocator then moved into the accumulator range).
+			// G2LATE: |g|^2 is read by tolg alone, and tolg by the line search's failure branch, the lost-definiteness branch and the convergence
+			//   tests -- nothing the fixed-work solve passes through.  The evaluation site sums two values and leaves the lane's share of |g|^2
+			//   in part[1]; it is summed at the first evaluation and at an accepted step, as the third value of that step's few-value sum (the
+			//   chains of that form are independent per value: the bits the three-value sum of the evaluation site gave), and tolg is formed
+			//   behind the tests that read it, not at the top of every major.
+			enum { NORMS = (MINW == 1 && NTGW_ROOTS_IN_LANES), G2LATE = (MINW == 1 && NTGW_G2_LATE) };
+#define NTGW_ROOT(v_) (NORMS ? (v_) : sqrt(v_))
+#define NTGW_TOLG() (kernargs()->sp.sr * (1.0 + fmax(1.0 + fabs(F), sqrt(gn2))))
 			for (;;) {
 				double part[3];
 				for (;;) {
@@ -868,7 +908,11 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 #ifdef NTGW_DBL_RED3
 					{ double q_[3] = {part[0], part[1], part[2]}; asm volatile("" : "+v"(q_[0]), "+v"(q_[1]), "+v"(q_[2])); wave_sums<3, MINW == 1>(q_, lane); asm volatile("" ::"s"(q_[0]), "s"(q_[1]), "s"(q_[2])); }
 #endif
-					wave_sums<3, MINW == 1>(part, lane);
+					if constexpr (G2LATE) {   // F and the slope; part[1] stays the lane's share of |g|^2
+						double fs[2] = {part[0], part[2]};
+						wave_sums_few<2>(fs);
+						part[0] = fs[0]; part[2] = fs[1];
+					} else wave_sums<3, MINW == 1>(part, lane);
 					NTGW_STAMPV(6, part[0] + part[1] + part[2]);
 					if constexpr (!NEST) break;
 					else {
@@ -909,7 +953,7 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 				nfev++;
 				bool new_major = false;
 				if (state == ST_INIT) {
-					F = Fn; gn2 = gn2n;
+					F = Fn; gn2 = G2LATE ? wave_total_few(gn2n) : gn2n;
 #pragma unroll
 					for (int e = 0; e < EPL; e++) gp[e] = gpt[e];
 					apply_w0(gp, d);
@@ -917,7 +961,7 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 					for (int k = 0; k < 4; k++) r4[k] = 0.0;
 #pragma unroll
 					for (int e = 0; e < EPL; e++) { r4[0] += gp[e] * d[e]; r4[1] += d[e] * d[e]; r4[2] += x[e] * x[e]; r4[3] += gp[e] * gp[e]; }
-					wave_sums<4, MINW == 1>(r4, lane);
+					wave_sums<4, MINW == 1, NORMS ? 0xCu : 0u>(r4, lane);   // (NORMS: |x|, |gp|)
 					NTGW_STAMP(4);
 					new_major = true;
 				} else {
@@ -932,8 +976,8 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 						}
 					}
 					if (rc != 1) {
-						const double tolg = kernargs()->sp.sr * (1.0 + fmax(1.0 + fabs(F), sqrt(gn2)));
-						if (nupd > 0 && sqrt(r4[3]) > tolg) {
+						const double tolg = NTGW_TOLG();
+						if (nupd > 0 && NTGW_ROOT(r4[3]) > tolg) {
 							// line search failed with a non-trivial W: drop the updates and retry from the same point with W0
 							nupd = 0; ns = 0; headpair = false;
 							apply_w0(gp, d);
@@ -944,7 +988,7 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 							r4[0] = r2[0]; r4[1] = r2[1];
 							new_major = true;
 						} else {
-							const double gpn0 = sqrt(r4[3]);
+							const double gpn0 = NTGW_ROOT(r4[3]);
 							if (gpn0 <= tolg) inner_inform = 0;
 							else if (gpn0 <= 1e3 * tolg) { inner_inform = 0; weak = true; }
 							else inner_inform = 6;
@@ -988,8 +1032,8 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 							r6[0] += s * y; r6[1] += y * u; r6[2] += s * gq; r6[3] += u * gq; r6[4] += s * s; r6[5] += y * y;
 							r6[6] += x[e] * x[e]; r6[7] += gq * gq;
 						}
-						wave_sums<8, MINW == 1>(r6, lane);
-						const bool upd = r6[0] > 1e-12 * sqrt(r6[4]) * sqrt(r6[5]);
+						wave_sums<8, MINW == 1, NORMS ? 0xF0u : 0u>(r6, lane);   // (NORMS: |s|, |y|, |x|, |gp+|)
+						const bool upd = r6[0] > 1e-12 * NTGW_ROOT(r6[4]) * NTGW_ROOT(r6[5]);
 						const double rho = upd ? 1.0 / r6[0] : 0.0, c2 = upd ? rho * (1.0 + rho * r6[1]) : 0.0;
 						// the new direction d+ is formed in place of d (the loop-carried direction keeps one set of registers instead of being rebuilt
 						// from a temporary on this path only); the pair term's u = t - d of the old d is kept for it
@@ -1030,12 +1074,19 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 							gp[e] = gpt[e];
 							r2[0] += gp[e] * d[e]; r2[1] += d[e] * d[e];
 						}
-						wave_sums<2, MINW == 1>(r2, lane);
-						r4[0] = r2[0]; r4[1] = r2[1]; r4[2] = r6[6]; r4[3] = r6[7];
-						F = Fn; gn2 = gn2n;
+						if constexpr (G2LATE) {   // |g|^2 of the accepted point rides with the two products of the new direction
+							double r3[3] = {r2[0], r2[1], gn2n};
+							wave_sums_few<3>(r3);
+							r4[0] = r3[0]; r4[1] = r3[1]; r4[2] = r6[6]; r4[3] = r6[7];
+							F = Fn; gn2 = r3[2];
+						} else {
+							wave_sums<2, MINW == 1>(r2, lane);
+							r4[0] = r2[0]; r4[1] = r2[1]; r4[2] = r6[6]; r4[3] = r6[7];
+							F = Fn; gn2 = gn2n;
+						}
 						iter++;
-						if (!kernargs()->sp.fixed_iters && alpha * pnorm <= kernargs()->sp.sr * (1.0 + sqrt(r4[2])) &&
-						    sqrt(r4[3]) <= kernargs()->sp.sr * (1.0 + fmax(1.0 + fabs(F), sqrt(gn2)))) { inner_inform = 0; finished = true; }
+						if (!kernargs()->sp.fixed_iters && alpha * pnorm <= kernargs()->sp.sr * (1.0 + NTGW_ROOT(r4[2])) &&
+						    NTGW_ROOT(r4[3]) <= kernargs()->sp.sr * (1.0 + fmax(1.0 + fabs(F), sqrt(gn2)))) { inner_inform = 0; finished = true; }
 						else new_major = true;
 					}
 				}
@@ -1045,8 +1096,10 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 					else {
 						double dphi0 = -r4[0];
 						pnorm = sqrt(r4[1]);
-						const double xnorm = sqrt(r4[2]), gpnorm = sqrt(r4[3]);
-						const double tolg = kernargs()->sp.sr * (1.0 + fmax(1.0 + fabs(F), sqrt(gn2)));
+						const double xnorm = NTGW_ROOT(r4[2]), gpnorm = NTGW_ROOT(r4[3]);
+						// (G2LATE: tolg is formed at its two uses below, behind their tests -- here it cost a root sequence per major)
+						const double tolg = G2LATE ? 0.0 : NTGW_TOLG();
+#define NTGW_TOLG_HERE() (G2LATE ? NTGW_TOLG() : tolg)
 						if (pnorm == 0.0 || !(dphi0 < 0.0)) {
 							if (pnorm != 0.0) {   // W lost definiteness numerically: restart from W0 once
 								nupd = 0; ns = 0; headpair = false;
@@ -1058,9 +1111,10 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 								r4[0] = r2[0]; r4[1] = r2[1];
 								dphi0 = -r2[0]; pnorm = sqrt(r2[1]);
 							}
-							if (pnorm == 0.0 || !(dphi0 < 0.0)) { inner_inform = (gpnorm <= tolg) ? 0 : 6; finished = true; }
+							if (pnorm == 0.0 || !(dphi0 < 0.0)) { inner_inform = (gpnorm <= NTGW_TOLG_HERE()) ? 0 : 6; finished = true; }
 						}
-						if (!finished && !kernargs()->sp.fixed_iters && gpnorm <= 1e-3 * tolg) { inner_inform = 0; finished = true; }
+						if (!finished && !kernargs()->sp.fixed_iters && gpnorm <= 1e-3 * NTGW_TOLG_HERE()) { inner_inform = 0; finished = true; }
+#undef NTGW_TOLG_HERE
 						if (!finished) {
 							const double amax = kernargs()->sp.steplimit * (1.0 + xnorm) / pnorm;
 							const double a = amax < 1.0 ? amax : 1.0;
@@ -1114,6 +1168,8 @@ sqp_wave_kernel(NtgDims D, NtgTables T, SolveParams sp, WaveArgs A)
 		}
 #undef NTGW_LS_STEP
 #undef NTGW_LS_DBL
+#undef NTGW_ROOT
+#undef NTGW_TOLG
 #undef NTGW_STAMP
 #undef NTGW_STAMPV
 		if (lane == 0) {

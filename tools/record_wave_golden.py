@@ -1,13 +1,14 @@
 """Record tests/golden/wave_instances.npz (tests/test_gpu_wave_golden_instances.py), with --restarts tests/golden/wave_restarts.npz
 (tests/test_gpu_wave_golden_restarts.py), with --tail tests/golden/wave_tail.npz (tests/test_gpu_wave_golden_tail.py), with --exits
-tests/golden/wave_exits.npz (solves that end at the iteration limit: tests/test_gpu_wave_golden_exits.py) or with --sqp
+tests/golden/wave_exits.npz (solves that end at the iteration limit: tests/test_gpu_wave_golden_exits.py), with --norms
+tests/golden/wave_norms.npz (solves through the consumers of the iterate's norms and of |g|^2: tests/test_gpu_wave_golden_norms.py) or with --sqp
 tests/golden/sqp_modes.npz (the Newton and QP modes of sqp_kernel: tests/test_gpu_sqp_golden.py) with the library named by NTG_AMD_LIB --
 meant for the library of the commit BEFORE a change that must not move a bit.
 
   python tools/record_wave_golden.py --audit LIB     where LIB was built (no GPU): audit the device assembly of its wave kernels
                                                      (ntg_amd/isa_audit.py) and the call boundaries of every unit's (ntg_amd/call_audit.py),
                                                      and write LIB.audited
-  NTG_AMD_LIB=LIB python tools/record_wave_golden.py [--restarts | --tail | --exits | --sqp] [OUT.npz]     on the GPU: refuses a library without a matching LIB.audited
+  NTG_AMD_LIB=LIB python tools/record_wave_golden.py [--restarts | --tail | --exits | --norms | --sqp] [OUT.npz]     on the GPU: refuses a library without a matching LIB.audited
 
 A library whose wave kernels failed the audit may corrupt the chain or fault on the GPU: it is never run."""
 import glob
@@ -65,10 +66,13 @@ def main():
     if not ok:
         sys.exit("%s has no matching .audited stamp (run --audit where it was built): not run" % lib)
     import numpy as np
-    args = [a for a in sys.argv[1:] if a not in ("--restarts", "--tail", "--exits", "--sqp")]
+    args = [a for a in sys.argv[1:] if a not in ("--restarts", "--tail", "--exits", "--norms", "--sqp")]
     if "--sqp" in sys.argv[1:]:
         import sqp_golden_cases as wc
         default = "sqp_modes.npz"
+    elif "--norms" in sys.argv[1:]:
+        import wave_golden_norms_cases as wc
+        default = "wave_norms.npz"
     elif "--exits" in sys.argv[1:]:
         import wave_golden_exit_cases as wc
         default = "wave_exits.npz"
