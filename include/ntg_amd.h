@@ -44,6 +44,8 @@
  *                        per sample: the minimum and maximum over the horizon of ratios of products of such forms (curvature^2, lateral acceleration^2)
  *   ntg_batch_trig       nothing in the reference bounds a row between samples; constraints.c:119-160 evaluates the manipulator's rows at the
  *                        breakpoints only: the minimum and maximum over the horizon of sums of sines and cosines of the flag (a tip's height and reach)
+ *   ntg_batch_minmax     nothing in the reference bounds a row between samples; constraints.c:119-160 evaluates the trajectory rows at the
+ *                        breakpoints only: the minimum and maximum over the horizon of min / max expressions over such forms (polygons, boxes, corridors)
  *   ntg_batch_kincar_reverse  examples/kincar.c:68-92 kincar_flat_reverse (the example's flat-to-state map), for a batch
  *   ntg(), npsoloption(), linspace(), SplineInterp(), matrix helpers: see include/ntg.h
  */
@@ -825,6 +827,94 @@ int ntg_batch_trig(const ntg_plan *p, int batch, const double *d_x,
                    const double *d_flo, const double *d_fhi,
                    double *d_ext, double *d_when, int *d_status, int *d_npieces,
                    double *d_viol, int *d_where, void *stream);
+
+/* Certified extrema of MIN / MAX EXPRESSIONS over quadratic forms of the flat flag, declared at the call: ntg_batch_forms' statement -- the
+ * global minimum and maximum over the horizon, each enclosed to a tolerance and each with a witness time -- for
+ *   h_g(t) = OUTER_k INNER_{j in clause k} m_kj(t),   m(t) = q_form(z(t)) + d,   OUTER and INNER each min or max,
+ * the regions that several functions describe together.  A convex polygonal obstacle: the trajectory stays outside iff min over t of max_j
+ * n_j . (p(t) - v_j) >= 0 (no single face says so: each goes negative far from the polygon).  A rotated box, a lane, a convex corridor: inside
+ * iff max over t of max_j (...) <= 0.  A safe corridor of overlapping boxes: max over t of min_k max_j f_kj <= 0.  Coverage by beacons: max over
+ * t of min_j (d_j^2 - R_j^2) <= 0.  min and max are monotone: with every member enclosed by [plo_m, phi_m] on a piece, OUTER_k INNER_j over the
+ * plo and over the phi enclose h_g there, and its value at a piece end is the same expression over the members' end points, which are attained
+ * values.  So ntg_batch_extrema's bisection applies to pieces that carry the polygons of all members.  No family callback runs: every plan is
+ * served (built-in families, loaded modules, per-problem grids).
+ * Forms are declared exactly as for ntg_batch_forms (form_nterms, terms, nfp, d_fprm: same arrays, same checks, same messages); none of them is
+ * certified by itself.  0 <= nform <= NTG_MINMAX_MAXFORMS, at most NTG_FORM_MAXTERMS terms per form and NTG_MINMAX_MAXTERMS = 40 over all forms
+ * (40 terms, 16 forms, 32 members and 4 groups are what fits the 4096-byte kernel argument: 3520 bytes).
+ * Members and groups.  groups [ngroup] and members are HOST arrays, copied by the call; members is concatenated group after group, clause after
+ * clause: group g has nclause clauses of nmem[k] members.  Member m is q_form(z(t)) + d with d = c + (pc >= 0 ? fprm_b[pc] : 0), one rounding.
+ * outer and inner are NTG_MINMAX_MIN or NTG_MINMAX_MAX.  All forms named by one group belong to one basis class; different groups may use
+ * different classes.  0 <= ngroup <= NTG_MINMAX_MAXGROUPS, 1 <= nclause <= NTG_MINMAX_MAXCLAUSES, nmem[k] >= 1, at most NTG_MINMAX_MAXMEMBERS
+ * members per group and 32 over all groups.
+ * Outputs, any may be NULL but not all seven; those of ntg_batch_forms with the group in the place of the form:
+ *   d_ext     [batch][ngroup][4]  {min_lo, min_hi, max_lo, max_hi}
+ *   d_when    [batch][ngroup][2]  {t_min, t_max}
+ *   d_which   [batch][ngroup][2]  the member, by its index in the group's concatenated list, that decides h_g at t_min and at t_max: inside a
+ *                                 clause the member that attains INNER, ties to the smallest index; among the clauses the clause that attains
+ *                                 OUTER, ties to the smallest clause; -1 where the time is NaN
+ *   d_status  [batch][ngroup]     NTG_EXTREMA_OK / _DEPTH / _FULL / _NAN
+ *   d_npieces [batch][ngroup]     pieces evaluated
+ *   d_viol    [batch][2]          {attained, certified}
+ *   d_where   [batch][2]          group of each of the two violations; ties to the smallest group; -1 where the figure is 0
+ * Definition, per problem and per group.  Every product and every sum is rounded separately (no fused multiply-add).
+ * 1. Level 0, knot interval j of the group's class.  A member's polygon is its form's level-0 polygon by step 1 of ntg_batch_forms, bit for
+ *    bit.  Then + d is added to every point, with one rounding; a member with pc = -1 and c = 0.0 adds nothing.  Then the polygon is elevated
+ *    to the group's degree D_g = max of its members' form degrees, with the formula ntg_batch_envelope states.  A piece carries the polygons
+ *    of all members of the group.
+ * 2. Piece.  plo_m and phi_m are the smallest and the largest of member m's points.  plo = OUTER_k INNER_j plo_kj and phi = OUTER_k INNER_j
+ *    phi_kj: min and max of doubles, exact and independent of the order.  A NaN in any member's figures marks the group as rule 5 of
+ *    ntg_batch_extrema does (status NTG_EXTREMA_NAN), before anything else.
+ * 3. Ends.  The value at a piece end is OUTER_k INNER_j of the members' first or last points.  These are the attained values U / V, with the
+ *    times and the smaller-time tie rule of rule 2 of ntg_batch_extrema.  which is recorded together with the value it belongs to; of two
+ *    ends with equal values and equal times the one with the smaller which is kept.
+ * 4. Levels, results, NaN, violation.  Rules 2 to 7 of ntg_batch_extrema, unchanged: tol, max_depth, sides, NTG_EXTREMA_CAP and the statuses
+ *    OK, DEPTH, FULL and NAN; there is no NONE.  Every polygon of an open piece is halved with 0.5 * (a + b).  npieces counts pieces, not
+ *    polygons: l at level 0, two per open piece afterwards.  The bounds are d_glo / d_ghi [batch][ngroup].
+ * 5. Pins.  A group of one clause with one member, c = 0.0 and pc = -1, returns what ntg_batch_forms returns for that form: ext, when, status
+ *    and npieces are equal under ==.  Repeating that member, as two clauses of one or one clause of two, changes nothing.  With every w and
+ *    every c negated, fprm-borne offsets negated by the caller, and MIN and MAX swapped in outer and inner, ext comes back negated with its two
+ *    sides exchanged, and when, which, status and npieces with the sides exchanged, under ==: every operation above is odd-symmetric in
+ *    round-to-nearest.
+ * Rounding.  min and max do not amplify an error: if every member's points are within e_m of the exact polygon's, plo, phi and the end values
+ *    are within max_m e_m of the exact figures.  A point of form f carries at most 2^-39 M_f with M_f = sum_t |w_t| S_u S_v (ntg_batch_forms);
+ *    forming d and adding it are two roundings, below 2^-52 (M_f + |d|); the at most 18 elevation steps (3 roundings each, convex combinations)
+ *    add less than 2^-47 (M_f + |d|).  The slack of a group is
+ *      slack_g = max over its members of 2^-39 (M_f + |d|)      (DESIGN.md 2o).
+ * Convergence.  Where the extremum sits on a smooth arc of one member, the enclosure closes quadratically in the piece width, as for a form.
+ *    Where it sits at a kink -- the minimum of a MAX group generically does, where two faces cross -- it closes only linearly: U - plo is about
+ *    slope * width.  Only one or two pieces stay open per level, so the cost stays small, but the depth needed is about log2(h * slope / tol),
+ *    h the knot interval.  With max_depth <= 30 a tolerance far below h * slope * 2^-30 ends in status DEPTH: that is the honest answer, and the
+ *    enclosure returned is still valid.
+ * Arguments.  tol, max_depth and sides as in ntg_batch_extrema.  Stream ordered, without scratch in HBM and without floating-point atomics: a
+ * wavefront owns a problem and walks its groups, lane p owns open piece p.  Results are bit-identical from call to call and independent of
+ * the batch around a problem.  Per-problem grids are honoured: the batch must be the grids'.
+ * batch <= 0 or ngroup == 0 returns 0 after the checks.  The refusals of ntg_batch_forms apply unchanged (with the caps above).  NTG_E_BADARG,
+ * naming the group, clause or member at fault, for null groups or members with ngroup > 0; ngroup, nclause, nmem[k], the members of a group or
+ * of all groups outside their ranges; a clause with 0 members; outer or inner outside {0, 1}; form outside [0, nform); pc outside [-1, nfp), or
+ * pc named while d_fprm is null; a non-finite c; all seven outputs null; violation outputs without both bounds; a batch other than the grids'.
+ * NTG_E_UNSUPPORTED for host-callback plans, for a form that names entries of different basis classes, for a group whose forms belong to
+ * different basis classes (the message names the group and the two outputs), and for tables and work lists above 158 KiB of LDS even with one
+ * wavefront: 3025 product weights, sum over basis classes of l (k^2 + 2) + 1, and per wavefront nC + nfp + 64 (MC * PW + 1) doubles -- MC = 8
+ * where no group has more than 8 members, else 16; PW = 7 (largest order <= 6 and every group linear: polygons of 6 points), 11 (largest
+ * order <= 6) or 19 -- on per-problem grids the class tables count per wavefront too.  Four wavefronts where four fit, else two, else one;
+ * MC = 16 with PW = 19 does not fit even one. */
+#define NTG_MINMAX_MIN 0
+#define NTG_MINMAX_MAX 1
+#define NTG_MINMAX_MAXFORMS   16   /* forms declared at one call */
+#define NTG_MINMAX_MAXTERMS   40   /* terms of all forms together; at most NTG_FORM_MAXTERMS per form */
+#define NTG_MINMAX_MAXGROUPS   4
+#define NTG_MINMAX_MAXCLAUSES  8   /* per group */
+#define NTG_MINMAX_MAXMEMBERS 16   /* per group; at most 32 over all groups */
+typedef struct { int form, pc; double c; } ntg_minmax_member;
+typedef struct { int outer, inner, nclause, pad; int nmem[NTG_MINMAX_MAXCLAUSES]; } ntg_minmax_group;
+
+int ntg_batch_minmax(const ntg_plan *p, int batch, const double *d_x,
+                     int nform, const int *form_nterms, const ntg_form_term *terms, int nfp, const double *d_fprm,
+                     int ngroup, const ntg_minmax_group *groups, const ntg_minmax_member *members,
+                     double tol, int max_depth, int sides,
+                     const double *d_glo, const double *d_ghi,
+                     double *d_ext, double *d_when, int *d_which, int *d_status, int *d_npieces,
+                     double *d_viol, int *d_where, void *stream);
 
 /* The flat-to-state map of the kinematic car for a whole ntg_batch_interp result (examples/kincar.c:68-92 kincar_flat_reverse,
  * called per sample by the example's output loop, kincar.c:392-406): d_z [batch][ntimes][nz] -> d_state [batch][ntimes][ncars][5] =

@@ -62,6 +62,21 @@ class TrigTerm(C.Structure):
 TRIG_MAXFORMS, TRIG_MAXTERMS, TRIG_MAXENT = 8, 4, 4   # NTG_TRIG_*
 TRIG_SIN, TRIG_COS, TRIG_LIN = 0, 1, 2
 
+
+
+class MinmaxMember(C.Structure):
+    """ntg_minmax_member: q_form(z) + c + fprm[pc] (index -1: no parameter)"""
+    _fields_ = [("form", C.c_int), ("pc", C.c_int), ("c", C.c_double)]
+
+
+class MinmaxGroup(C.Structure):
+    """ntg_minmax_group: OUTER over nclause clauses of INNER over nmem[k] members each, outer / inner = MINMAX_MIN or MINMAX_MAX"""
+    _fields_ = [("outer", C.c_int), ("inner", C.c_int), ("nclause", C.c_int), ("pad", C.c_int), ("nmem", C.c_int * 8)]
+
+
+MINMAX_MIN, MINMAX_MAX = 0, 1
+MINMAX_MAXFORMS, MINMAX_MAXTERMS, MINMAX_MAXGROUPS, MINMAX_MAXCLAUSES, MINMAX_MAXMEMBERS = 16, 40, 4, 8, 16   # NTG_MINMAX_*
+
 _lib = None
 
 
@@ -108,6 +123,8 @@ def lib():
         L.ntg_batch_ratios.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, ip, C.POINTER(FormTerm), C.c_int, C.c_void_p, C.c_int, C.POINTER(Ratio), C.c_double, C.c_int,
                                        C.c_int] + [C.c_void_p] * 9
         L.ntg_batch_trig.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, ip, C.POINTER(TrigTerm), C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_int] + [C.c_void_p] * 9
+        L.ntg_batch_minmax.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, ip, C.POINTER(FormTerm), C.c_int, C.c_void_p, C.c_int, C.POINTER(MinmaxGroup), C.POINTER(MinmaxMember),
+                                       C.c_double, C.c_int, C.c_int] + [C.c_void_p] * 10
         L.ntg_batch_refine.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ntg_plan_set_grids.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ntg_plan_clear_grids.argtypes = [C.c_void_p]
@@ -607,6 +624,34 @@ class Plan:
         _check(lib().ntg_batch_trig(self.h, batch, _ptr(x), nform, nterms, terms, 0 if fprm is None else int(fprm.shape[1]), _ptr(fprm), float(tol), int(max_depth),
                                     int(sides), _ptr(lower), _ptr(upper), _ptr(out["ext"]), _ptr(out["when"]), _ptr(out["status"]), _ptr(out["npieces"]),
                                     _ptr(out.get("viol")), _ptr(out.get("where")), self._stream()))
+        return out
+
+    def minmax(self, x, forms, groups, tol, max_depth: int = 30, sides: int = 3, fprm=None, lower=None, upper=None):
+        """The minimum and maximum over the whole horizon of min / max expressions over quadratic forms of the flat flag, each enclosed to tol,
+        by bisection of pieces that carry the polygons of all members (ntg_batch_minmax): forms as for Plan.forms (up to MINMAX_MAXFORMS, 40
+        terms together); groups is a list of up to MINMAX_MAXGROUPS triples (outer, inner, clauses), clauses a list of lists of members
+        (form, c, pc): h = OUTER over the clauses of INNER over the clause's members of q_form(z) + c + fprm[b, pc].  The constructors of
+        ntg_amd.minmax build both (polygon, box, corridor, discs, merge).  Returns the dict of Plan.forms with the group in the place of the
+        form, plus which [batch, ngroup, 2]: the member, by its index in the group's concatenated list, that decides h at t_min and at t_max.
+        lower / upper [batch, ngroup]; viol[:, 1] == 0 certifies every group over the whole horizon."""
+        import torch
+        sp, dev, batch = self._cert_inputs(x, None, None)
+        forms = list(forms)
+        groups = [(int(o), int(i), [[(int(f), float(c), int(pc)) for f, c, pc in cl] for cl in cls]) for o, i, cls in groups]
+        nform, ngroup = len(forms), len(groups)
+        nterms, terms, nfp = _declare_forms(forms, fprm, lower, upper, dev, batch, ngroup, "groups")
+        for g, (o, i, cls) in enumerate(groups):
+            if len(cls) > MINMAX_MAXCLAUSES:
+                raise NtgError(f"group {g}: nclause = {len(cls)} must lie in 1 .. {MINMAX_MAXCLAUSES}")
+        pad = lambda v: (C.c_int * 8)(*(list(v) + [0] * (8 - len(v))))
+        grp = (MinmaxGroup * max(ngroup, 1))(*[MinmaxGroup(o, i, len(cls), 0, pad([len(cl) for cl in cls])) for o, i, cls in groups])
+        flat = [MinmaxMember(f, pc, c) for _, _, cls in groups for cl in cls for f, c, pc in cl]
+        mem = (MinmaxMember * max(len(flat), 1))(*flat)
+        out = _bisect_out(batch, ngroup, dev, lower is not None)
+        out["which"] = torch.empty((batch, max(ngroup, 1), 2), dtype=torch.int32, device=dev)
+        _check(lib().ntg_batch_minmax(self.h, batch, _ptr(x), nform, nterms, terms, nfp, _ptr(fprm), ngroup, grp, mem, float(tol), int(max_depth), int(sides),
+                                      _ptr(lower), _ptr(upper), _ptr(out["ext"]), _ptr(out["when"]), _ptr(out["which"]), _ptr(out["status"]), _ptr(out["npieces"]),
+                                      _ptr(out.get("viol")), _ptr(out.get("where")), self._stream()))
         return out
 
     def set_grids(self, knots, bps, with_precond: bool = True):

@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libntg_amd.so")
-SOURCES = ["basis.hip", "hostpath.hip", "times.hip", "mpc.hip", "certs.hip", "ratios.hip", "trig.hip", "grids.hip", "fam_kincar.hip", "fam_kincar_chm.hip", "fam_kincar_wave.hip", "fam_vanderpol.hip",
+SOURCES = ["basis.hip", "hostpath.hip", "times.hip", "mpc.hip", "certs.hip", "ratios.hip", "trig.hip", "minmax.hip", "grids.hip", "fam_kincar.hip", "fam_kincar_chm.hip", "fam_kincar_wave.hip", "fam_vanderpol.hip",
            "fam_testfam.hip", "fam_obstacle.hip", "fam_quadrotor.hip", "fam_manip.hip", "fam_obstacle_field.hip", "plan.cpp", "plan_solve.cpp", "plan_times.cpp", "plan_build.cpp",
            "plan_grids.cpp", "plan_refine.cpp", "plan_kkt.cpp", "plan_cost.cpp", "plan_verify.cpp", "plan_cert.cpp", "ntg_host.cpp", "layout.cpp", "family_registry.cpp"]
 HEADERS = sorted(os.path.basename(f) for f in glob.glob(os.path.join(CSRC, "*.hpp"))) + ["../../include/" + f for f in ("ntg_amd.h", "ntg.h", "ntg_amd_family.hpp")]   # every header: rebuild tests, ABI stamp

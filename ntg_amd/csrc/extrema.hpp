@@ -23,7 +23,9 @@
 // No scratch in HBM, no atomics, nothing depends on the batch around a problem.  Every private array is indexed by unrolled loop counters only.
 // The levels themselves (ext_levels) take the row as a source of level-0 polygons and a threshold flag: ext_row hands them a row of the plan,
 // forms.hpp a declared form, separation.hpp the squared difference of two trajectories, with its "not plo >= s2" in the opening rule.
-// ratio_levels (ratios.hpp) is its twin on pairs of polygons, kept in step by hand: whoever edits ext_levels edits that one too.  One loop
+// ratio_levels (ratios.hpp) is its twin on pairs of polygons, kept in step by hand: whoever edits ext_levels edits that one too -- and
+// trig_levels (trig.hpp, pieces of up to four angle polygons) and, the third loop on polygons proper, minmax_levels (minmax.hpp: pieces of
+// up to 16 member polygons, which do not fit the registers, so that loop sweeps the members twice per level over a member-major list).  One loop
 // templated over the piece gives the same bits (tests/golden holds both to recorded results) and no worse registers, but it cost the extrema
 // and separation kernels 1 to 2 % of their rate, more than their run-to-run spread: DESIGN.md has the figures.  The two loops share the
 // de Casteljau split (ext_split) and the epilogue (ExtOut: a row's outputs, and the violation of a problem folded over its rows).

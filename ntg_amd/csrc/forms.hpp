@@ -89,11 +89,15 @@ __device__ __forceinline__ void form_term_into(EnvPoly<2 * KM - 1> &S, const Env
 }
 
 // what the kernels know of form f
-struct FormOf { const FormArgs &A; int f; FormRow R; EnvClass C; };
+struct FormOf {
+	const FormArgs &A; int f; FormRow R; EnvClass C;
+	__device__ __forceinline__ const FormTerm &term(int t) const { return A.term[f][t]; }
+};
 
-// Polygon (degree R.D) of a form on knot interval j: its terms' polygons, elevated to R.D where they are lower, summed in declared order
-template <int KM>
-__device__ __forceinline__ EnvPoly<2 * KM - 1> form_poly(const FormOf &F, const ExtLds &M, int j)
+// Polygon (degree R.D) of a form on knot interval j: its terms' polygons, elevated to R.D where they are lower, summed in declared order.
+// FO: what the caller knows of the form -- its row R, its class C and its terms term(t) (FormOf here, MinmaxFormOf in minmax.hpp)
+template <int KM, class FO>
+__device__ __forceinline__ EnvPoly<2 * KM - 1> form_poly(const FO &F, const ExtLds &M, int j)
 {
 #pragma clang fp contract(off)
 	constexpr int KD = 2 * KM - 1;
@@ -104,7 +108,7 @@ __device__ __forceinline__ EnvPoly<2 * KM - 1> form_poly(const FormOf &F, const 
 #pragma unroll
 	for (int s = 0; s < KD; s++) S.b[s] = 0.0;
 	for (int t = 0; t < F.R.nt; t++) {
-		const FormTerm &Q = F.A.term[F.f][t];
+		const FormTerm &Q = F.term(t);
 		const int kind = Q.kind;
 		const double w = Q.w;
 		EnvPoly<KM> P, V;

@@ -397,7 +397,7 @@ static inline size_t ntg_separation_lds(const SepArgs &A) { return ntg_separatio
 #define NTG_FORM_PROD 1     // w (z[u] - a)(z[v] - b)
 #define NTG_FORM_SQUARE 2   // ... with the same entry, parameter and constant twice: formed as envelope_sos.hpp forms a square
 struct FormTerm { int iCu, iCv, pu, pv; short ru, rv, kind, pad; double w, su, sv; };
-struct FormRow { int nt, cl, D, pad; };
+struct FormRow { int nt, cl, D, t0; };   // t0: the form's first term where the terms of all forms lie in one flat table (MinmaxArgs); 0 here
 struct FormArgs {
 	CertBase g;
 	int nform, nfp;
@@ -464,3 +464,32 @@ static inline __host__ __device__ int ntg_trig_w(const CertBase &G) { return NTG
 // dynamic LDS: no tables in front; a coefficient row and a row of fprm per wave.  The limit is ntg_batch_extrema's
 static __host__ __device__ __forceinline__ BisectLds ntg_trig_layout(const TrigArgs &A, int W) { return BisectLds{0, A.g.ne, A.q.nk, A.g.nC, A.nprm, W, A.g.pp}; }
 static inline size_t ntg_trig_lds(const TrigArgs &A, int nw) { return ntg_trig_layout(A, ntg_trig_w(A.g)).bytes(nw); }
+
+// ntg_batch_minmax (minmax.hpp): the minimum and maximum over the horizon of lattice expressions h_g = OUTER_k INNER_j m_kj over quadratic
+// forms that the CALLER declares, m = q_form(z) + d.  row / term: the forms in ntg_batch_forms' kernel form, the terms of all forms in ONE
+// flat table (row[f].t0 is form f's first).  mem: the members of all groups, group after group, clause after clause; c and pc give d = c +
+// fprm_b[pc].  grp[g]: outer / inner (NTG_MINMAX_MIN / _MAX), its nm members from mem[m0], the basis class cl of all its forms, the degree D
+// of its polygons (the largest of its forms'), and clast: bit m is set where member m is the last of its clause.  mcap: members the work
+// list has room for (8 or 16), pw: doubles of one polygon in it (the instance's points, made odd), nw: waves of a workgroup (4, 2 or 1).
+// glo / ghi [batch][ngroup] (null unless a violation is asked for), which [batch][ngroup][2] or null.  Outputs (q) as documented at
+// ntg_batch_minmax, any may be null.
+#define NTG_MINMAX_MAXMEMTOT 32
+struct MinmaxMem { int form, pc; double c; };
+struct MinmaxGroup { int outer, inner, nm, m0, cl, D; unsigned int clast; int pad; };
+struct MinmaxArgs {
+	CertBase g;
+	int nform, nfp, ngroup, nw, mcap, pw, pad0, pad1;
+	CertBisect q;
+	FormRow row[NTG_MINMAX_MAXFORMS];
+	FormTerm term[NTG_MINMAX_MAXTERMS];
+	MinmaxGroup grp[NTG_MINMAX_MAXGROUPS];
+	MinmaxMem mem[NTG_MINMAX_MAXMEMTOT];
+	const double *fprm, *glo, *ghi; int *which;
+};
+static_assert(sizeof(MinmaxArgs) <= 4096, "MinmaxArgs travels as a kernel argument");
+// points of the polygons of a call's instance: 6 (every group linear on a plan of largest order <= 6), 11 (that plan, quadratic members) or 19
+static inline __host__ __device__ int ntg_minmax_points(const CertBase &G, int dmax) { return G.kmax > 6 ? 2 * NTG_MAX_ORDER - 1 : dmax <= 5 ? 6 : 11; }
+// dynamic LDS: the product tables (built on the device) in front; a coefficient row and a row of fprm per wave.  The work list is
+// member-major, list[member][slot][pw]: the BisectLds element is the mcap polygons of a slot taken together.  The limit is ntg_batch_extrema's
+static __host__ __device__ __forceinline__ BisectLds ntg_minmax_layout(const MinmaxArgs &A) { return BisectLds{NTG_FORM_WALL, A.g.ne, A.q.nk, A.g.nC, A.nfp, A.mcap * A.pw, A.g.pp}; }
+static inline size_t ntg_minmax_lds(const MinmaxArgs &A, int nw) { return ntg_minmax_layout(A).bytes(nw); }

@@ -118,6 +118,10 @@ hipError_t ntg_launch_ratios(const RatioArgs &A, int ncu, hipStream_t st);
 // of several angle polygons (trig.hpp) ----
 hipError_t ntg_launch_trig(const TrigArgs &A, int ncu, hipStream_t st);
 
+// ---- minmax.hip: minimum and maximum over the horizon of min / max expressions over declared forms, by the certificates' bisection on
+// pieces that carry the polygons of all members of a group (minmax.hpp) ----
+hipError_t ntg_launch_minmax(const MinmaxArgs &A, int ncu, hipStream_t st);
+
 // ---- grids.hip: per-problem grids, the device-side setup algebra ----
 struct NtgGridLin {
 	const double *blk, *linrows; const int *plan_off, *erow, *csr_ptr, *csr_col, *csc_ptr, *csc_row, *sinv_ptr, *sinv_col, *q_col, *q_row2coef;

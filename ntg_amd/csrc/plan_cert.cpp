@@ -1,9 +1,9 @@
 // plan_cert.cpp -- the time certificates behind include/ntg_amd.h: ntg_batch_envelope, ntg_batch_envelope_sos, ntg_batch_extrema,
-// ntg_batch_separation, ntg_batch_forms, ntg_batch_ratios, ntg_batch_trig and the queries ntg_plan_sos_rows and ntg_plan_extrema_rows.  What they share comes first: the refusals (each call tests them between its own
+// ntg_batch_separation, ntg_batch_forms, ntg_batch_ratios, ntg_batch_trig, ntg_batch_minmax and the queries ntg_plan_sos_rows and ntg_plan_extrema_rows.  What they share comes first: the refusals (each call tests them between its own
 // argument checks, in its own order), which rows of a plan are certified -- a linear trajectory row whose outputs share a basis class, from
 // the host mirror of ltc; a nonlinear row by the family's sum-of-squares declaration, NtgFamily::sos, against the plan's iz / cls -- and the
 // three parts of the kernels' arguments (CertBase, CertLin, CertSos: ntg_dev.hpp).  An entry point then reads: its own argument checks,
-// the setup, its own fields, the launch.  The arithmetic is in envelope.hpp, envelope_sos.hpp, extrema.hpp, separation.hpp, forms.hpp, ratios.hpp and trig.hpp.  No family callback runs, so
+// the setup, its own fields, the launch.  The arithmetic is in envelope.hpp, envelope_sos.hpp, extrema.hpp, separation.hpp, forms.hpp, ratios.hpp, trig.hpp and minmax.hpp.  No family callback runs, so
 // the calls serve every built-in family and every loaded module.  They allocate nothing.
 #include <cstring>
 #include "plan_priv.hpp"
@@ -350,17 +350,20 @@ extern "C" int ntg_batch_separation(const ntg_plan *p, int batch, const double *
 	return 0;
 }
 
-// ---------------- forms declared at the call (ntg_batch_forms, ntg_batch_ratios) ----------------
+// ---------------- forms declared at the call (ntg_batch_forms, ntg_batch_ratios, ntg_batch_minmax) ----------------
 namespace {
 // the first form that names two basis classes, and two outputs that show it
 struct FormCross { int form = -1, a = -1, b = -1; };
-// the arguments that declare the forms, checked in ntg_batch_forms' order, and the forms in the kernels' form (A.row, A.term)
+// where a declaration goes: rows [maxforms], and the terms either [maxforms][NTG_FORM_MAXTERMS] (flat = false: FormArgs) or one table of
+// maxterms for all forms, row.t0 the form's first (flat = true: MinmaxArgs)
+struct FormSink { FormRow *row; FormTerm *term; int maxforms, maxterms; bool flat; };
+// the arguments that declare the forms, checked in ntg_batch_forms' order, and the forms in the kernels' form (S.row, S.term)
 int forms_declare(const ntg_plan *p, const double *d_x, int nform, const int *form_nterms, const ntg_form_term *terms, int nfp, const double *d_fprm,
-                  double tol, int max_depth, int sides, FormArgs &A, FormCross &X)
+                  double tol, int max_depth, int sides, const FormSink &S, FormCross &X)
 {
 	if (!p) return fail(NTG_E_BADARG, "null plan");
 	if (!d_x || !form_nterms || !terms) return fail(NTG_E_BADARG, "null argument");
-	if (nform < 0 || nform > NTG_FORM_MAXFORMS) return fail(NTG_E_BADARG, "nform must lie in 0 .. " + std::to_string(NTG_FORM_MAXFORMS));
+	if (nform < 0 || nform > S.maxforms) return fail(NTG_E_BADARG, "nform must lie in 0 .. " + std::to_string(S.maxforms));
 	if (nfp < 0) return fail(NTG_E_BADARG, "nfp must be >= 0");
 	if (int rc = cert_levels(tol, max_depth)) return rc;
 	if (int rc = cert_sides(sides)) return rc;
@@ -370,7 +373,11 @@ int forms_declare(const ntg_plan *p, const double *d_x, int nform, const int *fo
 		const int nt = form_nterms[f];
 		const std::string fname = "form " + std::to_string(f);
 		if (nt < 1 || nt > NTG_FORM_MAXTERMS) return fail(NTG_E_BADARG, fname + " has " + std::to_string(nt) + " terms: 1 .. " + std::to_string(NTG_FORM_MAXTERMS) + " are taken");
-		FormRow &R = A.row[f];
+		FormRow &R = S.row[f];
+		const int t0 = (int)(q - terms);
+		if (S.flat && t0 + nt > S.maxterms)
+			return fail(NTG_E_BADARG, fname + " brings the terms of all forms to " + std::to_string(t0 + nt) + ": " + std::to_string(S.maxterms) + " are taken at one call");
+		R.t0 = S.flat ? t0 : 0;
 		int first = -1;
 		for (int t = 0; t < nt; t++, q++) {
 			const std::string tname = fname + ", term " + std::to_string(t);
@@ -387,7 +394,7 @@ int forms_declare(const ntg_plan *p, const double *d_x, int nform, const int *fo
 				if (D.cls[o] != R.cl && X.form < 0) { X.form = f; X.a = first; X.b = o; }
 			const int du = std::max(D.order[eu.o] - 1 - eu.r, 0), dv = lin ? 0 : std::max(D.order[ev.o] - 1 - ev.r, 0);
 			R.D = std::max(R.D, du + dv);
-			FormTerm &T = A.term[f][t];
+			FormTerm &T = S.term[S.flat ? t0 + t : f * NTG_FORM_MAXTERMS + t];
 			T.iCu = D.iC[eu.o]; T.ru = (short)eu.r; T.pu = q->pu; T.su = q->su; T.w = q->w;
 			T.iCv = lin ? 0 : D.iC[ev.o]; T.rv = (short)(lin ? 0 : ev.r); T.pv = lin ? -1 : q->pv; T.sv = lin ? 0.0 : q->sv;
 			T.kind = lin ? NTG_FORM_LIN : (q->v == q->u && q->pu == q->pv && std::memcmp(&q->su, &q->sv, sizeof(double)) == 0) ? NTG_FORM_SQUARE : NTG_FORM_PROD;
@@ -415,6 +422,8 @@ int forms_refuse(const ntg_plan *p, int batch, const FormCross &X)
 		                                   " of different basis classes: it has no common pieces");
 	return 0;
 }
+// the tables of ntg_batch_forms and ntg_batch_ratios as a sink
+FormSink forms_sink(FormArgs &A) { return FormSink{A.row, &A.term[0][0], NTG_FORM_MAXFORMS, NTG_FORM_MAXFORMS * NTG_FORM_MAXTERMS, false}; }
 // the kernels' arguments but the launch figures, the forms' parameters and the bounds
 void forms_args(const ntg_plan *p, int batch, const double *d_x, int nform, int nfp, FormArgs &A)
 {
@@ -429,7 +438,7 @@ extern "C" int ntg_batch_forms(const ntg_plan *p, int batch, const double *d_x, 
 {
 	FormArgs A{};
 	FormCross X;
-	if (int rc = forms_declare(p, d_x, nform, form_nterms, terms, nfp, d_fprm, tol, max_depth, sides, A, X)) return rc;
+	if (int rc = forms_declare(p, d_x, nform, form_nterms, terms, nfp, d_fprm, tol, max_depth, sides, forms_sink(A), X)) return rc;
 	if (int rc = forms_outputs(d_flo, d_fhi, "d_flo", "d_fhi", d_ext, d_when, d_status, d_npieces, d_viol, d_where)) return rc;
 	if (batch <= 0 || nform == 0) return 0;
 	if (int rc = forms_refuse(p, batch, X)) return rc;
@@ -449,7 +458,7 @@ extern "C" int ntg_batch_ratios(const ntg_plan *p, int batch, const double *d_x,
 {
 	RatioArgs A{};
 	FormCross X;
-	if (int rc = forms_declare(p, d_x, nform, form_nterms, terms, nfp, d_fprm, tol, max_depth, sides, A.f, X)) return rc;
+	if (int rc = forms_declare(p, d_x, nform, form_nterms, terms, nfp, d_fprm, tol, max_depth, sides, forms_sink(A.f), X)) return rc;
 	if (nratio < 0 || nratio > NTG_RATIO_MAXRATIOS) return fail(NTG_E_BADARG, "nratio must lie in 0 .. " + std::to_string(NTG_RATIO_MAXRATIOS));
 	if (nratio > 0 && !ratios) return fail(NTG_E_BADARG, "null argument");
 	for (int r = 0; r < nratio; r++) {
@@ -581,5 +590,85 @@ extern "C" int ntg_batch_trig(const ntg_plan *p, int batch, const double *d_x, i
 	A.fprm = d_fprm; A.flo = d_flo; A.fhi = d_fhi;
 	HIPCHK(hipSetDevice(p->device));
 	HIPCHK(ntg_launch_trig(A, plan_ncu(p), (hipStream_t)stream));
+	return 0;
+}
+
+// ---------------- min / max expressions over forms declared at the call (ntg_batch_minmax) ----------------
+extern "C" int ntg_batch_minmax(const ntg_plan *p, int batch, const double *d_x, int nform, const int *form_nterms, const ntg_form_term *terms, int nfp, const double *d_fprm,
+                                int ngroup, const ntg_minmax_group *groups, const ntg_minmax_member *members, double tol, int max_depth, int sides,
+                                const double *d_glo, const double *d_ghi, double *d_ext, double *d_when, int *d_which, int *d_status, int *d_npieces,
+                                double *d_viol, int *d_where, void *stream)
+{
+	MinmaxArgs A{};
+	FormCross X;
+	if (int rc = forms_declare(p, d_x, nform, form_nterms, terms, nfp, d_fprm, tol, max_depth, sides, FormSink{A.row, A.term, NTG_MINMAX_MAXFORMS, NTG_MINMAX_MAXTERMS, true}, X)) return rc;
+	if (ngroup < 0 || ngroup > NTG_MINMAX_MAXGROUPS) return fail(NTG_E_BADARG, "ngroup must lie in 0 .. " + std::to_string(NTG_MINMAX_MAXGROUPS));
+	if (ngroup > 0 && (!groups || !members)) return fail(NTG_E_BADARG, "null argument: groups and members");
+	int mtot = 0, mmax = 0;
+	for (int g = 0; g < ngroup; g++) {
+		const ntg_minmax_group &Q = groups[g];
+		const std::string gname = "group " + std::to_string(g);
+		MinmaxGroup &G = A.grp[g];
+		if (Q.outer < NTG_MINMAX_MIN || Q.outer > NTG_MINMAX_MAX || Q.inner < NTG_MINMAX_MIN || Q.inner > NTG_MINMAX_MAX)
+			return fail(NTG_E_BADARG, gname + ": outer and inner must be NTG_MINMAX_MIN (0) or NTG_MINMAX_MAX (1)");
+		if (Q.nclause < 1 || Q.nclause > NTG_MINMAX_MAXCLAUSES) return fail(NTG_E_BADARG, gname + ": nclause = " + std::to_string(Q.nclause) + " must lie in 1 .. " + std::to_string(NTG_MINMAX_MAXCLAUSES));
+		G.outer = Q.outer; G.inner = Q.inner; G.m0 = mtot;
+		for (int k = 0; k < Q.nclause; k++) {
+			const std::string cname = gname + ", clause " + std::to_string(k);
+			const int n = Q.nmem[k];
+			if (n < 1) return fail(NTG_E_BADARG, cname + " has " + std::to_string(n) + " members: a clause needs at least one");
+			if (n > NTG_MINMAX_MAXMEMBERS || G.nm + n > NTG_MINMAX_MAXMEMBERS)
+				return fail(NTG_E_BADARG, cname + " brings the group to " + std::to_string(G.nm + n) + " members: at most " + std::to_string(NTG_MINMAX_MAXMEMBERS) + " are taken");
+			if (mtot + n > NTG_MINMAX_MAXMEMTOT)
+				return fail(NTG_E_BADARG, cname + " brings the members of all groups to " + std::to_string(mtot + n) + ": at most " + std::to_string(NTG_MINMAX_MAXMEMTOT) + " are taken");
+			for (int j = 0; j < n; j++) {
+				const ntg_minmax_member &m = members[mtot + j];
+				const std::string mname = cname + ", member " + std::to_string(j);
+				if (m.form < 0 || m.form >= nform) return fail(NTG_E_BADARG, mname + " names form " + std::to_string(m.form) + ": the call declares forms 0 .. " + std::to_string(nform - 1));
+				if (m.pc < -1 || m.pc >= nfp) return fail(NTG_E_BADARG, mname + ": pc must lie in -1 .. nfp - 1 = " + std::to_string(nfp - 1));
+				if (m.pc >= 0 && !d_fprm) return fail(NTG_E_BADARG, mname + " names a parameter, but d_fprm is null");
+				if (!std::isfinite(m.c)) return fail(NTG_E_BADARG, mname + ": c must be finite");
+				A.mem[mtot + j] = MinmaxMem{m.form, m.pc, m.c};
+			}
+			mtot += n; G.nm += n;
+			G.clast |= 1u << (G.nm - 1);
+		}
+		mmax = std::max(mmax, G.nm);
+	}
+	const bool want_v = d_viol || d_where;
+	if (!d_ext && !d_when && !d_which && !d_status && !d_npieces && !want_v)
+		return fail(NTG_E_BADARG, "no output asked for: pass d_ext, d_when, d_which, d_status, d_npieces, d_viol or d_where");
+	if (want_v && (!d_glo || !d_ghi)) return fail(NTG_E_BADARG, "d_viol / d_where need the bounds d_glo and d_ghi");
+	if (batch <= 0 || ngroup == 0) return 0;
+	if (int rc = forms_refuse(p, batch, X)) return rc;
+	const NtgDims &D = p->D;
+	int dmax = 0;
+	for (int g = 0; g < ngroup; g++) {   // the one class and the degree of every group
+		MinmaxGroup &G = A.grp[g];
+		const int f0 = A.mem[G.m0].form;
+		G.cl = A.row[f0].cl;
+		for (int m = G.m0; m < G.m0 + G.nm; m++) {
+			const FormRow &R = A.row[A.mem[m].form];
+			if (R.cl != G.cl) {   // two outputs that show it: the first entry of each form
+				const auto out_of = [&](int f) { const int u = terms[A.row[f].t0].u; return flag_entry(D, u).o; };
+				return fail(NTG_E_UNSUPPORTED, "group " + std::to_string(g) + " names forms " + std::to_string(f0) + " and " + std::to_string(A.mem[m].form) + " on outputs " +
+				                                   std::to_string(out_of(f0)) + " and " + std::to_string(out_of(A.mem[m].form)) + " of different basis classes: it has no common pieces");
+			}
+			G.D = std::max(G.D, R.D);
+		}
+		dmax = std::max(dmax, G.D);
+	}
+	cert_base(p, batch, d_x, nullptr, nullptr, A.g, A.q.koff, &A.q.nk);
+	A.nform = nform; A.nfp = nfp; A.ngroup = ngroup;
+	cert_bisect(A.q, tol, max_depth, sides, d_ext, d_when, d_status, d_npieces, d_viol, d_where);
+	A.mcap = mmax <= 8 ? 8 : NTG_MINMAX_MAXMEMBERS;
+	A.pw = ntg_minmax_points(A.g, dmax) | 1;
+	A.nw = ntg_minmax_lds(A, 4) <= NTG_EXTREMA_LDS_MAX ? 4 : ntg_minmax_lds(A, 2) <= NTG_EXTREMA_LDS_MAX ? 2 : 1;
+	if (A.g.kmax > NTG_MAX_ORDER || ntg_minmax_lds(A, A.nw) > NTG_EXTREMA_LDS_MAX)
+		return fail(NTG_E_UNSUPPORTED, "the tables and work lists of this call exceed " + std::to_string(NTG_EXTREMA_LDS_MAX / 1024) + " KiB of LDS even with one wavefront: the product and class tables, and per wavefront nC + nfp + " +
+		                                   std::to_string(NTG_EXTREMA_CAP) + " (" + std::to_string(A.mcap) + " * " + std::to_string(A.pw) + " + 1) doubles");
+	A.fprm = d_fprm; A.glo = d_glo; A.ghi = d_ghi; A.which = d_which;
+	HIPCHK(hipSetDevice(p->device));
+	HIPCHK(ntg_launch_minmax(A, plan_ncu(p), (hipStream_t)stream));
 	return 0;
 }
