@@ -22,27 +22,13 @@
 #include "separation.hpp"
 #include "forms.hpp"
 #include "kkt.hpp"
+#include "cert_launch.hpp"
 
-// The time certificates (envelope.hpp, envelope_sos.hpp, extrema.hpp).  Each has a kernel for per-problem grids (kpp: one problem per wave,
-// a workgroup per nt / 64 problems) and one for shared grids (ksh: persistent workgroups; each builds its weights once, so each should
-// stream several of the `units` of work: a workgroup for every four of them, no more than fill the device), both in the instance with the
-// smallest private polygons that hold the plan's largest order (KM = 6 or NTG_MAX_ORDER).
-template <class Args>
-static hipError_t launch_cert(void (*kpp)(Args), void (*ksh)(Args), const Args &A, int nt, int units, int ncu, size_t lds, hipStream_t st)
-{
-	const int groups = (A.g.batch + nt / 64 - 1) / (nt / 64);
-	auto kfn = A.g.pp ? kpp : ksh;
-	if (lds > 64 * 1024) {
-		const hipError_t e = hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-		if (e != hipSuccess) return e;
-	}
-	const int grid = A.g.pp ? std::min(groups, 8 * ncu) : std::max(1, std::min((units + 3) / 4, 8 * ncu));
-	hipLaunchKernelGGL(kfn, dim3(grid), dim3(nt), lds, st, A);
-	return hipGetLastError();
-}
+// The time certificates, through launch_cert (cert_launch.hpp): both kernels in the instance with the smallest private polygons that hold the
+// plan's largest order (KM = 6 or NTG_MAX_ORDER).
 #define NTG_CERT_LAUNCH(name, NT, units)                                                                                    \
-	(A.g.kmax <= 6 ? launch_cert(name##_pp_kernel<NT, 6>, name##_shared_kernel<NT, 6>, A, NT, units, ncu, lds, st) \
-	               : launch_cert(name##_pp_kernel<NT, NTG_MAX_ORDER>, name##_shared_kernel<NT, NTG_MAX_ORDER>, A, NT, units, ncu, lds, st))
+	(A.g.kmax <= 6 ? launch_cert(name##_pp_kernel<NT, 6>, name##_shared_kernel<NT, 6>, A, A.g, NT, units, ncu, lds, st) \
+	               : launch_cert(name##_pp_kernel<NT, NTG_MAX_ORDER>, name##_shared_kernel<NT, NTG_MAX_ORDER>, A, A.g, NT, units, ncu, lds, st))
 
 // hipErrorInvalidValue: the tables exceed the LDS (the entry points refuse such a plan before it gets here).  On shared grids a workgroup of
 // the two envelope calls takes one problem at a time ...
@@ -85,8 +71,8 @@ hipError_t ntg_launch_separation(const SepArgs &A, int ncu, hipStream_t st)
 	if (lds > NTG_EXTREMA_LDS_MAX || A.g.kmax > NTG_MAX_ORDER || A.g.pp || A.g.nclass != 1) return hipErrorInvalidValue;
 	if (A.npairs <= 0 || A.g.batch <= 0) return hipSuccess;
 	const int units = (A.npairs + NT / 64 - 1) / (NT / 64);
-	return A.g.kmax <= 6 ? launch_cert<SepArgs>(nullptr, separation_kernel<NT, 6>, A, NT, units, ncu, lds, st)
-	                     : launch_cert<SepArgs>(nullptr, separation_kernel<NT, NTG_MAX_ORDER>, A, NT, units, ncu, lds, st);
+	return A.g.kmax <= 6 ? launch_cert<SepArgs>(nullptr, separation_kernel<NT, 6>, A, A.g, NT, units, ncu, lds, st)
+	                     : launch_cert<SepArgs>(nullptr, separation_kernel<NT, NTG_MAX_ORDER>, A, A.g, NT, units, ncu, lds, st);
 }
 
 // ntg_batch_refine (refine.hpp): coefficients on a finer knot grid.  pp != 0: per-problem grids.  hipErrorInvalidValue: the tables exceed the LDS.

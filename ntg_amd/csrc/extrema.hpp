@@ -25,7 +25,8 @@
 // forms.hpp a declared form, separation.hpp the squared difference of two trajectories, with its "not plo >= s2" in the opening rule.
 // ratio_levels (ratios.hpp) is its twin on pairs of polygons, kept in step by hand: whoever edits ext_levels edits that one too -- and
 // trig_levels (trig.hpp, pieces of up to four angle polygons) and, the third loop on polygons proper, minmax_levels (minmax.hpp: pieces of
-// up to 16 member polygons, which do not fit the registers, so that loop sweeps the members twice per level over a member-major list).  One loop
+// up to 16 member polygons, which do not fit the registers, so that loop sweeps the members twice per level over a member-major list).  By
+// hand, but held in step by the tests: tests/bisect_oracle.py is the one written sequence all of them are tested against.  One loop
 // templated over the piece gives the same bits (tests/golden holds both to recorded results) and no worse registers, but it cost the extrema
 // and separation kernels 1 to 2 % of their rate, more than their run-to-run spread: DESIGN.md has the figures.  The two loops share the
 // de Casteljau split (ext_split) and the epilogue (ExtOut: a row's outputs, and the violation of a problem folded over its rows).
@@ -34,6 +35,12 @@
 #pragma once
 #include "wave_ops.hpp"
 #include "envelope_sos.hpp"
+
+// a declared-form call's own parameter row of problem b (forms, ratios, trig; minmax.hpp writes the loop out), by one wave
+__device__ __forceinline__ void cert_stage_fprm(const double *fprm, int nfp, int b, double *row, int lane)
+{
+	for (int i = lane; i < nfp; i += 64) row[i] = fprm[(size_t)b * nfp + i];
+}
 
 // (value, time) minimum / maximum: on equal values the smaller time; a NaN is never taken
 __device__ __forceinline__ void ext_take_min(double &v, double &t, double ov, double ot) { if (ov < v || (ov == v && ot < t)) { v = ov; t = ot; } }

@@ -175,12 +175,6 @@ __device__ __forceinline__ void form_problem(const FormArgs &A, const ExtLds &M,
 	O.problem(b);
 }
 
-// the call's own parameter row of problem b, by one wave
-__device__ __forceinline__ void form_stage_fprm(const FormArgs &A, int b, double *frow, int lane)
-{
-	for (int i = lane; i < A.nfp; i += 64) frow[i] = A.fprm[(size_t)b * A.nfp + i];
-}
-
 template <int NT, int KM>
 __global__ void __launch_bounds__(NT)
 forms_shared_kernel(FormArgs A)
@@ -198,7 +192,7 @@ forms_shared_kernel(FormArgs A)
 		if (b >= A.g.batch) continue;
 		__builtin_amdgcn_wave_barrier();   // the problem before is done with the rows
 		env_stage_rows(A.g, nullptr, b, S.xrow, nullptr, lane, 64);
-		form_stage_fprm(A, b, S.prow, lane);
+		cert_stage_fprm(A.fprm, A.nfp, b, S.prow, lane);
 		__builtin_amdgcn_wave_barrier();
 		form_problem<KM>(A, M, b, lane);
 	}
@@ -222,7 +216,7 @@ forms_pp_kernel(FormArgs A)
 		const int b = b0 + blockIdx.x * NW + wave;
 		const bool on = b < A.g.batch;
 		__syncthreads();
-		if (on) { env_stage_pp(A.g, nullptr, b, S.kns, S.xrow, nullptr, lane); form_stage_fprm(A, b, S.prow, lane); }
+		if (on) { env_stage_pp(A.g, nullptr, b, S.kns, S.xrow, nullptr, lane); cert_stage_fprm(A.fprm, A.nfp, b, S.prow, lane); }
 		__syncthreads();
 		if (on) env_build(S.kns, C, S.tab + C.eoff, S.tab + C.hoff, lane, 64);
 		__syncthreads();

@@ -1,5 +1,5 @@
-// minmax.hip -- the kernels of ntg_batch_minmax (minmax.hpp) and their launcher: a translation unit of its own, so that the instances of the
-// other bisection calls (certs.hip, ratios.hip, trig.hip) stay what they are.
+// minmax.hip -- the kernels of ntg_batch_minmax (minmax.hpp) and the checks of their launch: a translation unit of its own, so that the
+// instances of the other bisection calls (certs.hip, ratios.hip, trig.hip) stay what they are.
 //
 //   minmax_shared_kernel / minmax_pp_kernel <KM, KP>   KM = 6 or NTG_MAX_ORDER: points of a factor's polygon, by the plan's largest order;
 //                                                     KP = 6, 11 or 19: points of a member's polygon in the level loop and the work list,
@@ -12,20 +12,13 @@
 #include "ntg_dev.hpp"
 #include "plan.hpp"
 #include "minmax.hpp"
+#include "cert_launch.hpp"
 
+// launch_cert (cert_launch.hpp) with nw waves per workgroup and a pass of nw problems as the unit of work
 template <int KM, int KP>
 static hipError_t launch_minmax(const MinmaxArgs &A, int ncu, size_t lds, hipStream_t st)
 {
-	const int nw = A.nw, groups = (A.g.batch + nw - 1) / nw;
-	auto kfn = A.g.pp ? minmax_pp_kernel<KM, KP> : minmax_shared_kernel<KM, KP>;
-	if (lds > 64 * 1024) {
-		const hipError_t e = hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-		if (e != hipSuccess) return e;
-	}
-	// shared grids: persistent workgroups, each builds its tables once, so each should stream several passes; no more than fill the device
-	const int grid = A.g.pp ? std::min(groups, 8 * ncu) : std::max(1, std::min((groups + 3) / 4, 8 * ncu));
-	hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * nw), lds, st, A);
-	return hipGetLastError();
+	return launch_cert(minmax_pp_kernel<KM, KP>, minmax_shared_kernel<KM, KP>, A, A.g, 64 * A.nw, (A.g.batch + A.nw - 1) / A.nw, ncu, lds, st);
 }
 
 // hipErrorInvalidValue: the tables exceed the LDS or the declaration the kernels' tables (ntg_batch_minmax refuses such a call before it gets here)

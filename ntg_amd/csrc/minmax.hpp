@@ -10,7 +10,9 @@
 //   level 0   mm_member_poly on every knot interval j of the group's basis class: form_poly (forms.hpp) of the member's form, + d on every
 //             point, elevated to the group's degree.
 //   levels    minmax_levels: ext_levels (extrema.hpp) on pieces of nm polygons -- a third twin of that loop beside ratio_levels and
-//             trig_levels, kept in step by hand.  It shares ext_split, ext_time, ext_last, ExtRun and ExtOut with them.
+//             trig_levels, kept in step by hand and held in step by the tests: tests/bisect_oracle.py is the one written sequence all of
+//             them are tested against (this one by tests/test_gpu_minmax.py).  It shares ext_split, ext_time, ext_last, ExtRun and ExtOut
+//             with them.
 // A piece of 16 polygons of 11 points is 176 doubles: it is never in registers at once.  The work list is MEMBER-MAJOR, list[member][slot]
 // [PW], and a level makes two sweeps over the members:
 //   sweep 1   member by member: load the parent's polygon, split it (ext_split), fold plo, phi of both children and the value at the new end
@@ -322,6 +324,7 @@ minmax_shared_kernel(MinmaxArgs A)
 		if (b >= A.g.batch) continue;
 		__builtin_amdgcn_wave_barrier();   // the problem before is done with the rows
 		env_stage_rows(A.g, nullptr, b, S.xrow, nullptr, lane, 64);
+		// cert_stage_fprm (extrema.hpp) written out, here and below: through the helper these instances allocate their registers differently
 		for (int i = lane; i < A.nfp; i += 64) S.prow[i] = A.fprm[(size_t)b * A.nfp + i];
 		__builtin_amdgcn_wave_barrier();
 		minmax_problem<KM, KP>(A, M, b, lane);

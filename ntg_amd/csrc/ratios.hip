@@ -1,5 +1,5 @@
-// ratios.hip -- the kernels of ntg_batch_ratios (ratios.hpp) and their launcher: a translation unit of its own, because the instances carry
-// polygons of 13 or 25 points for both plan sizes and would double the build time of certs.hip.
+// ratios.hip -- the kernels of ntg_batch_ratios (ratios.hpp) and the checks of their launch: a translation unit of its own, because the
+// instances carry polygons of 13 or 25 points for both plan sizes and would double the build time of certs.hip.
 //
 //   ratios_shared_kernel / ratios_pp_kernel <KM, KR>   KM = 6 or NTG_MAX_ORDER: the forms' polygons, as in forms.hpp; KR = 13 or 25: points of the
 //                                                     pair's polygons, the smallest that holds the largest degree of the call's ratios
@@ -9,20 +9,13 @@
 #include "ntg_dev.hpp"
 #include "plan.hpp"
 #include "ratios.hpp"
+#include "cert_launch.hpp"
 
+// launch_cert (cert_launch.hpp) with nw waves per workgroup and a pass of nw problems as the unit of work
 template <int KM, int KR>
 static hipError_t launch_ratios(const RatioArgs &A, int ncu, size_t lds, hipStream_t st)
 {
-	const int nw = A.nw, groups = (A.f.g.batch + nw - 1) / nw;
-	auto kfn = A.f.g.pp ? ratios_pp_kernel<KM, KR> : ratios_shared_kernel<KM, KR>;
-	if (lds > 64 * 1024) {
-		const hipError_t e = hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-		if (e != hipSuccess) return e;
-	}
-	// shared grids: persistent workgroups, each builds its tables once, so each should stream several passes; no more than fill the device
-	const int grid = A.f.g.pp ? std::min(groups, 8 * ncu) : std::max(1, std::min((groups + 3) / 4, 8 * ncu));
-	hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * nw), lds, st, A);
-	return hipGetLastError();
+	return launch_cert(ratios_pp_kernel<KM, KR>, ratios_shared_kernel<KM, KR>, A, A.f.g, 64 * A.nw, (A.f.g.batch + A.nw - 1) / A.nw, ncu, lds, st);
 }
 
 // hipErrorInvalidValue: the tables exceed the LDS or the polygons the instances (ntg_batch_ratios refuses such a call before it gets here)

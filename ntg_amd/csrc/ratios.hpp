@@ -19,7 +19,8 @@
 // of the template meets.  The second time the condition was equal bits, no worse registers and a rate within the run-to-run spread: bits and
 // registers held, the ratio instances were even faster, but the single-polygon instances of extrema and separation lost 1 to 2 %.
 // With a denominator of ones the two loops take the same decisions on the same bits (n / 1.0 == n), which tests/test_gpu_ratios.py holds
-// them to; tests/golden/bisect_calls.npz holds both to recorded results.
+// them to; tests/golden/bisect_calls.npz holds both to recorded results.  The loops are kept in step by hand and held in step by the tests:
+// tests/bisect_oracle.py is the one written sequence every level loop of the library is tested against, this one by tests/test_gpu_ratios.py.
 //
 //   ratios_shared_kernel  plans on their own grid: persistent workgroups of four waves (two where four work lists do not fit); the forms'
 //                         product tables, the chains' product tables, the extraction weights and the breaks of every basis class are built once
@@ -348,7 +349,7 @@ ratios_shared_kernel(RatioArgs A)
 		if (b >= F.g.batch) continue;
 		__builtin_amdgcn_wave_barrier();   // the problem before is done with the rows
 		env_stage_rows(F.g, nullptr, b, S.xrow, nullptr, lane, 64);
-		form_stage_fprm(F, b, S.prow, lane);
+		cert_stage_fprm(F.fprm, F.nfp, b, S.prow, lane);
 		__builtin_amdgcn_wave_barrier();
 		ratio_problem<KM, KR>(A, M, pw, b, lane);
 	}
@@ -374,7 +375,7 @@ ratios_pp_kernel(RatioArgs A)
 		const int b = b0 + blockIdx.x * NW + wave;
 		const bool on = b < F.g.batch;
 		__syncthreads();
-		if (on) { env_stage_pp(F.g, nullptr, b, S.kns, S.xrow, nullptr, lane); form_stage_fprm(F, b, S.prow, lane); }
+		if (on) { env_stage_pp(F.g, nullptr, b, S.kns, S.xrow, nullptr, lane); cert_stage_fprm(F.fprm, F.nfp, b, S.prow, lane); }
 		__syncthreads();
 		if (on) env_build(S.kns, C, S.tab + C.eoff, S.tab + C.hoff, lane, 64);
 		__syncthreads();

@@ -9,9 +9,10 @@
 //   level 0   trig_poly on every knot interval j of the form's basis class: per term the entries' polygons as forms.hpp forms a factor
 //             (form_factor, shift 0), times coef, elevated, summed, the phase added.  The LIN terms' weighted polygons are summed into one.
 //   levels    trig_levels: ext_levels (extrema.hpp) on pieces of up to NTG_TRIG_MAXTERMS polygons -- a third twin of that loop, kept in
-//             step by hand like ratio_levels.  A piece is halved polygon by polygon (ext_split); its enclosure (trig_range) and the attained
-//             value at its new end (trig_end) call sincos once per SIN / COS term.  The two outer ends of a parent were taken a level
-//             earlier with the same bits and the same times, so only the middle end is evaluated.
+//             step by hand like ratio_levels, and held in step by the tests: tests/bisect_oracle.py is the one written sequence all of
+//             them are tested against (this one by tests/test_gpu_trig.py).  A piece is halved polygon by polygon (ext_split); its
+//             enclosure (trig_range) and the attained value at its new end (trig_end) call sincos once per SIN / COS term.  The two outer
+//             ends of a parent were taken a level earlier with the same bits and the same times, so only the middle end is evaluated.
 // A work-list element is NTG_TRIG_MAXTERMS polygons of KM doubles and two doubles of padding: every polygon starts at 16 bytes and a lane
 // reads and writes its own piece with 16-byte accesses; the element is an odd number of 16-byte slots.  The list is updated in place as in
 // ext_levels: every parent is in registers (4 KM doubles) before a child is stored.
@@ -343,12 +344,6 @@ __device__ __forceinline__ void trig_problem(const TrigArgs &A, const ExtLds &M,
 	O.problem(b);
 }
 
-// the call's own parameter row of problem b, by one wave
-__device__ __forceinline__ void trig_stage_fprm(const TrigArgs &A, int b, double *frow, int lane)
-{
-	for (int i = lane; i < A.nfp; i += 64) frow[i] = A.fprm[(size_t)b * A.nfp + i];
-}
-
 template <int KM>
 __global__ void __launch_bounds__(256)
 trig_shared_kernel(TrigArgs A)
@@ -364,7 +359,7 @@ trig_shared_kernel(TrigArgs A)
 		if (b >= A.g.batch) continue;
 		__builtin_amdgcn_wave_barrier();   // the problem before is done with the rows
 		env_stage_rows(A.g, nullptr, b, S.xrow, nullptr, lane, 64);
-		trig_stage_fprm(A, b, S.prow, lane);
+		cert_stage_fprm(A.fprm, A.nfp, b, S.prow, lane);
 		__builtin_amdgcn_wave_barrier();
 		trig_problem<KM>(A, M, b, lane);
 	}
@@ -386,7 +381,7 @@ trig_pp_kernel(TrigArgs A)
 		const int b = b0 + blockIdx.x * NW + wave;
 		const bool on = b < A.g.batch;
 		__syncthreads();
-		if (on) { env_stage_pp(A.g, nullptr, b, S.kns, S.xrow, nullptr, lane); trig_stage_fprm(A, b, S.prow, lane); }
+		if (on) { env_stage_pp(A.g, nullptr, b, S.kns, S.xrow, nullptr, lane); cert_stage_fprm(A.fprm, A.nfp, b, S.prow, lane); }
 		__syncthreads();
 		if (on) env_build(S.kns, C, S.tab + C.eoff, S.tab + C.hoff, lane, 64);
 		__syncthreads();

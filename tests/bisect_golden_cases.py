@@ -35,7 +35,7 @@ SEP_CASES = ["%s-d%d" % nd for nd in po.CASES]
 FORM_CASES = [c for c in fo.CASES if c != "MOD"]
 RATIO_CASES = [c for c in ro.CASES if c != "RMOD"]
 CASES = SEP_CASES + FORM_CASES + RATIO_CASES + ["RK100"]
-NAN_RATIOS = [ro.KAPPA2, ro.SLOPE, fm.ratio([2]), fm.ratio([2, 2], [2])]   # the last two name x' alone
+NAN_RATIOS = ro.NAN_RATIOS
 
 
 def rk100():
@@ -105,21 +105,15 @@ def _ratios(res, name):
         _record(res, "r0_fine", lambda: plan.ratios(xd, c.forms, c.ratios, float(c.fine[0])))
         return
     lo, up = median_bounds(c.levels(), c.x.shape[0])
-    xp = c.x.copy()
-    if name == "RK4":
-        n = c.spec.ncoef[0]
-        xp[7, 3:9] = xp[7, 3]; xp[7, n + 3:n + 9] = xp[7, n + 3]   # the six coefficients of knot interval 1, of x and of y
     for r, ratio in enumerate(c.ratios):
         kw = dict(lower=dev(lo[:, r:r + 1]), upper=dev(up[:, r:r + 1]))
         _record(res, "r%d" % r, lambda: plan.ratios(xd, c.forms, [ratio], float(c.tol[r]), **kw))
         _record(res, "r%d_fine" % r, lambda: plan.ratios(xd, c.forms, [ratio], float(c.fine[r]), **kw))
         if name == "RK4":
             _record(res, "r%d_d3" % r, lambda: plan.ratios(xd, c.forms, [ratio], float(c.tol[r]), 3))
-            _record(res, "r%d_park" % r, lambda: plan.ratios(dev(xp), c.forms, [ratio], float(c.tol[r]), **kw))
+            _record(res, "r%d_park" % r, lambda: plan.ratios(dev(ro.parked_x(c)), c.forms, [ratio], float(c.tol[r]), **kw))
     if name == "RK4":
-        xn = c.x.copy()
-        xn[5, c.spec.ncoef[0] + 1] = np.nan   # a coefficient of y on the first knot interval of problem 5
-        _record(res, "nan", lambda: plan.ratios(dev(xn), c.forms, NAN_RATIOS, float(c.tol[0])))
+        _record(res, "nan", lambda: plan.ratios(dev(ro.nan_x(c)), c.forms, ro.NAN_RATIOS, float(c.tol[0])))
 
 
 def run_case(name):

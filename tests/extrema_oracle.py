@@ -1,7 +1,8 @@
 """ntg_batch_extrema's definition (include/ntg_amd.h) for the tests, and the inputs the CPU and GPU tests share.
 
-  level_oracle   the level algorithm of the definition in float64, on level-0 polygons handed in: from row_polygons (numpy: the interval
-                 polygons of envelope_oracle, differenced, multiplied by the Bezier product, elevated, summed) or from exact_polygons rounded.
+  level_oracle   the level algorithm of the definition in float64 (bisect_oracle.levels), on level-0 polygons handed in: from row_polygons
+                 (numpy: the interval polygons of envelope_oracle, differenced, multiplied by the Bezier product, elevated, summed) or from
+                 exact_polygons rounded.
   exact_extrema  the true minimum and maximum of a row in fractions.Fraction: rational bisection of the exact level-0 Bernstein polygons
                  (the polynomials of envelope_sos_oracle's de Boor recursion, converted once), until the enclosure is narrower than eps.
   slack          2 * envelope_sos_oracle.sos_slack for a quadratic row (2^-39 sum_t S_t^2), 2 * envelope_oracle.row_slack for a linear one.
@@ -10,17 +11,17 @@ Rows are numbered as ntg_batch_check numbers them: the nltc linear trajectory ro
 """
 import dataclasses
 from fractions import Fraction as Fr
-from math import comb, inf, isnan, nan
+from math import comb
 
 import numpy as np
 
+import bisect_oracle as bo
 import envelope_oracle as eo
 import envelope_sos_oracle as so
+from bisect_oracle import CAP, DEPTH, FULL, MAX_DEPTH, NAN, NONE, OK   # (the tests take them from here)
 from cert_common import field_x, greville, obstacle_x, rows_spec, scaled_grids   # (the tests and tools take them from here too)
 from ntg_amd import configs as cf
 
-OK, DEPTH, FULL, NAN, NONE = 0, 1, 2, 3, -1
-CAP, MAX_DEPTH = 64, 30
 
 
 # ---------------- rows ----------------
@@ -136,53 +137,9 @@ def exact_polygons(spec, xb, pb=None, kb=None):
 
 # ---------------- the definition ----------------
 def level_oracle(polys, kn, tol, max_depth=MAX_DEPTH, sides=3, cap=CAP):
-    """one row of one problem: polys [l][D + 1] floats, kn [l + 1] its breaks.  Returns a dict: ext (min_lo, min_hi, max_lo, max_hi), when
-    (t_min, t_max), status, npieces, and for the tests depth (the last level evaluated) and max_open (the most open pieces at a level)"""
-    kn = [float(v) for v in kn]
-    hh = [kn[j + 1] - kn[j] for j in range(len(kn) - 1)]
-    U, tU, V, tV = inf, inf, -inf, inf
-    Rlo, Rhi = inf, -inf
-    anynan = False
-    pieces = [(j, 0, [float(v) for v in polys[j]]) for j in range(len(polys))]
-    npieces, lam, max_open = 0, 0, 0
-    while True:
-        npieces += len(pieces)
-        for j, i, B in pieces:
-            for v, t in ((B[0], kn[j] + hh[j] * (float(i) / float(1 << lam))), (B[-1], kn[j + 1] if i + 1 == (1 << lam) else kn[j] + hh[j] * (float(i + 1) / float(1 << lam)))):
-                if v < U or (v == U and t < tU):
-                    U, tU = v, t
-                if v > V or (v == V and t < tV):
-                    V, tV = v, t
-        opened, hull = [], []
-        for j, i, B in pieces:
-            if any(isnan(v) for v in B):
-                anynan = True
-                continue
-            plo, phi = min(B), max(B)
-            if ((sides & 1) and plo < U - tol) or ((sides & 2) and phi > V + tol):
-                opened.append((j, i, B)); hull.append((plo, phi))
-            else:
-                Rlo, Rhi = min(Rlo, plo), max(Rhi, phi)
-        max_open = max(max_open, len(opened))
-        if not opened:
-            status = OK
-            break
-        if lam == max_depth or len(opened) > cap:
-            status = DEPTH if lam == max_depth else FULL
-            Rlo, Rhi = min([Rlo] + [h[0] for h in hull]), max([Rhi] + [h[1] for h in hull])
-            break
-        pieces = []
-        for j, i, B in opened:
-            R, L = list(B), [B[0]]
-            for r in range(1, len(B)):
-                for s in range(len(B) - r):
-                    R[s] = 0.5 * (R[s] + R[s + 1])
-                L.append(R[0])
-            pieces += [(j, 2 * i, L), (j, 2 * i + 1, R)]
-        lam += 1
-    if anynan:
-        return dict(ext=(nan,) * 4, when=(nan, nan), status=NAN, npieces=npieces, depth=lam, max_open=max_open)
-    return dict(ext=(Rlo, U, V, Rhi), when=(tU, tV), status=status, npieces=npieces, depth=lam, max_open=max_open)
+    """one row of one problem: polys [l][D + 1] floats, kn [l + 1] its breaks.  bisect_oracle.levels on single polygons: a dict with ext
+    (min_lo, min_hi, max_lo, max_hi), when (t_min, t_max), status, npieces, and for the tests depth, max_open and margin"""
+    return bo.levels(bo.POLYGON, [[float(v) for v in B] for B in polys], kn, tol, max_depth, sides, cap)
 
 
 def _exact_min(polys, eps):

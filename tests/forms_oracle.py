@@ -2,7 +2,7 @@
 
   product         the Bezier product of two polygons of degrees d and e in float64: g_m = sum_{i + j = m} W_{d,e}[i][j] p_i q_j, i ascending.
   form_polygons   level-0 polygons of every form: the interval polygons of envelope_oracle, differenced, shifted, multiplied, weighted,
-                  elevated and summed in declared order.  The levels are extrema_oracle.level_oracle, imported, not copied.
+                  elevated and summed in declared order.  The levels are extrema_oracle.level_oracle: bisect_oracle.levels on single polygons.
   exact_polygons  the same polynomials in fractions.Fraction through envelope_sos_oracle's rational machinery (de Boor's recursion on
                   polynomials, power basis, one conversion to the Bernstein basis at the form's degree), extended here to products;
                   extrema_oracle.exact_extrema then gives the true minimum and maximum.
@@ -19,11 +19,10 @@ import numpy as np
 import envelope_oracle as eo
 import envelope_sos_oracle as so
 import extrema_oracle as xo
+from bisect_oracle import DEPTH, FULL, NAN, OK, violation   # (the tests take them from here)
 from cert_common import full_list_problem, greville, scaled_grids
 from ntg_amd import configs as cf, forms as fm
 
-OK, DEPTH, FULL, NAN = xo.OK, xo.DEPTH, xo.FULL, xo.NAN
-INF_BOUND = cf.INF_BOUND
 
 
 def product(P, Q):
@@ -159,56 +158,10 @@ def values(spec, z, forms, fprm=None):
     return out
 
 
-def violation(ext, lo, up):
-    """(viol [2], where [2]) of one problem from ext [nform][4] and the forms' bounds: rule 7 of ntg_batch_extrema"""
-    viol, where = [0.0, 0.0], [-1, -1]
-    for side, (a, b) in enumerate(((1, 2), (0, 3))):
-        for f in range(len(ext)):
-            v = 0.0
-            if abs(lo[f]) < INF_BOUND:
-                v = max(v, lo[f] - ext[f][a])
-            if abs(up[f]) < INF_BOUND:
-                v = max(v, ext[f][b] - up[f])
-            if v > viol[side]:
-                viol[side], where[side] = v, f
-    return viol, where
-
-
-# ---------------- how far the oracle's decisions are from their limits ----------------
-class _Limit:
-    """U - tol or V + tol inside extrema_oracle.level_oracle: compares like the float it holds, and keeps the smallest distance of a compared value"""
-    def __init__(self, v, rec):
-        self.v, self.rec = v, rec
-
-    def _seen(self, other):
-        self.rec[0] = min(self.rec[0], abs(other - self.v))
-
-    def __gt__(self, other):   # plo < U - tol
-        self._seen(other)
-        return self.v > other
-
-    def __lt__(self, other):   # phi > V + tol
-        self._seen(other)
-        return self.v < other
-
-
-class _Tol:
-    """a tolerance that hands level_oracle its limits as _Limit: the level loop itself stays extrema_oracle's"""
-    def __init__(self, t):
-        self.t, self.rec = t, [np.inf]
-
-    def __rsub__(self, U):
-        return _Limit(U - self.t, self.rec)
-
-    def __radd__(self, V):
-        return _Limit(V + self.t, self.rec)
-
-
 def decision_margin(polys, kn, tol, max_depth=xo.MAX_DEPTH, sides=3):
-    """(the smallest |plo - (U - tol)| or |phi - (V + tol)| over every comparison level_oracle makes, its result)"""
-    t = _Tol(tol)
-    r = xo.level_oracle(polys, kn, t, max_depth, sides)
-    return t.rec[0], r
+    """(the smallest |plo - (U - tol)| or |phi - (V + tol)| over every decision level_oracle makes, its result)"""
+    r = xo.level_oracle(polys, kn, tol, max_depth, sides)
+    return r["margin"], r
 
 
 # ---------------- the inputs of the tests ----------------

@@ -4,9 +4,9 @@
             c = 0.0 adds nothing), elevated to the group's degree (rule 1).
   lattice   OUTER_k INNER_j of one figure per member, with the member that decides it (ties: smallest index, smallest clause) and `gap`,
             the smallest difference that, reversed, would name another member.
-  levels    the level loop of ntg_batch_extrema on those pieces with the enclosure of rule 2 and the ends of rule 3.  It records the depth,
-            the most pieces open at a level, `margin` (the smallest distance of any open / retire decision from its limit) and `tie` (the
-            lattice gap at the two ends that are returned).
+  levels    the level loop of ntg_batch_extrema (bisect_oracle.levels) on those pieces with the enclosure of rule 2 and the ends of rule 3.
+            It records the depth, the most pieces open at a level, `margin` (the smallest distance of any open / retire decision from its
+            limit) and `tie` (the lattice gap at the two ends that are returned).
   slack     max over the members of 2^-39 (M_f + |d|), M_f forms_oracle's sum.
   values    the groups from flag values, for the sampled extrema.
 
@@ -15,18 +15,17 @@ which its path can still go wrong.
 """
 import dataclasses
 import math
-from math import inf, isnan, nan
+from math import inf, nan
 
 import numpy as np
 
+import bisect_oracle as bo
 import envelope_oracle as eo
 import forms_oracle as fo
+from bisect_oracle import CAP, DEPTH, FULL, MAX_DEPTH, NAN, OK, violation   # (the tests take them from here)
 from cert_common import full_list_problem, greville, scaled_grids
 from ntg_amd import configs as cf, forms as fm, minmax as mm
 
-OK, DEPTH, FULL, NAN = 0, 1, 2, 3
-CAP, MAX_DEPTH = 64, 30
-INF_BOUND = cf.INF_BOUND
 MIN, MAX = mm.MIN, mm.MAX
 
 
@@ -104,60 +103,11 @@ def enclose(group, B):
 
 
 def levels(group, polys, kn, tol, max_depth=MAX_DEPTH, sides=3, cap=CAP):
-    """one group of one problem: polys [l, nm, D + 1], kn [l + 1].  extrema_oracle.level_oracle's loop on pieces of several polygons.  Returns
-    ext, when, which, status, npieces and for the tests depth, max_open, margin and tie"""
-    kn = [float(v) for v in kn]
-    hh = [kn[j + 1] - kn[j] for j in range(len(kn) - 1)]
-    U, tU, wU, gU, V, tV, wV, gV = inf, inf, -1, inf, -inf, inf, -1, inf
-    Rlo, Rhi = inf, -inf
-    anynan = False
-    pieces = [(j, 0, np.array(polys[j], dtype=np.float64)) for j in range(len(polys))]
-    npieces, lam, max_open, margin = 0, 0, 0, inf
-    while True:
-        npieces += len(pieces)
-        for j, i, B in pieces:
-            for col, t in ((0, kn[j] + hh[j] * (float(i) / float(1 << lam))), (-1, kn[j + 1] if i + 1 == (1 << lam) else kn[j] + hh[j] * (float(i + 1) / float(1 << lam)))):
-                v, w, gap = lattice(group, B[:, col])
-                if v < U or (v == U and (t < tU or (t == tU and w < wU))):
-                    U, tU, wU, gU = v, t, w, gap
-                if v > V or (v == V and (t < tV or (t == tV and w < wV))):
-                    V, tV, wV, gV = v, t, w, gap
-        opened, hull = [], []
-        for j, i, B in pieces:
-            plo, phi = enclose(group, B)
-            if isnan(plo) or isnan(phi):
-                anynan = True
-                continue
-            if sides & 1:
-                margin = min(margin, abs(plo - (U - tol)))
-            if sides & 2:
-                margin = min(margin, abs(phi - (V + tol)))
-            if ((sides & 1) and plo < U - tol) or ((sides & 2) and phi > V + tol):
-                opened.append((j, i, B)); hull.append((plo, phi))
-            else:
-                Rlo, Rhi = min(Rlo, plo), max(Rhi, phi)
-        max_open = max(max_open, len(opened))
-        if not opened:
-            status = OK
-            break
-        if lam == max_depth or len(opened) > cap:
-            status = DEPTH if lam == max_depth else FULL
-            Rlo, Rhi = min([Rlo] + [h[0] for h in hull]), max([Rhi] + [h[1] for h in hull])
-            break
-        pieces = []
-        for j, i, B in opened:
-            R, L = B.copy(), np.empty_like(B)
-            L[:, 0] = B[:, 0]
-            n = B.shape[1]
-            for r in range(1, n):
-                R[:, :n - r] = 0.5 * (R[:, :n - r] + R[:, 1:n - r + 1])
-                L[:, r] = R[:, 0]
-            pieces += [(j, 2 * i, L), (j, 2 * i + 1, R)]
-        lam += 1
-    extra = dict(npieces=npieces, depth=lam, max_open=max_open, margin=margin, tie=min(gU, gV))
-    if anynan:
-        return dict(ext=(nan,) * 4, when=(nan, nan), which=(-1, -1), status=NAN, **extra)
-    return dict(ext=(Rlo, U, V, Rhi), when=(tU, tV), which=(wU, wV), status=status, **extra)
+    """one group of one problem: polys [l, nm, D + 1], kn [l + 1].  bisect_oracle.levels on pieces of several polygons: the deciding member
+    breaks the ties of the ends and its lattice gap is carried along.  Returns ext, when, which, status, npieces and for the tests depth,
+    max_open, margin and tie"""
+    kind = (lambda B: [lattice(group, B[:, col]) for col in (0, -1)], lambda B: enclose(group, B), bo.halve)
+    return bo.levels(kind, [np.array(P, dtype=np.float64) for P in polys], kn, tol, max_depth, sides, cap)
 
 
 def slack(spec, x, forms, groups, fprm=None, knots=None):
@@ -193,9 +143,6 @@ def fold(group, mv):
 def values(spec, z, forms, groups, fprm=None):
     """the groups from flag values z [nb, nt, nz] in double precision: [nb, nt, ngroup]"""
     return np.stack([fold(g, member_values(spec, z, forms, g, fprm)) for g in groups], axis=2)
-
-
-violation = fo.violation   # (viol [2], where [2]) of one problem from ext [ngroup][4] and the groups' bounds: rule 7 of ntg_batch_extrema
 
 
 def negated(forms, groups, fprm):

@@ -2,9 +2,9 @@
 
   pair_polygons   level-0 pairs of every ratio in float64: forms_oracle.form_polygons of the forms, each side the chain of
                   forms_oracle.product (the chain so far times the next form), the lower side raised by envelope_oracle.elevate.
-  level_oracle    the level algorithm on pairs: extrema_oracle.level_oracle's sequence with the pair rule -- quotients of the points where every
-                  denominator point is positive, (-inf, +inf) otherwise; an end with denominator <= 0 stops the loop: POLE.  It records how far
-                  every decision was from its limit (margin), the smallest denominator point and the largest quotient of the retired pieces.
+  level_oracle    the level algorithm (bisect_oracle.levels) on pairs, with the pair rule -- quotients of the points where every denominator
+                  point is positive, (-inf, +inf) otherwise; an end with denominator <= 0 stops the loop: POLE.  It records how far every
+                  decision was from its limit (margin), the smallest denominator point and the largest quotient of the retired pieces.
   exact_extrema   the true minimum and maximum of a ratio in exact arithmetic: forms_oracle.exact_polygons multiplied and elevated in Fractions,
                   then bisected on integers (both polygons of a pair scaled alike) until the enclosure is narrower than eps.
   slack           the header's rounding statement: eps_side = prod m_f (sum delta_f / m_f + 2^-43), (eps_N + |rho| eps_D) / (d_min - eps_D).
@@ -18,13 +18,14 @@ from math import comb, inf, isnan, nan
 
 import numpy as np
 
+import bisect_oracle as bo
 import envelope_oracle as eo
 import extrema_oracle as xo
 import forms_oracle as fo
+from bisect_oracle import DEPTH, FULL, NAN, OK, POLE, violation   # (the tests take them from here)
 from cert_common import scaled_grids
 from ntg_amd import configs as cf, forms as fm
 
-OK, DEPTH, FULL, NAN, POLE = xo.OK, xo.DEPTH, xo.FULL, xo.NAN, 4
 MAXDEG = 24
 # Every case runs at two tolerances per ratio.  `tol`, in slacks of its worst problem: there every decision of the oracle stays 16 slacks of
 # its own problem away from its limit (tests/test_ratios_oracle.py), so equal status and npieces follow from the rounding statement alone; a
@@ -68,89 +69,38 @@ def pair_polygons(spec, x, forms, ratios, fprm=None, knots=None):
 
 
 # ---------------- the definition ----------------
-def _quotients(N, Q):
-    """(plo, phi, is NaN) of a pair"""
+def _quotients(P):
+    """(plo, phi) of a pair"""
+    N, Q = P
     if any(isnan(v) for v in N) or any(isnan(v) for v in Q):
-        return nan, nan, True
+        return nan, nan
     if all(d > 0.0 for d in Q):
         rho = [n / d for n, d in zip(N, Q)]
-        return min(rho), max(rho), False
-    return -inf, inf, False
+        return min(rho), max(rho)
+    return -inf, inf
+
+
+def _end_quotients(P):
+    """the quotients at the two ends; a denominator <= 0 there is a pole, a NaN there is never taken"""
+    N, Q = P
+    return [(None if d <= 0.0 else n / d, 0, inf) for n, d in ((N[0], Q[0]), (N[-1], Q[-1]))]
+
+
+PAIR = (_end_quotients, _quotients, lambda P: tuple(zip(bo.halve(P[0]), bo.halve(P[1]))))   # pieces: (N, Q), lists of floats
 
 
 def level_oracle(N0, Q0, kn, tol, max_depth=xo.MAX_DEPTH, sides=3, cap=xo.CAP):
-    """one ratio of one problem: N0, Q0 [l][DR + 1] floats, kn [l + 1] its breaks.  Returns extrema_oracle.level_oracle's dict, and margin (the
-    smallest |plo - (U - tol)| or |phi - (V + tol)| over every comparison made with a finite plo / phi), dmin (the smallest denominator point
-    of the retired pieces) and rmax (the largest |quotient| of the retired pieces and the ends taken)"""
-    kn = [float(v) for v in kn]
-    hh = [kn[j + 1] - kn[j] for j in range(len(kn) - 1)]
-    U, tU, V, tV = inf, inf, -inf, inf
-    Rlo, Rhi = inf, -inf
-    anynan = pole = False
-    margin, dmin = inf, inf
-    pieces = [(j, 0, [float(v) for v in N0[j]], [float(v) for v in Q0[j]]) for j in range(len(N0))]
-    npieces, lam, max_open = 0, 0, 0
-    status = OK
-    while True:
-        npieces += len(pieces)
-        for j, i, N, Q in pieces:
-            t0 = kn[j] + hh[j] * (float(i) / float(1 << lam))
-            t1 = kn[j + 1] if i + 1 == (1 << lam) else kn[j] + hh[j] * (float(i + 1) / float(1 << lam))
-            for n, d, t in ((N[0], Q[0], t0), (N[-1], Q[-1], t1)):
-                if d > 0.0:
-                    v = n / d
-                    if v < U or (v == U and t < tU):
-                        U, tU = v, t
-                    if v > V or (v == V and t < tV):
-                        V, tV = v, t
-                elif d <= 0.0:
-                    pole = True
-        opened, hull = [], []
-        for j, i, N, Q in pieces:
-            plo, phi, isn = _quotients(N, Q)
-            if isn:
-                anynan = True
-                continue
-            if pole:
-                continue
-            if plo > -inf:
-                if sides & 1:
-                    margin = min(margin, abs(plo - (U - tol)))
-                if sides & 2:
-                    margin = min(margin, abs(phi - (V + tol)))
-            if ((sides & 1) and plo < U - tol) or ((sides & 2) and phi > V + tol):
-                opened.append((j, i, N, Q)); hull.append((plo, phi))
-            else:
-                Rlo, Rhi = min(Rlo, plo), max(Rhi, phi)
-                dmin = min(dmin, min(Q))
-        if pole:
-            break
-        max_open = max(max_open, len(opened))
-        if not opened:
-            break
-        if lam == max_depth or len(opened) > cap:
-            status = DEPTH if lam == max_depth else FULL
-            Rlo, Rhi = min([Rlo] + [h[0] for h in hull]), max([Rhi] + [h[1] for h in hull])
-            dmin = min([dmin] + [min(Q) for _, _, _, Q in opened])
-            break
-        pieces = []
-        for j, i, N, Q in opened:
-            halves = []
-            for B in (N, Q):
-                R, L = list(B), [B[0]]
-                for r in range(1, len(B)):
-                    for s in range(len(B) - r):
-                        R[s] = 0.5 * (R[s] + R[s + 1])
-                    L.append(R[0])
-                halves.append((L, R))
-            pieces += [(j, 2 * i, halves[0][0], halves[1][0]), (j, 2 * i + 1, halves[0][1], halves[1][1])]
-        lam += 1
-    extra = dict(npieces=npieces, depth=lam, max_open=max_open, margin=margin, dmin=dmin)
-    if anynan:
-        return dict(ext=(nan,) * 4, when=(nan, nan), status=NAN, rmax=nan, **extra)
-    if pole:
-        return dict(ext=(-inf, inf, -inf, inf), when=(nan, nan), status=POLE, rmax=inf, **extra)
-    return dict(ext=(Rlo, U, V, Rhi), when=(tU, tV), status=status, rmax=max(abs(Rlo), abs(Rhi), abs(U), abs(V)), **extra)
+    """one ratio of one problem: N0, Q0 [l][DR + 1] floats, kn [l + 1] its breaks.  bisect_oracle.levels on pairs: its dict (margin over every
+    decision made with a finite plo / phi), and dmin (the smallest denominator point of the retired pieces) and rmax (the largest
+    |quotient| of the retired pieces and the ends taken)"""
+    dmin = [inf]
+
+    def retired(P):
+        dmin[0] = min(dmin[0], min(P[1]))
+
+    r = bo.levels(PAIR, [([float(v) for v in N], [float(v) for v in Q]) for N, Q in zip(N0, Q0)], kn, tol, max_depth, sides, cap, retired=retired)
+    r.update(dmin=dmin[0], rmax=nan if r["status"] == NAN else inf if r["status"] == POLE else max(abs(v) for v in r["ext"]))
+    return r
 
 
 # ---------------- exact arithmetic ----------------
@@ -280,10 +230,6 @@ def values(spec, z, forms, ratios, fprm=None):
     return out
 
 
-def violation(ext, lo, up):
-    return fo.violation(ext, lo, up)
-
-
 # ---------------- the inputs of the tests ----------------
 @dataclasses.dataclass
 class Inputs:
@@ -373,3 +319,21 @@ def inputs(name, family=0):
                    [fm.ratio([1], [0]), fm.ratio([0, 0])])
     _inputs[name] = c.finish()
     return c
+
+
+NAN_RATIOS = [KAPPA2, SLOPE, fm.ratio([2]), fm.ratio([2, 2], [2])]   # the last two name x' alone
+
+
+def parked_x(c):
+    """RK4's x with problem 7 standing still on knot interval 1 (its six coefficients there equal, of x and of y): a pole where the ratio has
+    a denominator"""
+    xp, n = c.x.copy(), c.spec.ncoef[0]
+    xp[7, 3:9] = xp[7, 3]; xp[7, n + 3:n + 9] = xp[7, n + 3]
+    return xp
+
+
+def nan_x(c):
+    """RK4's x with a NaN coefficient of y on the first knot interval of problem 5: of NAN_RATIOS the first two name y"""
+    xn = c.x.copy()
+    xn[5, c.spec.ncoef[0] + 1] = np.nan
+    return xn

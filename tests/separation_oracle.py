@@ -3,8 +3,8 @@
   deltas         the difference coefficients of every pair, [npairs, ndim, n]: one subtraction each.
   pair_polygons  level-0 polygons of the squared distance in float64: the interval polygons of envelope_oracle on delta, differenced,
                  squared by extrema_oracle.square, summed in dimension order.
-  level_sep      the level algorithm with the threshold rule: a piece is open iff plo < U - tol and not plo >= s2.  Without a threshold
-                 (s2 = +inf) it is extrema_oracle.level_oracle at sides = 1, which tests/test_separation_oracle.py checks bit for bit.
+  level_sep      the level algorithm (bisect_oracle.levels) at sides = 1 with the threshold rule: a piece is open iff plo < U - tol and not
+                 plo >= s2.  Without a threshold (s2 = +inf) it is extrema_oracle.level_oracle at sides = 1.
   slack          2^-39 sum_t S_t^2 with S_t = max_i (|x_a,i| + |x_b,i|) (2 (k - 1) / h_min)^deriv.
   exact_min      the true minimum in fractions.Fraction: extrema_oracle.exact_polygons / exact_extrema on a two-output obstacle-field spec
                  given delta (positions in the plane), the same polynomials summed here for every other case.
@@ -15,12 +15,13 @@ from math import inf, isnan, nan
 
 import numpy as np
 
+import bisect_oracle as bo
 import envelope_oracle as eo
 import envelope_sos_oracle as so
 import extrema_oracle as xo
+from bisect_oracle import BADPAIR, DEPTH, FULL, NAN, OK   # (the tests take them from here)
 from ntg_amd import configs as cf
 
-OK, DEPTH, FULL, NAN, BADPAIR = xo.OK, xo.DEPTH, xo.FULL, xo.NAN, -2
 MAXDIM = 4
 
 
@@ -45,48 +46,8 @@ def pair_polygons(spec, dl, o0, deriv):
 def level_sep(polys, kn, tol, s2=inf, max_depth=xo.MAX_DEPTH, cap=xo.CAP):
     """one pair: polys [l][D + 1] floats, kn [l + 1] the breaks.  Returns a dict: min (min_lo, min_hi), when, status, npieces and, for the
     tests, depth (the last level evaluated) and max_open (the most open pieces at a level)"""
-    kn = [float(v) for v in kn]
-    hh = [kn[j + 1] - kn[j] for j in range(len(kn) - 1)]
-    U, tU, Rlo = inf, inf, inf
-    anynan = False
-    pieces = [(j, 0, [float(v) for v in polys[j]]) for j in range(len(polys))]
-    npieces, lam, max_open = 0, 0, 0
-    while True:
-        npieces += len(pieces)
-        for j, i, B in pieces:
-            for v, t in ((B[0], kn[j] + hh[j] * (float(i) / float(1 << lam))), (B[-1], kn[j + 1] if i + 1 == (1 << lam) else kn[j] + hh[j] * (float(i + 1) / float(1 << lam)))):
-                if v < U or (v == U and t < tU):
-                    U, tU = v, t
-        opened = []
-        for j, i, B in pieces:
-            if any(isnan(v) for v in B):
-                anynan = True
-                continue
-            plo = min(B)
-            if plo < U - tol and not plo >= s2:
-                opened.append((j, i, B, plo))
-            else:
-                Rlo = min(Rlo, plo)
-        max_open = max(max_open, len(opened))
-        if not opened:
-            status = OK
-            break
-        if lam == max_depth or len(opened) > cap:
-            status = DEPTH if lam == max_depth else FULL
-            Rlo = min([Rlo] + [p[3] for p in opened])
-            break
-        pieces = []
-        for j, i, B, _ in opened:
-            R, L = list(B), [B[0]]
-            for r in range(1, len(B)):
-                for s in range(len(B) - r):
-                    R[s] = 0.5 * (R[s] + R[s + 1])
-                L.append(R[0])
-            pieces += [(j, 2 * i, L), (j, 2 * i + 1, R)]
-        lam += 1
-    if anynan:
-        return dict(min=(nan, nan), when=nan, status=NAN, npieces=npieces, depth=lam, max_open=max_open)
-    return dict(min=(Rlo, U), when=tU, status=status, npieces=npieces, depth=lam, max_open=max_open)
+    r = bo.levels(bo.POLYGON, [[float(v) for v in B] for B in polys], kn, tol, max_depth, 1, cap, s2)
+    return dict(min=r["ext"][:2], when=r["when"][0], status=r["status"], npieces=r["npieces"], depth=r["depth"], max_open=r["max_open"])
 
 
 def violation(mn, s2):

@@ -2,8 +2,8 @@
 
   pieces0   level-0 pieces of every form: per term the entries' interval polygons of envelope_oracle, differenced, times coef, elevated,
             summed, the phase added; the LIN terms' weighted polygons summed into one (rule 1).
-  levels    the level loop of ntg_batch_extrema on those pieces with the enclosure of rule 2 and the ends of rule 3.  It records the depth,
-            the most pieces open at a level, and the smallest margin of any open / retire decision.
+  levels    the level loop of ntg_batch_extrema (bisect_oracle.levels) on those pieces with the enclosure of rule 2 and the ends of rule 3.
+            It records the depth, the most pieces open at a level, and the smallest margin of any open / retire decision.
   slack     2^-39 sum_t |w_t| (1 + A_t), A_t = |phase| + |fprm[pp]| + sum_i |coef_i| S_i, S_i as in forms_oracle; a term with A_t > 2^11 adds
             2^-51 |w_t| A_t^2.
   values    the forms from flag values, for the sampled extrema.
@@ -11,18 +11,17 @@
 A form is a list of ntg_amd.trig.Term.  Shapes are small: each case is the smallest at which its path can still go wrong.
 """
 import dataclasses
-from math import inf, isnan, nan
+from math import inf, nan
 
 import numpy as np
 
+import bisect_oracle as bo
 import envelope_oracle as eo
 import envelope_sos_oracle as so
+from bisect_oracle import CAP, DEPTH, FULL, MAX_DEPTH, NAN, OK, violation   # (the tests take them from here)
 from cert_common import full_list_problem, scaled_grids
 from ntg_amd import configs as cf, trig as tg
 
-OK, DEPTH, FULL, NAN = 0, 1, 2, 3
-CAP, MAX_DEPTH = 64, 30
-INF_BOUND = cf.INF_BOUND
 SIN, COS, LIN = tg.SIN, tg.COS, tg.LIN
 
 
@@ -129,60 +128,10 @@ def end_value(meta, B, last):
 
 
 def levels(meta, polys, kn, tol, max_depth=MAX_DEPTH, sides=3, cap=CAP):
-    """one form of one problem: polys [l, np, D + 1], kn [l + 1].  extrema_oracle.level_oracle's loop on pieces of several polygons.  Returns
-    ext, when, status, npieces and for the tests depth, max_open and margin (the smallest distance of a compared plo / phi from its limit)"""
-    kn = [float(v) for v in kn]
-    hh = [kn[j + 1] - kn[j] for j in range(len(kn) - 1)]
-    U, tU, V, tV = inf, inf, -inf, inf
-    Rlo, Rhi = inf, -inf
-    anynan = False
-    pieces = [(j, 0, np.array(polys[j], dtype=np.float64)) for j in range(len(polys))]
-    npieces, lam, max_open, margin = 0, 0, 0, inf
-    while True:
-        npieces += len(pieces)
-        for j, i, B in pieces:
-            for v, t in ((end_value(meta, B, False), kn[j] + hh[j] * (float(i) / float(1 << lam))),
-                         (end_value(meta, B, True), kn[j + 1] if i + 1 == (1 << lam) else kn[j] + hh[j] * (float(i + 1) / float(1 << lam)))):
-                if v < U or (v == U and t < tU):
-                    U, tU = v, t
-                if v > V or (v == V and t < tV):
-                    V, tV = v, t
-        opened, hull = [], []
-        for j, i, B in pieces:
-            plo, phi = enclose(meta, B)
-            if isnan(plo) or isnan(phi):
-                anynan = True
-                continue
-            if sides & 1:
-                margin = min(margin, abs(plo - (U - tol)))
-            if sides & 2:
-                margin = min(margin, abs(phi - (V + tol)))
-            if ((sides & 1) and plo < U - tol) or ((sides & 2) and phi > V + tol):
-                opened.append((j, i, B)); hull.append((plo, phi))
-            else:
-                Rlo, Rhi = min(Rlo, plo), max(Rhi, phi)
-        max_open = max(max_open, len(opened))
-        if not opened:
-            status = OK
-            break
-        if lam == max_depth or len(opened) > cap:
-            status = DEPTH if lam == max_depth else FULL
-            Rlo, Rhi = min([Rlo] + [h[0] for h in hull]), max([Rhi] + [h[1] for h in hull])
-            break
-        pieces = []
-        for j, i, B in opened:
-            R, L = B.copy(), np.empty_like(B)
-            L[:, 0] = B[:, 0]
-            n = B.shape[1]
-            for r in range(1, n):
-                R[:, :n - r] = 0.5 * (R[:, :n - r] + R[:, 1:n - r + 1])
-                L[:, r] = R[:, 0]
-            pieces += [(j, 2 * i, L), (j, 2 * i + 1, R)]
-        lam += 1
-    extra = dict(npieces=npieces, depth=lam, max_open=max_open, margin=margin)
-    if anynan:
-        return dict(ext=(nan,) * 4, when=(nan, nan), status=NAN, **extra)
-    return dict(ext=(Rlo, U, V, Rhi), when=(tU, tV), status=status, **extra)
+    """one form of one problem: polys [l, np, D + 1], kn [l + 1].  bisect_oracle.levels on pieces of several polygons.  Returns ext, when,
+    status, npieces and for the tests depth, max_open and margin (the smallest distance of a compared plo / phi from its limit)"""
+    kind = (lambda B: [(end_value(meta, B, last), 0, inf) for last in (False, True)], lambda B: enclose(meta, B), bo.halve)
+    return bo.levels(kind, [np.array(P, dtype=np.float64) for P in polys], kn, tol, max_depth, sides, cap)
 
 
 def slack(spec, x, forms, fprm=None, knots=None):
@@ -215,21 +164,6 @@ def values(spec, z, forms, fprm=None):
             th = sum(c * z[:, :, v] for v, c in zip(t.ent, t.coef)) + (t.phase + _param(t, fprm, z.shape[0]))[:, None]
             out[:, :, f] += t.w * (np.sin(th) if t.kind == SIN else np.cos(th) if t.kind == COS else th)
     return out
-
-
-def violation(ext, lo, up):
-    """(viol [2], where [2]) of one problem from ext [nform][4] and the forms' bounds: rule 7 of ntg_batch_extrema"""
-    viol, where = [0.0, 0.0], [-1, -1]
-    for side, (a, b) in enumerate(((1, 2), (0, 3))):
-        for f in range(len(ext)):
-            v = 0.0
-            if abs(lo[f]) < INF_BOUND:
-                v = max(v, lo[f] - ext[f][a])
-            if abs(up[f]) < INF_BOUND:
-                v = max(v, ext[f][b] - up[f])
-            if v > viol[side]:
-                viol[side], where[side] = v, f
-    return viol, where
 
 
 # ---------------- the inputs of the tests ----------------
